@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: transductive tasks/sec of the EM-Dirichlet hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Headline workload = the north-star shape, BASELINE.json configs[3] as it lands on one GPU:
@@ -47,12 +47,6 @@ import json
 import os
 import sys
 import time
-
-# Independent batches run on up to three HIP streams; HIP gives a process four hardware queues by default and RCCL's
-# own streams take some of them under torch.distributed, after which the engine's streams share a queue and
-# serialise (measured with one rank under torch.distributed.run: K=100 1 641 tasks/s against 2 119 with 8 queues,
-# which is also the rate without a process group).  Read when the HIP runtime initialises, so set before torch.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -319,6 +313,44 @@ def write_record(full):
     return rel
 
 
+DUMP_BUDGET = 64 << 20      # bytes: everything --dump-outputs writes
+DUMP_FULL = 1 << 21         # elements: a method array up to this size is written in full ...
+DUMP_SAMPLE = 1 << 20       # ... a larger one as this many seeded draws of its elements (duplicates dropped)
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, ev, acc_mean):
+    """What the timed path delivered in its last step, one float32 / float64 .npy file per array: the gathered per-task
+    results of `evaluate_tasks` (accuracies, predicted class per query, per-batch criterions and MM counts) and the
+    engine's outputs of the method object (v in full; alpha and u - 5 GB and 375 MB at the headline - as a seeded
+    uniform sample of about a million elements each: `<name>_sample.npy`, with the flat indices it took in
+    `<name>_sample_index.npy`).  Integers are stored as float32 (exact: predictions < K and MM counts <= iter_mm) and
+    indices as float64 (exact below 2^53).  Returns {file name: shape}."""
+    import numpy as np
+    m = ev.last_method
+    arrays = {"mean_accuracy": np.asarray(acc_mean, dtype=np.float64),
+              "task_accuracies": np.asarray(ev.last_task_accuracies, dtype=np.float32),
+              "task_predictions": np.asarray(ev.last_task_predictions, dtype=np.float32),
+              "batch_criterions": np.asarray(ev.last_batch_criterions, dtype=np.float32),
+              "batch_mm_iters": np.asarray(ev.last_batch_mm_iters, dtype=np.float32)}
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    for name in ("v", "u", "alpha"):
+        t = getattr(m, name).detach()
+        if t.numel() <= DUMP_FULL:
+            arrays[name] = t.float().cpu().numpy()
+            continue
+        idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=gen).unique()      # sorted
+        arrays[name + "_sample"] = t.reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+        arrays[name + "_sample_index"] = idx.numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in arrays.items()}
+
+
 def roofline_of(prof, steps, K, pmc_key):
     """prof = engine.profile_collect() of `steps` timed steps (+ engine.profile_last_kernels() as a fifth entry)."""
     mm_ms, mm_launch_sum, mm_launches, updates = prof[:4]
@@ -389,7 +421,14 @@ def main():
                          "K = 1000 tasks) on N GPUs - 90 s per step on one GPU")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; gloo only to test the N>1 path on one GPU)")
     ap.add_argument("--single-device", action="store_true", help="testing: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline path delivered in its last step to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; the inputs are the same on every run with the same arguments)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload in ("k397_hard", "fs_k1000"):
+        ap.error("--dump-outputs records the headline path (--workload k1000 or k100)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -582,7 +621,7 @@ def main():
     head = HEADLINE if args.workload == "k1000" else SECONDARY
     ev, table, labels, idx = prepare(head, world)
     elapsed, prof, acc_mean, per_rank = run_steps(ev, table, labels, idx, args.warmup, args.steps)
-    steps = max(args.steps, 1)
+    steps = args.steps
     mm_iters = ev.last_method.mm_iters                  # (local batches, iters)
     line = None
     if rank == 0:
@@ -619,6 +658,8 @@ def main():
             line["backend"] = dist.get_backend()
             line["rank_step_ms"] = {"min": 1e3 * min(per_rank) / steps, "max": 1e3 * max(per_rank) / steps,
                                     "all": [1e3 * t / steps for t in per_rank]}
+        if args.dump_outputs:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, ev, acc_mean)}
     del ev, table, labels, idx
     torch.cuda.empty_cache()
 

@@ -11,8 +11,8 @@ so on one machine it reproduces the reference bit for bit - the special function
 own (calc_digamma, Sleef lgammaf/logf/expf) and the summation orders are torch's.  That is what
 licenses timing it as "the reference's CPU path" in bench.py (kind "port").
 
-Pinned against: tests/golden/*.npz, produced by running /root/reference itself in the build
-container (tests/golden/make_golden.py); tests/test_oracle_golden.py demands bit-exact
+Pinned against: tests/golden/*.npz, produced by running the reference itself
+(tests/golden/make_golden.py); tests/test_oracle_golden.py demands bit-exact
 alpha/u/v/criterions and identical MM iteration counts on every small fixture.
 
 Reference lines followed (paths relative to the reference repo):

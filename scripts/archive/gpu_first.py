@@ -1,9 +1,10 @@
 import sys, os, time, numpy as np, torch
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/transductive-clip_amd'); sys.path.insert(0,'/root/repo/transductive-clip_amd/drop_in')
+R=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0,R); sys.path.insert(0,f'{R}/transductive-clip_amd'); sys.path.insert(0,f'{R}/transductive-clip_amd/drop_in')
 from tclip_amd import engine
 dev=torch.device('cuda:0')
 for name in sys.argv[1:]:
-    g=np.load(f'/root/repo/tests/golden/{name}.npz'); kind=str(g['kind']); few=kind.startswith('fs'); K=int(g['K'])
+    g=np.load(f'{R}/tests/golden/{name}.npz'); kind=str(g['kind']); few=kind.startswith('fs'); K=int(g['K'])
     t=time.time()
     res=engine.run_em_dirichlet(torch.from_numpy(g['x_q']).to(dev), torch.from_numpy(g['x_s']).to(dev) if few else None, torch.from_numpy(g['y_s']).to(dev) if few else None,
         n_batches=1, iters=int(g['iters']), iter_mm=1000, lambd=int(K/5)*75, hard=kind.endswith('hard'))

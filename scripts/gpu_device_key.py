@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "transductive-clip_amd"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "transductive-clip_amd"))
 import torch
 from tclip_amd import sharding
 p = torch.cuda.get_device_properties(0)

@@ -1,6 +1,5 @@
 """Where a bench step spends its time outside the engine: python3 scripts/gpu_step_breakdown.py [k100|k1000]"""
 import os, sys, time, random
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "transductive-clip_amd")); sys.path.insert(0, os.path.join(ROOT, "transductive-clip_amd", "drop_in"))
 import numpy as np, torch

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by RUNNING the reference.
 
-Only works in the build container, where /root/reference exists.  The reference's Python
+Needs a checkout of the reference (TCLIP_REFERENCE).  The reference's Python
 sources are imported (never copied): `clip` and `torchvision` are absent from this image and
 are not used on the EM-Dirichlet path, so empty stub modules satisfy the import lines
 (SURVEY.md section 8c).  What is committed is data only: seeded inputs and the outputs the
@@ -32,7 +32,9 @@ sys.path[:] = [p for p in sys.path if "transductive-clip_amd" not in p]
 
 for _m in ("clip", "torchvision", "torchvision.transforms"):
     sys.modules.setdefault(_m, types.ModuleType(_m))
-REF = "/root/reference"
+REF = os.environ.get("TCLIP_REFERENCE", "")      # a checkout of the reference, SegoleneMartin/transductive-CLIP
+if not os.path.isdir(REF):
+    sys.exit("set TCLIP_REFERENCE to a checkout of the reference (SegoleneMartin/transductive-CLIP)")
 
 
 class Args(dict):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden vectors for BD-CSPN from the REFERENCE's own class
-(/root/reference/src/methods/few_shot/bdcspn.py), CPU, on seeded synthetic probability features.
-Run in the build container only; the .npz files are committed.
+(the reference's src/methods/few_shot/bdcspn.py), CPU, on seeded synthetic probability features.
+Needs a checkout of the reference (TCLIP_REFERENCE); the .npz files are committed.
 
     python tests/golden/make_golden_bdcspn.py
 
@@ -16,7 +16,9 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = os.environ.get("TCLIP_REFERENCE", "")      # a checkout of the reference, SegoleneMartin/transductive-CLIP
+if not os.path.isdir(REF):
+    sys.exit("set TCLIP_REFERENCE to a checkout of the reference (SegoleneMartin/transductive-CLIP)")
 # the product package mirrors the reference's `src` module names: load its synthetic-data module by file path
 import importlib.util  # noqa: E402
 import types  # noqa: E402

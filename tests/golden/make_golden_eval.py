@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden vectors for the task-batch loop, produced by RUNNING the
-reference's Evaluator_*.evaluate_tasks on a synthetic feature table in the build container
-(/root/reference is imported, never copied; clip/torchvision are stubbed as in make_golden.py).
+reference's Evaluator_*.evaluate_tasks on a synthetic feature table, with a checkout of the reference
+(TCLIP_REFERENCE; imported, never copied; clip/torchvision are stubbed as in make_golden.py).
 
 Seeds are set the way main.py:42-46 sets them, the sampler iterators are wrapped to record the
 index tensors they yield, and the returned (mean accuracy, mean time) is stored.
@@ -29,7 +29,9 @@ sys.path[:] = [p for p in sys.path if "transductive-clip_amd" not in p]
 
 for _m in ("clip", "torchvision", "torchvision.transforms"):
     sys.modules.setdefault(_m, types.ModuleType(_m))
-REF = "/root/reference"
+REF = os.environ.get("TCLIP_REFERENCE", "")      # a checkout of the reference, SegoleneMartin/transductive-CLIP
+if not os.path.isdir(REF):
+    sys.exit("set TCLIP_REFERENCE to a checkout of the reference (SegoleneMartin/transductive-CLIP)")
 try:                                    # laplacian_shot.py imports matplotlib only to select a backend
     import matplotlib  # noqa: F401
 except ImportError:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden vectors for LAPLACIAN_SHOT from the REFERENCE's own class
-(/root/reference/src/methods/few_shot/laplacian_shot.py), CPU (numpy / scipy.sparse / sklearn kNN), on seeded synthetic
-probability features.  Run in the build container only; the .npz files are committed.
+(the reference's src/methods/few_shot/laplacian_shot.py), CPU (numpy / scipy.sparse / sklearn kNN), on seeded synthetic
+probability features.  Needs a checkout of the reference (TCLIP_REFERENCE); the .npz files are committed.
 
     python tests/golden/make_golden_lshot.py
 
@@ -21,7 +21,9 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = os.environ.get("TCLIP_REFERENCE", "")      # a checkout of the reference, SegoleneMartin/transductive-CLIP
+if not os.path.isdir(REF):
+    sys.exit("set TCLIP_REFERENCE to a checkout of the reference (SegoleneMartin/transductive-CLIP)")
 import importlib.util  # noqa: E402
 _spec = importlib.util.spec_from_file_location("tclip_synth", os.path.join(ROOT, "transductive-clip_amd", "tclip_amd", "synth.py"))
 synth = importlib.util.module_from_spec(_spec)

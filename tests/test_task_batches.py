@@ -195,6 +195,9 @@ def _worker_eight(rank, world, port, out):
     """configs[3] as the 8-GPU bench runs it, minus the GPUs: 80 batches of 125 tasks dealt to 8 ranks, every rank hands its
     10 batches' records to the ONE packed all_gather; the ranks' step times and device indices travel as the bench moves
     them (sharding.gather_rank_values / check_one_device_per_rank)."""
+    # eight processes must not open a GPU the host may have (sharding._device_key asks torch.cuda): every rank takes the
+    # GPU-less path, process-local indices, as on a host without one
+    torch.cuda.is_available = lambda: False
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     n_batches, N, Q, iters = 80, 125, 75, 20

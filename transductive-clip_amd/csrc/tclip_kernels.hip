@@ -3876,7 +3876,7 @@ static int pool_init(int groups) {
 // Group 0 runs on the caller's stream, the others on pool streams.  Measured on the K=100 bench
 // (10 batches): 1 group 685 ms per step, 2 or 3 groups 606 ms, 4 groups 685 ms again with HIP's
 // default of four hardware queues per process (streams beyond the queues serialise behind each
-// other; GPU_MAX_HW_QUEUES=8 brings 4 groups to 619 ms).  Small problems are launch-bound and
+// other; eight hardware queues per process bring 4 groups to 619 ms).  Small problems are launch-bound and
 // run best on one stream (K=10, 10 batches of 10 tasks: 53 ms against 114 ms on four).
 static int stream_groups() {
     static const int n = [] {

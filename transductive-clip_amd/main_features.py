@@ -31,8 +31,6 @@ import sys
 import numpy as np
 import torch
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")    # see tclip_amd/__init__.py: the engine's streams need their own hardware queues
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 for _p in (HERE, os.path.join(HERE, "drop_in")):          # tclip_amd/ and the reference-named src/ package
     if _p not in sys.path:
