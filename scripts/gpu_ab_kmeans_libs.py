@@ -3,7 +3,7 @@
 K = 397 and K = 100, 1000 tasks): milliseconds per engine call and a digest of the results, one child process per library
 (TCLIP_LIB), as scripts/gpu_ab_libs.py does for EM-Dirichlet.
 
-    python scripts/gpu_ab_kmeans_libs.py orig gpurun_variants/x.so ...
+    python scripts/gpu_ab_kmeans_libs.py orig variants/x.so ...
 """
 import hashlib, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -3,7 +3,7 @@
 process per library (TCLIP_LIB), so that a kernel change is timed against its predecessor on the SAME box and checked to
 return the same bits in the same call.
 
-    python scripts/gpu_ab_libs.py orig gpurun_variants/base.so ... [-- K B N iters [hard [shots]] ...]
+    python scripts/gpu_ab_libs.py orig variants/base.so ... [-- K B N iters [hard [shots]] ...]
 """
 import hashlib, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

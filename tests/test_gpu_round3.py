@@ -157,7 +157,7 @@ def test_class_split_kernel_with_nan_and_stopped_batches(K, N, iter_mm):
     and a batch that stops early while the other keeps iterating (rows of a stopped batch are skipped by the same
     blocks): identical to k_mm_live.  Row lengths WITH a split instantiation in each lane layout: K = 100 (16 lanes x 7
     registers), 397 (32 x 13), 1000 (64 x 16) - round 3 ran this at K = 40, three registers per lane, below
-    TCLIP_SPLIT_MIN_E, where both modes are k_mm_live and the test passed trivially.  The profiler's kernel names
+    kSplitMinE, where both modes are k_mm_live and the test passed trivially.  The profiler's kernel names
     confirm that mode 1 launched k_mm_split and mode 0 did not."""
     from tclip_amd import engine, synth
     B = 2

@@ -1,7 +1,7 @@
 """GPU (round 6): the early limit-cycle probe of freshly dead rows (k_mm_probe_head) is an exact shortcut.
 
 A row that has just died used to run the whole first chunk (51 iterations) before k_mm_probe looked for its limit cycle; it now
-runs TCLIP_DEAD_HEAD = 12 iterations and the probe searches from there (further snapshots 8 and 32 iterations on), filling every checkpoint of the
+runs kDeadHead = 12 iterations and the probe searches from there (further snapshots 8 and 32 iterations on), filling every checkpoint of the
 row from the cycle it finds.  The cached stop-test terms decide when a BATCH stops (em_dirichlet.py:169-175), so a wrong entry
 shows up as a different MM count - in the outer iteration in which the row dies or in any later one - and from there in alpha."""
 import numpy as np

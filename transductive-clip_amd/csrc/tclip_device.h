@@ -104,17 +104,17 @@ __device__ __forceinline__ float group_sum_torch(const float (&x)[E], int K, int
     return fin;
 }
 
-// The same sum with a row spread over G = 8 or 16 lanes (short rows: more rows per wavefront, fuller lanes).
-// Element d lives in register d / G of lane d % G.  With H = G / 8 lanes-of-eight per group, lane (h, j) =
+// The same sum with a row spread over G = 16 lanes (short rows: four rows per wavefront, fuller lanes).
+// Element d lives in register d / 16 of lane d % 16.  With H = 2 lanes-of-eight per group, lane (h, j) =
 // 8 h + j holds the 8-float vector v = e H + h in register e; torch's accumulator r = v % 4 and step m = v / 4
-// are r = (e % P) H + h, m = e / P with P = 4 / H registers per step, so a lane keeps P partial sums.
+// are r = (e % P) H + h, m = e / P with P = 2 registers per step, so a lane keeps P partial sums.
 // kSure: the caller guarantees that registers below it hold steps of the 4-way interleaved part (e / P < K / 32) for every K
 // the instantiation is used for, which frees their additions from the per-register tests (wave-uniform, but K is a run-time
 // value: the compiler kept 2 E lane masks in scalar registers, spilled them, and read them back every iteration).
 template <int E, int G, bool kLane0 = false, int kSure = 0>
 __device__ __forceinline__ float group_sum_torch_g(const float (&x)[E], int K, int lane) {
-    static_assert(G == 8 || G == 16, "lanes per row");
-    constexpr int H = G / 8, P = 4 / H;
+    static_assert(G == 16, "lanes per row");
+    constexpr int H = 2, P = 2;
     static_assert((E + P - 1) / P <= 31, "rows this long need the second cascade dump of the 32-lane form");
     auto shfl = [](float v, int src) { return __shfl(v, src, G); };
     if (K < 8) {  // scalar_inner_sum: 4 interleaved scalar accumulators; the whole row sits in register 0
@@ -162,7 +162,7 @@ __device__ __forceinline__ float group_sum_torch_g(const float (&x)[E], int K, i
 #pragma unroll
     for (int r = 1; r < 4; r++) {                                            // valid in lanes 0..7
         if (r % H == 0) p0 += pm[r / H];                                     // own lane's other accumulator
-        else if (kLane0 && G == 16) p0 += dpp_row_shl<8>(pm[r / H]);         // lane 8 + j of the same DPP row
+        else if (kLane0) p0 += dpp_row_shl<8>(pm[r / H]);                    // lane 8 + j of the same DPP row
         else p0 += shfl(pm[r / H], 8 * (r % H) + j);
     }
     // scalar tail (K mod 8 elements, in the partial vector vec_size) first, then the 8 vector lanes in order

@@ -46,12 +46,10 @@
 #include "tclip_pk.h"
 #include "tclip_selftest_inputs.h"
 
-#ifndef TCLIP_G64_MIN_K
-#define TCLIP_G64_MIN_K 897           // rows from this length on: one wavefront per row, 16 registers per lane instead of 32 lanes x 32
-                                      // registers (half the code, 4 instead of 3 wavefronts per SIMD): K = 1000 bench shape 12.55 -> 11.90 s
-#endif
-
 namespace tclip {
+
+constexpr int kG64MinK = 897;   // rows from this length on: one wavefront per row, 16 registers per lane instead of 32 lanes x 32
+                                // registers (half the code, 4 instead of 3 wavefronts per SIMD): K = 1000 bench shape 12.55 -> 11.90 s
 
 // ------------------------------------------------------------------------------------------
 // element-wise log of the features: log(x + 1e-15)                      (em_dirichlet.py:38)
@@ -466,9 +464,7 @@ struct MMArgs {
 // `queue` = 64*E floats of LDS private to this wave.
 // y of a row: in registers for short rows, re-read from global memory (L1/L2 hits, read-only)
 // every iteration for long rows, where 2 x E registers per lane would cost occupancy and spills.
-#ifndef TCLIP_Y_REGS_MAX_E
-#define TCLIP_Y_REGS_MAX_E 16
-#endif
+constexpr int kYRegsMaxE = 16;
 // Element held by register e of lane `lane` of a row's lane group.  G <= 32: element e G + lane.  G = 64 (rows of
 // 897..1024 elements, one wavefront per row): lanes 0..31 hold the first 16 steps of 32 elements, lanes 32..63 the
 // rest, so that each half accumulates its part of torch's 16-step cascade locally (see group_sum_torch_64).
@@ -484,7 +480,7 @@ __host__ __device__ constexpr int full_registers(int K) {
     else return K / G;
 }
 
-template <int E, int G = kGroup, int kRegsMaxE = TCLIP_Y_REGS_MAX_E>
+template <int E, int G = kGroup, int kRegsMaxE = kYRegsMaxE>
 struct RowY {
     static constexpr bool kInRegs = E <= kRegsMaxE;
     float r[kInRegs ? E : 1];
@@ -553,9 +549,6 @@ __device__ __forceinline__ float lgamma_big_dense(float v) {
 // the large-argument results queued at `queue[base...]` in ballot order, and the update algebra.
 // Elements are advanced two at a time on the packed fp32 pipe (tclip_pk.h); an odd last one
 // takes the scalar form.
-#ifndef TCLIP_MM_PACKED
-#define TCLIP_MM_PACKED 1
-#endif
 template <int E, int G = kGroup>
 __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E, G>& yv, int K, int lane, float psi_s,
                                                  const LogTabEntry* tab, const float* queue, int base, bool measure,
@@ -588,7 +581,7 @@ __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E,
     };
     PkUpdateStage pending;
 #pragma unroll
-    for (int p = 0; p < (TCLIP_MM_PACKED ? E / 2 : 0); p++) {
+    for (int p = 0; p < E / 2; p++) {
         const int e = 2 * p;
         const f2 a{beta[e], beta[e + 1]};
         const bool big0 = a.x + 1.0f >= 2.3f, big1 = a.y + 1.0f >= 2.3f;
@@ -602,9 +595,9 @@ __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E,
         if (p > 0) finish(p - 1, pending);         // while this pair's table look-ups are in flight
         pending = st;
     }
-    if (TCLIP_MM_PACKED && E / 2 > 0) finish(E / 2 - 1, pending);
+    if (E / 2 > 0) finish(E / 2 - 1, pending);
 #pragma unroll
-    for (int e = (TCLIP_MM_PACKED ? E / 2 * 2 : 0); e < E; e++) {
+    for (int e = E / 2 * 2; e < E; e++) {
         const float a = beta[e];
         const float x1 = a + 1.0f;
         const bool big = x1 >= 2.3f;
@@ -632,9 +625,6 @@ __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E,
 // of digamma's recurrence unmasked (pk_mm_update_stage1_small).  In the first outer iteration every parameter starts at 1:
 // all wavefronts take this path for the first iterations, 44 % of the K = 1000 rows still do after 50 (HISTORY.md section 8);
 // dead rows, whose parameters collapse to ~0.14 within a dozen iterations, always do.
-#ifndef TCLIP_MM_SMALL_PATH
-#define TCLIP_MM_SMALL_PATH 1
-#endif
 template <int E, int G = kGroup>
 __device__ __forceinline__ void mm_apply_updates_small(float (&beta)[E], const RowY<E, G>& yv, int K, int lane, float psi_s,
                                                        const LogTabEntry* tab, bool measure, double& num, double& den) {
@@ -696,21 +686,18 @@ __device__ __forceinline__ void mm_apply_updates_small(float (&beta)[E], const R
 // and the count is exact: with the row length a constant the compiler resolves every step, tail and mask of the row sum,
 // of the placement sweeps and of the update by itself - this constant and first_ragged_register are the two places where the
 // kernels' own template arithmetic has to be told.
+static_assert(kG64MinK >= 897, "sure_registers: the 64-lane layout takes 16 + e < K / 32 for granted");
 template <int E, int G, int KC = 0>
 constexpr int sure_registers() {
     if (KC > 0) {
         const int size_ilp = (KC >> 3) >> 2;                               // steps of the 4-way interleaved part
         if (G == 64) return size_ilp - 16 < 0 ? 0 : (size_ilp - 16 > E ? E : size_ilp - 16);     // the upper half's step of register e is 16 + e
         if (G == 32) return size_ilp > E ? E : size_ilp;
-        const int P = 4 / (G / 8);                                          // registers per step (group_sum_torch_g)
-        return size_ilp * P > E ? E : size_ilp * P;
+        return size_ilp * 2 > E ? E : size_ilp * 2;                        // G = 16: two registers per step (group_sum_torch_g)
     }
-    if (G == 64) return (TCLIP_G64_MIN_K >= 897 && E == 16) ? 12 : 0;      // 16 + e < K / 32 for K >= 897
+    if (G == 64) return E == 16 ? 12 : 0;                                  // 16 + e < K / 32 for K >= kG64MinK
     // G = 32: one register per step of 32 elements; G = 16: two.  The instantiation E is launched for K > (next smaller
     // size) x G, whose interleaved part has at least E - 4 registers' worth of steps for every E launch_mm_G hands out.
-    // G = 8 has FOUR registers per step and buckets (10 -> 13 -> 16) whose smallest row ends inside register E - 4
-    // (E = 13: K = 81 has size_ilp = 2, i.e. 8 sure registers, not 9): nothing is taken for sure there.
-    if (G == 8) return 0;
     return E > 4 ? E - 4 : 0;
 }
 // registers below it hold only slots inside the row in every lane (the split kernel queues them whole)
@@ -777,25 +764,16 @@ __device__ __forceinline__ void mm_iterate(float (&beta)[E], const RowY<E, G>& y
     }
     __builtin_amdgcn_wave_barrier();
     // phase C: per element digamma, cheap lgamma branch, pick-up, algebra
-    if (TCLIP_MM_SMALL_PATH && n_big == 0) mm_apply_updates_small<E, G>(beta, yv, K, lane, psi_s, tab, measure, num, den);
+    if (n_big == 0) mm_apply_updates_small<E, G>(beta, yv, K, lane, psi_s, tab, measure, num, den);
     else mm_apply_updates<E, G>(beta, yv, K, lane, psi_s, tab, queue, 0, measure, num, den);
     __builtin_amdgcn_wave_barrier();
 }
 
-#ifndef TCLIP_PROBE_CHUNKS
-#define TCLIP_PROBE_CHUNKS 2        // the limit-cycle probe runs after each of the first this-many chunks
-#endif
-#ifndef TCLIP_MAX_CYCLE
-#define TCLIP_MAX_CYCLE 64
-#endif
-constexpr int kMaxCycle = TCLIP_MAX_CYCLE;  // longest limit cycle looked for on dead rows (periods up to 20 seen at K=1000)
+constexpr int kProbeChunks = 2;     // the limit-cycle probe runs after each of the first this-many chunks
+constexpr int kMaxCycle = 64;       // longest limit cycle looked for on dead rows (periods up to 20 seen at K=1000)
 
-#ifndef TCLIP_MM_WAVES_LARGE
-#define TCLIP_MM_WAVES_LARGE 3     // waves per SIMD requested for long rows (E > 8)
-#endif
-#ifndef TCLIP_MM_WAVES_SMALL
-#define TCLIP_MM_WAVES_SMALL 4     // waves per SIMD requested for short rows (E <= 8)
-#endif
+constexpr int kMMWavesLarge = 3;    // waves per SIMD requested for long rows (E > 16)
+constexpr int kMMWavesSmall = 4;    // waves per SIMD requested for short rows (E <= 16)
 // Limit-cycle probe for the dead rows that have just run chunk 0 (k_mm_live<.., true> left b_51 in
 // `beta_dead` and the first stop-test pair in the cache).
 // Dead rows (y = -10 everywhere) contract within ~10-30 iterations onto a short limit cycle of the
@@ -804,7 +782,7 @@ constexpr int kMaxCycle = TCLIP_MAX_CYCLE;  // longest limit cycle looked for on
 // here: the remaining ~900 iterations of this row need not be executed.  No cycle within
 // kMaxCycle steps: nothing is assumed, the row keeps iterating chunk by chunk.
 template <int E, int G>
-__global__ __launch_bounds__(256, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_WAVES_SMALL)) void k_mm_probe(MMArgs a) {
+__global__ __launch_bounds__(256, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void k_mm_probe(MMArgs a) {
     __shared__ LogTabEntry tab[16];
     __shared__ double cyc[256 / G][kMaxCycle][2];
     __shared__ float lg_queue[4][64 * E];             // per wave: arguments / results of the large-x lgamma
@@ -864,7 +842,7 @@ __global__ __launch_bounds__(256, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_WAVE
 }
 
 // Early limit-cycle probe (round 6) for rows that have JUST died: k_mm_live<.., true> has run only the first `a.l0`
-// iterations (TCLIP_DEAD_HEAD = 12, not the whole first chunk) and left b_{l0} in `beta_dead`.
+// iterations (kDeadHead = 12, not the whole first chunk) and left b_{l0} in `beta_dead`.
 // Measured on the reference's trajectories (scripts/dead_row_cycles.py, CPU oracle, the alpha rows of a task after its first
 // outer iteration): a dead row is ON its cycle after 8..15 iterations at K = 100 (median 10; periods 1, 2, 4) and after
 // 8..28 at K = 1000 (median 11, 99 % within 16; periods 20 (75 %), 5, 4, 8) - so the 51 iterations of chunk 0 that
@@ -883,11 +861,10 @@ __global__ __launch_bounds__(256, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_WAVE
 // No cycle within kMaxCycle iterations, or a row whose cache is partly filled (a batch that stopped early): the row goes to
 // the list `next_rows`, which the host hands to the old path (k_mm_live<.., true> over the whole chunk from alpha, then
 // k_mm_probe) - nothing is assumed about such a row.
-#ifndef TCLIP_DEAD_HEAD
-#define TCLIP_DEAD_HEAD 12
-#endif
+constexpr int kDeadHead = 12;
+static_assert(kDeadHead <= 18, "the last snapshot (32 iterations after the head) must lie at or before the first checkpoint (iteration 50)");
 template <int E, int G>
-__global__ __launch_bounds__(256, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_WAVES_SMALL)) void k_mm_probe_head(MMArgs a) {
+__global__ __launch_bounds__(256, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void k_mm_probe_head(MMArgs a) {
     __shared__ LogTabEntry tab[16];
     __shared__ double cyc[256 / G][kMaxCycle][2];
     __shared__ float lg_queue[4][64 * E];
@@ -988,9 +965,6 @@ __global__ __launch_bounds__(256, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_WAVE
 // one wave evaluates digamma for all rows of the block in a single pass (one row per lane) inside the
 // dense-pass window instead of every 32-lane group evaluating its own row's value 32 times over.
 struct QueueCtl { int count[2][8]; int bad; float rowsum[2][64]; float psi[2][64]; };
-#ifdef TCLIP_COUNT_SMALL
-__device__ unsigned long long g_small_count[4];
-#endif
 
 // the row sum in torch's order, valid in lane 0 of the row's lane group (K >= 8; shorter rows: in every lane)
 template <int E, int G, int KC = 0>
@@ -1086,19 +1060,7 @@ __device__ __forceinline__ void mm_iterate_block(float (&beta)[R][E], const RowY
         ctl->psi[turn & 1][lane64] = digamma_pos_f32(ctl->rowsum[turn & 1][lane64], tab);
     __syncthreads();
     // phase C: per element digamma, cheap lgamma branch, pick-up, algebra
-#ifdef TCLIP_COUNT_SMALL
-    // design study (scripts/gpu_small_count.py): [0] wavefront-iterations of k_mm_live, [1] those that queued nothing, [2] block-iterations,
-    // [3] those in which NO wavefront of the block queued anything
-    if (lane64 == 0) {
-        atomicAdd(&g_small_count[0], 1ull);
-        if (base[R] == 0) atomicAdd(&g_small_count[1], 1ull);
-        if (wave == 0) {
-            atomicAdd(&g_small_count[2], 1ull);
-            if (n_big == 0) atomicAdd(&g_small_count[3], 1ull);
-        }
-    }
-#endif
-    if (TCLIP_MM_SMALL_PATH && base[R] == 0) {                   // nothing of this wavefront's rows is in the queue (wave-uniform)
+    if (base[R] == 0) {                                        // nothing of this wavefront's rows is in the queue (wave-uniform)
 #pragma unroll
         for (int r = 0; r < R; r++)
             if (active[r])
@@ -1113,21 +1075,14 @@ __device__ __forceinline__ void mm_iterate_block(float (&beta)[R][E], const RowY
                                    measure, num[r], den[r]);
 }
 
-#ifndef TCLIP_MM_BLOCK_WAVES
-#define TCLIP_MM_BLOCK_WAVES 4        // waves (= pairs of rows) per block of k_mm_live for E <= 8
-#endif
-#ifndef TCLIP_MM_ROWSETS
-#define TCLIP_MM_ROWSETS 2            // rows per 32-lane group of k_mm_live for E <= 8: 16 rows share a block's two barriers and
-                                      // its dense lgamma passes (fuller passes: +2 % on the K = 100 bench; 4 rows per group spill)
-#endif
 // kDead: the listed rows are dead rows whose cache ends at this chunk: y = -10, the iterate lives in
 // `beta_dead` (their alpha keeps its value, em_dirichlet.py:224-226) and the stop-test pair goes to the cache.
-// G: lanes per row (32; 16 or 8 for short rows, where a 32-lane group would leave lanes idle: K = 100 fills
-// 100 of 128 slots as 32 x 4 but 100 of 104 as 8 x 13, with eight rows per wavefront sharing the per-row work).
+// G: lanes per row (32; 16 for short rows, where a 32-lane group would leave lanes idle: K = 100 fills 100 of 128
+// slots as 32 x 4 but 100 of 112 as 16 x 7, with four rows per wavefront sharing the per-row work; 64 for long rows).
 template <int E, int W, bool kDead, int R, int G = kGroup, int KC = 0>
 // wavefronts per SIMD: 4 (128 VGPRs) up to 16 registers per lane - also for K = 257..512 as 32 lanes x 10..16 since round 2
 // (K = 397, hard, 1000 tasks: 1.24 -> 1.18 s) - 3 (168 VGPRs) for the 20..28-register kernels
-__global__ __launch_bounds__(64 * W, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_WAVES_SMALL)) void k_mm_live(MMArgs a) {
+__global__ __launch_bounds__(64 * W, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void k_mm_live(MMArgs a) {
     __shared__ LogTabEntry tab[16];
     __shared__ float queue[64 * W * E * R];
     __shared__ QueueCtl ctl;
@@ -1218,31 +1173,17 @@ __global__ __launch_bounds__(64 * W, (E > 16 ? TCLIP_MM_WAVES_LARGE : TCLIP_MM_W
 // K = 397 453 -> 439 ms, K = 1000 -1 %; k_mm_live, whose single queue is short, is better off sharing).
 // The host uses this kernel from the second outer iteration on; in the first one every parameter starts at 1 (class A)
 // and the queue traffic would be pure overhead (measured: +15 % there).
-#ifndef TCLIP_SPLIT_FROM
-#define TCLIP_SPLIT_FROM 1         // first outer iteration (0-based) that runs k_mm_split
-#endif
-#ifndef TCLIP_SPLIT_MAX_E
-#define TCLIP_SPLIT_MAX_E 24       // two words of LDS per element: 8 KB per wavefront at 16 registers per lane (16 wavefronts per CU),
-                                   // 12 KB at 24 (12 wavefronts per CU, which is what those kernels' registers allow anyway)
-#endif
-#ifndef TCLIP_SPLIT_Y_REGS_MAX_E
-#define TCLIP_SPLIT_Y_REGS_MAX_E 8     // y of a row in registers up to this many registers per lane; longer rows fetch it at the start of
-                                       // phase C (RowY::fetch_all).  Round 4 kept 16 registers of y across the dense passes: the compiler
-                                       // spilled them and re-read a pair at a time inside phase C, each re-read followed by a wait for
-                                       // everything in flight.  Same-box A/B (profiles/r05_ab_phase_c.txt): K = 1000 -1.1 %, few-shot
-                                       // K = 1000 -1.2 %, K = 397 hard -0.9 % per engine call, bit-identical; VGPR spills 59 -> 23
-#endif
-#ifndef TCLIP_SPLIT_WAVES_SMALL
-#define TCLIP_SPLIT_WAVES_SMALL 4  // wavefronts per SIMD requested for up to 8 registers per lane
-#endif
-#ifndef TCLIP_SPLIT_WAVES_MID
-#define TCLIP_SPLIT_WAVES_MID 4    // wavefronts per SIMD requested for 9..16 registers per lane
-#endif
-#ifndef TCLIP_SPLIT_MIN_E
-#define TCLIP_SPLIT_MIN_E 5        // shorter rows fill too little of a dense pass: measured with 16 lanes per row on 1000 tasks,
-                                   // split against k_mm_live: K = 10 +42 %, 37 +6 %, 47 +7 %, 64 +1 %, 80 -4.5 %, 96 -5 %, 100 -11 %,
-                                   // 128 -10 %, 196 -14 %, 256 -13 %, 300 -15 %, 512 -17 %, 1000 -17 %
-#endif
+constexpr int kSplitFrom = 1;       // first outer iteration (0-based) that runs k_mm_split
+constexpr int kSplitMaxE = 24;      // two words of LDS per element: 8 KB per wavefront at 16 registers per lane (16 wavefronts per CU),
+                                    // 12 KB at 24 (12 wavefronts per CU, which is what those kernels' registers allow anyway)
+constexpr int kSplitYRegsMaxE = 8;  // y of a row in registers up to this many registers per lane; longer rows fetch it at the start of
+                                    // phase C (RowY::fetch_all).  Round 4 kept 16 registers of y across the dense passes: the compiler
+                                    // spilled them and re-read a pair at a time inside phase C, each re-read followed by a wait for
+                                    // everything in flight.  Same-machine A/B (profiles/r05_ab_phase_c.txt): K = 1000 -1.1 %, few-shot
+                                    // K = 1000 -1.2 %, K = 397 hard -0.9 % per engine call, bit-identical; VGPR spills 59 -> 23
+constexpr int kSplitMinE = 5;       // shorter rows fill too little of a dense pass: measured with 16 lanes per row on 1000 tasks,
+                                    // split against k_mm_live: K = 10 +42 %, 37 +6 %, 47 +7 %, 64 +1 %, 80 -4.5 %, 96 -5 %, 100 -11 %,
+                                    // 128 -10 %, 196 -14 %, 256 -13 %, 300 -15 %, 512 -17 %, 1000 -17 %
 
 // Sleef's large-argument lgamma for a dense pass of arguments above 7 (class C: >= 10)
 __device__ __forceinline__ float lgamma_gt7_dense(float v) {
@@ -1257,14 +1198,14 @@ __device__ __forceinline__ float lgamma_gt7_dense(float v) {
 // kMeasure: the stop test's iteration (a template parameter so that the other 49 of 50 iterations are ONE basic block per
 // register-pair loop: with the flag tested per pair the scheduler could not overlap one pair's chain with the next one's)
 template <int E, int G, bool kTiny, bool kMeasure>
-__device__ __forceinline__ void split_apply_updates(float (&beta)[E], const RowY<E, G, TCLIP_SPLIT_Y_REGS_MAX_E>& yv, int K, int lane, float psi_s,
+__device__ __forceinline__ void split_apply_updates(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, float psi_s,
                                                     const float* my0, const float* my1, const uint32_t (&slot)[(E + 1) / 2],
                                                     double& num, double& den) {
     constexpr bool measure = kMeasure;
     // y of the row: from the registers of the whole chunk (short rows), or fetched here, all at once, for this phase alone -
     // 16 values per lane that live across the dense passes were 16 values the compiler spilled and re-read one pair at a
     // time, each re-read followed by a wait for EVERYTHING in flight, the next pair's square-root table entries included
-    constexpr bool kYLocal = !RowY<E, G, TCLIP_SPLIT_Y_REGS_MAX_E>::kInRegs;
+    constexpr bool kYLocal = !RowY<E, G, kSplitYRegsMaxE>::kInRegs;
     float yl[kYLocal ? E : 1];
     if constexpr (kYLocal) yv.fetch_all(yl);
     auto y_of = [&](int e) { if constexpr (kYLocal) return yl[e]; else return yv.get(e); };
@@ -1331,27 +1272,12 @@ __device__ __forceinline__ void wave_lds_handoff() {
 // the last one (one add and one LDS store per element), the dense passes check the one class condition their own form
 // depends on, and only a wavefront that met a misplaced entry sorts again (the two sweeps below, which every iteration
 // ran until round 4: 18 of 169 lane-instructions per update, most of them half-rate compares, v_mbcnt and selects).
-#ifndef TCLIP_SPLIT_LAZY
-#define TCLIP_SPLIT_LAZY 1
-#endif
-#ifdef TCLIP_PHASE_CLOCK
-// design studies only (scripts/gpu_phase_clock.py): wavefront clocks (s_memtime) spent in the parts of the split iteration,
-// summed over all wavefronts: [0] head (row sum, domain test, digamma of the row sum), [1] scatter or sort, [2] class A passes,
-// [3] class B passes, [4] class C passes, [5] phase C, [6] iterations, [7] passes abandoned (misplaced entry)
-__device__ unsigned long long g_phase_clock[8];
-#define TCLIP_CLK(i, t) do { const long long now_ = __builtin_readcyclecounter(); pl.clk[i] += now_ - (t); (t) = now_; } while (0)
-#else
-#define TCLIP_CLK(i, t) do { } while (0)
-#endif
 template <int E>
 struct SplitPlacement {
     uint32_t slot[(E + 1) / 2];
     int nA, nB, nC;
     bool valid;
     int sorts;          // full placements of this wavefront in the launch (instrumentation)
-#ifdef TCLIP_PHASE_CLOCK
-    long long clk[8];
-#endif
 };
 
 // The full placement: two sweeps over the registers.
@@ -1440,14 +1366,10 @@ __device__ __forceinline__ void split_scatter(const float (&beta)[E], int K, int
 
 // my0 / my1: the wavefront's two planes of 64 E words
 template <int E, int G, int KC = 0>
-__device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const RowY<E, G, TCLIP_SPLIT_Y_REGS_MAX_E>& yv, int K, int lane, bool active,
+__device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, bool active,
                                                       const LogTabEntry* tab, float* my0, float* my1, bool measure,
                                                       double& num, double& den, SplitPlacement<E>& pl, bool keep_placement) {
     const int lane64 = threadIdx.x & 63;
-#ifdef TCLIP_PHASE_CLOCK
-    long long tclk = __builtin_readcyclecounter();
-    pl.clk[6] += 1;
-#endif
     float s = 16.0f;
     bool in_domain = true;
     if (active) {
@@ -1493,8 +1415,7 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
     const bool tiny = __builtin_amdgcn_ballot_w64(smallest <= (int32_t)0x2d2febffu) != 0ull;      // 0x2d2febff = 1e-11f
     const float psi_s = digamma_pos_f32(s, tab);                    // the row sums of the wavefront's rows, one evaluation
     // phase A + phase B, until the dense passes have met every entry in a queue whose form is the one for its value
-    bool sort_now = !(TCLIP_SPLIT_LAZY && keep_placement && pl.valid);
-    TCLIP_CLK(0, tclk);
+    bool sort_now = !(keep_placement && pl.valid);
     for (;;) {
         if (sort_now) {
             split_place<E, G, KC>(beta, K, lane, my0, pl);
@@ -1502,7 +1423,6 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
         } else split_scatter<E, G, KC>(beta, K, lane, my0, pl);
         const int nA = pl.nA, nB = pl.nB, nC = pl.nC;
         wave_lds_handoff();
-        TCLIP_CLK(1, tclk);
         // phase B: the queues in dense passes; entry i leaves with lgamma(a+1) in plane 0 and digamma(a+1) in plane 1.
         // A lane beyond the end of its queue in a last, partial pass takes the queue's LAST entry along with that entry's own lane:
         // same argument, same results, written to the same two words - so no pass needs an execution mask around its LDS
@@ -1554,7 +1474,6 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
             my0[i] = lg;
             my1[i] = psi;
         }
-        TCLIP_CLK(2, tclk);
         // (two entries per lane in these passes - two independent chains for the scheduler to interleave - measured no
         // different: K = 100 361 against 359 ms, K = 1000 equal; the passes are not latency-bound)
         auto pass_b = [&](int i) -> bool {                          // recurrence (eight masked steps: x + 8 >= 10) + series + general large-argument lgamma
@@ -1584,7 +1503,6 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
             const int l = min(lane64, tB + tC - 1);
             misplaced = pass_b(l < tB ? nA + endB + l : nA + nB + endC + (l - tB));
         }
-        TCLIP_CLK(3, tclk);
         for (int j = 0; !misplaced && j < endC; j += 64) {
             const int i = nA + nB + min(j + lane64, endC - 1);
             const float x = my0[i];
@@ -1594,11 +1512,7 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
             my0[i] = lg;
             my1[i] = psi;
         }
-        TCLIP_CLK(4, tclk);
         if (!misplaced) break;
-#ifdef TCLIP_PHASE_CLOCK
-        pl.clk[7] += 1;
-#endif
         sort_now = true;                                            // (the passes of a fresh placement check nothing: this loop runs twice at most)
         wave_lds_handoff();
     }
@@ -1611,12 +1525,11 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
     } else if (__builtin_expect(tiny, 0)) split_apply_updates<E, G, true, false>(beta, yv, K, lane, psi_s, my0, my1, pl.slot, num, den);
     else split_apply_updates<E, G, false, false>(beta, yv, K, lane, psi_s, my0, my1, pl.slot, num, den);
     wave_lds_handoff();
-    TCLIP_CLK(5, tclk);
 }
 
 template <int E, int G, int KC = 0>
-__global__ __launch_bounds__(64, (E > 16 ? TCLIP_MM_WAVES_LARGE : (E > 8 ? TCLIP_SPLIT_WAVES_MID : TCLIP_SPLIT_WAVES_SMALL))) void k_mm_split(MMArgs a) {
-    static_assert(E <= TCLIP_SPLIT_MAX_E, "LDS: two words per element");
+__global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void k_mm_split(MMArgs a) {
+    static_assert(E <= kSplitMaxE, "LDS: two words per element");
     __shared__ LogTabEntry tab[16];
     __shared__ float plane0[64 * E];
     __shared__ float plane1[64 * E];
@@ -1633,7 +1546,7 @@ __global__ __launch_bounds__(64, (E > 16 ? TCLIP_MM_WAVES_LARGE : (E > 8 ? TCLIP
         const bool active = i < n && !a.stop[row / a.rows_per_batch];
         if (!__any(active)) continue;
         float beta[E];
-        RowY<E, G, TCLIP_SPLIT_Y_REGS_MAX_E> yv;
+        RowY<E, G, kSplitYRegsMaxE> yv;
         double num = 0.0, den = 0.0;
         yv.load(a.y + (size_t)row * K, lane, K);
 #pragma unroll
@@ -1644,18 +1557,11 @@ __global__ __launch_bounds__(64, (E > 16 ? TCLIP_MM_WAVES_LARGE : (E > 8 ? TCLIP
         SplitPlacement<E> pl;
         pl.valid = false;
         pl.sorts = 0;
-#ifdef TCLIP_PHASE_CLOCK
-        for (int i = 0; i < 8; i++) pl.clk[i] = 0;
-#endif
         for (int l = a.l0; l <= a.l1; l++)
             mm_iterate_wave_split<E, G, KC>(beta, yv, K, lane, active, tab, plane0, plane1, a.has_check && l == a.l1, num, den, pl,
                                             a.keep_placement != 0);
         // per-wavefront instrumentation by lane 0 whether or not ITS lane group has a row (in the 16- and 32-lane layouts the
         // wavefront iterates as long as any of its groups does: __any(active) above)
-#ifdef TCLIP_PHASE_CLOCK
-        if ((threadIdx.x & 63) == 0)
-            for (int i = 0; i < 8; i++) atomicAdd(&g_phase_clock[i], (unsigned long long)pl.clk[i]);
-#endif
         if (a.work_counter && (threadIdx.x & 63) == 0) {           // [1]: wavefront-iterations of this kernel, [2]: full placements among them
             atomicAdd(a.work_counter + 1, (unsigned long long)(a.l1 - a.l0 + 1));
             atomicAdd(a.work_counter + 2, (unsigned long long)pl.sorts);
@@ -1678,17 +1584,6 @@ __global__ __launch_bounds__(64, (E > 16 ? TCLIP_MM_WAVES_LARGE : (E > 8 ? TCLIP
     }
 }
 
-#ifdef TCLIP_ISA_ONLY
-// ISA studies (scripts/isa_one.sh): only the K = 1000 MM kernels are instantiated - seconds instead of two minutes per compile.
-// Never part of a build of the library.
-template __global__ void k_mm_split<16, 64, 1000>(MMArgs);
-template __global__ void k_mm_live<16, 4, false, 1, 64, 1000>(MMArgs);
-#ifdef TCLIP_ISA_K100
-template __global__ void k_mm_split<7, 16, 100>(MMArgs);
-template __global__ void k_mm_split<13, 32, 397>(MMArgs);
-#endif
-}  // namespace tclip
-#else
 // Batch-global stop test (em_dirichlet.py:169-175), one block per batch:
 //   crit = ||b'-b||_F^2 / ||b||_F^2 over all N*K*K entries of the batch;  stop if < 1e-11.
 // fp64 accumulation in a fixed order; the final arithmetic follows the reference's fp32 form
@@ -1959,14 +1854,8 @@ __global__ __launch_bounds__(256) void k_kmeans_logits_rows(const float* __restr
 // bits: tests/test_gpu_round4.py::test_kmeans_tile_kernel_is_invisible runs both kernels on 20 row lengths.
 // Rows of 32 .. 511 elements (fewer than 16 steps: torch's cascade never dumps; 64 x 511 floats of LDS = 131 KB).
 constexpr int kKmeansTile = 64;
-#ifndef TCLIP_KMEANS_TILE_THREADS
-#define TCLIP_KMEANS_TILE_THREADS 1024    // the tile's LDS (101 KB at K = 397) allows one block per CU: sixteen wavefronts share it, four per SIMD (512: 74 against 66 ms per 1000-task SOFT_KMEANS call)
-#endif
-constexpr int kKmeansTileThreads = TCLIP_KMEANS_TILE_THREADS;
-#ifndef TCLIP_KMEANS_PREFETCH
-#define TCLIP_KMEANS_PREFETCH 1        // 1000 tasks, K = 397, 20 iterations of SOFT_KMEANS: 66.5 ms against 73.7 without
-#endif
-__global__ __launch_bounds__(TCLIP_KMEANS_TILE_THREADS) void k_kmeans_logits_tile(const float* __restrict__ w, const float* __restrict__ z,
+constexpr int kKmeansTileThreads = 1024;    // the tile's LDS (101 KB at K = 397) allows one block per CU: sixteen wavefronts share it, four per SIMD (512: 74 against 66 ms per 1000-task SOFT_KMEANS call)
+__global__ __launch_bounds__(kKmeansTileThreads) void k_kmeans_logits_tile(const float* __restrict__ w, const float* __restrict__ z,
                                                             const uint8_t* __restrict__ need, int Q, int K, int stride, float pre,
                                                             float temperature, float* __restrict__ logit0) {
     extern __shared__ float wt[];                                   // [kKmeansTile][stride]
@@ -2001,9 +1890,9 @@ __global__ __launch_bounds__(TCLIP_KMEANS_TILE_THREADS) void k_kmeans_logits_til
         float acc[32];
 #pragma unroll
         for (int sl = 0; sl < 32; sl++) acc[sl] = 0.0f;
-#if TCLIP_KMEANS_PREFETCH
         // the query row's next 32 values are requested (scalar loads, ~300 cycles from L2) before the current step's
         // arithmetic, not at their first use: with one block per CU there are too few wavefronts to hide that latency
+        // (1000 tasks, K = 397, 20 iterations of SOFT_KMEANS: 66.5 ms against 73.7 without)
         float zc[32];
 #pragma unroll
         for (int sl = 0; sl < 32; sl++) zc[sl] = zq[sl];
@@ -2020,15 +1909,6 @@ __global__ __launch_bounds__(TCLIP_KMEANS_TILE_THREADS) void k_kmeans_logits_til
 #pragma unroll
             for (int sl = 0; sl < 32; sl++) zc[sl] = zn[sl];
         }
-#else
-        for (int m = 0; m < size_ilp; m++) {
-#pragma unroll
-            for (int sl = 0; sl < 32; sl++) {
-                const float df = wl[32 * m + sl] - zq[32 * m + sl];
-                acc[sl] += df * df;
-            }
-        }
-#endif
         int d = 32 * size_ilp;
         for (int i = 0; i < nleft; i++, d += 8) {                   // whole vectors beyond the 4-way part join accumulator 0
 #pragma unroll
@@ -2187,12 +2067,6 @@ __global__ __launch_bounds__(256) void k_softmax(const float* logit0, const floa
 // 10^6 elements, oracle/mathcheck.cpp::mc_norm8).  One wavefront per task; lane j (and its seven copies 8 i + j) owns
 // accumulator j.  The chain of n/8 dependent FMAs per accumulator is inherent; everything else is kept off it (main loop
 // below).  (A variant with four tasks per wavefront and DPP operands had a quarter of the wavefronts and was slower.)
-#ifndef TCLIP_CRITERION_PACKED
-#define TCLIP_CRITERION_PACKED 1
-#endif
-#ifndef TCLIP_CRITERION_DEPTH
-#define TCLIP_CRITERION_DEPTH 8
-#endif
 __global__ __launch_bounds__(64) void k_criterion(const float* __restrict__ alpha, float* __restrict__ alpha_old, int K, int T,
                                                   float* __restrict__ ratio) {
     const int t = blockIdx.x, lane = threadIdx.x, j = lane & 7;
@@ -2218,7 +2092,7 @@ __global__ __launch_bounds__(64) void k_criterion(const float* __restrict__ alph
     // call): not the look-ahead - blocks of 1024 / 2048 elements (one block's chain then lasts as long as a trip to HBM) were 3 % / 11 %
     // SLOWER - and not the packed form - the two chains as interleaved plain v_fma_f32 were 12 % slower: the cadence of the dependent
     // chain itself (~22 clocks per element), which is the reference's order (profiles/r06_ab_criterion.txt).
-    constexpr int kDepth = TCLIP_CRITERION_DEPTH, kRow = 8 * kDepth + 4;    // rows of 8 kDepth (d, o) pairs, padded by 4: the transposing 8-byte writes of a half-wavefront hit 32 different bank pairs
+    constexpr int kDepth = 8, kRow = 8 * kDepth + 4;    // rows of 8 kDepth (d, o) pairs, padded by 4: the transposing 8-byte writes of a half-wavefront hit 32 different bank pairs
     __shared__ __attribute__((aligned(16))) float2 sdo[8 * kRow];
     if (s0 + 64 * kDepth <= nv) {
         const int wi = lane >> 3;                             // this lane holds operand 8 k + wi of accumulator j in chunk k
@@ -2248,17 +2122,9 @@ __global__ __launch_bounds__(64) void k_criterion(const float* __restrict__ alph
 #pragma unroll
             for (int m = 0; m < 4 * kDepth; m++) {
                 const float4 v = *reinterpret_cast<const float4*>(&sdo[j * kRow + 2 * m]);
-#if TCLIP_CRITERION_PACKED
                 const f2 p0{v.x, v.y}, p1{v.z, v.w};
                 acc = pk_fma(p0, p0, acc);
                 acc = pk_fma(p1, p1, acc);
-#else
-                // the two chains as plain FMAs, interleaved (measured slower, see above)
-                acc.x = __builtin_fmaf(v.x, v.x, acc.x);
-                acc.y = __builtin_fmaf(v.y, v.y, acc.y);
-                acc.x = __builtin_fmaf(v.z, v.z, acc.x);
-                acc.y = __builtin_fmaf(v.w, v.w, acc.y);
-#endif
             }
             __syncthreads();                                  // ... and the reads before the next block's writes
         }
@@ -2504,7 +2370,7 @@ __global__ __launch_bounds__(256) void k_kl_divergences(const float* __restrict_
 // z + 1e-15 lies inside the fast forms' range (positive normal, |exponent| <= 60) whenever z itself is +0 .. 2^60: a test on
 // the bits of the wave-uniform z, i.e. on the scalar unit (sufficient, not necessary: anything else takes the generic forms)
 __device__ __forceinline__ bool kl_p_surely_fast(float z) { return f32_bits(z) <= 0x5d800000u; }
-__global__ __launch_bounds__(TCLIP_KMEANS_TILE_THREADS) void k_kl_divergences_tile(const float* __restrict__ w, const float* __restrict__ z,
+__global__ __launch_bounds__(kKmeansTileThreads) void k_kl_divergences_tile(const float* __restrict__ w, const float* __restrict__ z,
                                                                                   int Q, int K, int stride, float* __restrict__ divs) {
     extern __shared__ float wt[];                                   // [kKmeansTile][stride]: w + eps
     __shared__ uint32_t s_buckets[64];
@@ -2932,8 +2798,8 @@ struct Profile {
 };
 static thread_local bool g_last_mm_was_split = false;     // which kernel the last launch_mm(kMMSplit / kMMLive) started
 thread_local Profile g_prof;
-static int g_probe_chunks = TCLIP_PROBE_CHUNKS;     // tclip_debug_set_probe_chunks
-static int g_dead_head = TCLIP_DEAD_HEAD;           // tclip_debug_set_dead_head: iterations a fresh dead row runs before the early probe; 0 = no early probe
+static int g_probe_chunks = kProbeChunks;           // tclip_debug_set_probe_chunks
+static int g_dead_head = kDeadHead;                 // tclip_debug_set_dead_head: iterations a fresh dead row runs before the early probe; 0 = no early probe
 static int g_rowset_min_rows = -1;                  // tclip_debug_set_rowset_min_rows; negative: the default rule
 static int g_mm_split = -1;                         // tclip_debug_set_mm_split: 0 never, 1 always, negative: from the second outer iteration on
 static int g_split_keep_placement = 1;              // tclip_debug_set_split_keep_placement: 0 = k_mm_split sorts its queues in every iteration
@@ -3028,29 +2894,27 @@ static void dispatch_E(int K, Args... args) {
 // over 16 lanes (4 rows per wavefront, E = ceil(K / 16) registers), which fills the lanes (K = 100: 89 % as 16 x 7
 // instead of 78 % as 32 x 4; K = 10: 62 % instead of 31 %) and shares the per-row work among more rows.  Measured on
 // 1000 tasks (MM loop, 32 -> 16 lanes): K = 10 95 -> 71 ms, K = 37 186 -> 151, K = 47 217 -> 174, K = 100 476 -> 411
-// (460 with round 1's two rows per 32-lane group), K = 196 974 -> 895.  g_rowset_min_rows == 0 (test hook) forces the
-// 32-lane layout, which must give the same bits.
-#ifndef TCLIP_LOGITS_GRID
-#define TCLIP_LOGITS_GRID 16384
-#endif
-#ifndef TCLIP_G8_MAX_K
-#define TCLIP_G8_MAX_K 0              // 8 lanes per row: measured slower than 16 at 1000 tasks (too few wavefronts: K = 10 / 37 / 47:
-                                      // 81 / 166 / 211 ms against 71 / 151 / 174), 2 % faster at 3000 tasks of K = 100; not compiled by default
-#endif
-#ifndef TCLIP_G16_MAX_K
-#define TCLIP_G16_MAX_K 256
-#endif
-#ifndef TCLIP_MM_LAUNCH_WAVES
-#define TCLIP_MM_LAUNCH_WAVES 4
-#endif
+// (460 with round 1's two rows per 32-lane group), K = 196 974 -> 895.  8 lanes per row measured slower than 16 at 1000
+// tasks (too few wavefronts: K = 10 / 37 / 47: 81 / 166 / 211 ms against 71 / 151 / 174), 2 % faster at 3000 tasks of
+// K = 100.  g_rowset_min_rows == 0 (test hook) forces the 32-lane layout, which must give the same bits.
+constexpr int kG16MaxK = 256;
+static_assert(kG16MaxK >= 100 && kG16MaxK < 397 && kG64MinK <= 1000,
+              "launch_mm's fixed-K kernels: K = 100 in the 16-lane, 397 in the 32-lane, 1000 in the 64-lane layout");
+// lanes per row of the MM kernels for rows of K elements (the 64-lane layout needs the cascade's first dump, K >= 512:
+// kG64MinK >= 897)
+static int mm_lanes_per_row(int K) {
+    if (g_rowset_min_rows == 0) return 32;
+    if (K >= kG64MinK) return 64;
+    return K <= kG16MaxK ? 16 : 32;
+}
 enum MMKind { kMMLive = 0, kMMDead = 1, kMMProbe = 2, kMMSplit = 3, kMMProbeHead = 4 };
 template <int E, int G, int KC = 0>
 static void launch_mm_EG(int dead, int rows, hipStream_t st, const MMArgs& a) {
-    constexpr int kWaves = TCLIP_MM_LAUNCH_WAVES, kRowsPerBlock = (64 / G) * kWaves;
+    constexpr int kWaves = 4, kRowsPerBlock = (64 / G) * kWaves;
     int grid = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
     if (grid > 256 * 16) grid = 256 * 16;
-    if (dead == kMMSplit) {                        // live rows through the class-split kernel where it exists (TCLIP_SPLIT_MIN_E <= E <= TCLIP_SPLIT_MAX_E)
-        if constexpr (E <= TCLIP_SPLIT_MAX_E && E >= TCLIP_SPLIT_MIN_E) {
+    if (dead == kMMSplit) {                        // live rows through the class-split kernel where it exists (kSplitMinE <= E <= kSplitMaxE)
+        if constexpr (E <= kSplitMaxE && E >= kSplitMinE) {
             constexpr int kSplitRows = 64 / G;           // one wavefront per block
             int sgrid = (rows + kSplitRows - 1) / kSplitRows;
             if (sgrid > 256 * 64) sgrid = 256 * 64;
@@ -3068,16 +2932,14 @@ static void launch_mm_EG(int dead, int rows, hipStream_t st, const MMArgs& a) {
 }
 template <int G>
 static void launch_mm_G(int need, int dead, int rows, hipStream_t st, const MMArgs& a) {
-    if (G < 32 || need <= 8) {
-        if (need <= 1) return launch_mm_EG<1, G>(dead, rows, st, a);
-        if (need <= 2) return launch_mm_EG<2, G>(dead, rows, st, a);
-        if (need <= 3) return launch_mm_EG<3, G>(dead, rows, st, a);
-        if (need <= 4) return launch_mm_EG<4, G>(dead, rows, st, a);
-        if (need <= 5) return launch_mm_EG<5, G>(dead, rows, st, a);
-        if (need <= 6) return launch_mm_EG<6, G>(dead, rows, st, a);
-        if (need <= 7) return launch_mm_EG<7, G>(dead, rows, st, a);
-        if (need <= 8) return launch_mm_EG<8, G>(dead, rows, st, a);
-    }
+    if (need <= 1) return launch_mm_EG<1, G>(dead, rows, st, a);
+    if (need <= 2) return launch_mm_EG<2, G>(dead, rows, st, a);
+    if (need <= 3) return launch_mm_EG<3, G>(dead, rows, st, a);
+    if (need <= 4) return launch_mm_EG<4, G>(dead, rows, st, a);
+    if (need <= 5) return launch_mm_EG<5, G>(dead, rows, st, a);
+    if (need <= 6) return launch_mm_EG<6, G>(dead, rows, st, a);
+    if (need <= 7) return launch_mm_EG<7, G>(dead, rows, st, a);
+    if (need <= 8) return launch_mm_EG<8, G>(dead, rows, st, a);
     if (need <= 10) return launch_mm_EG<10, G>(dead, rows, st, a);
     if (need <= 13) return launch_mm_EG<13, G>(dead, rows, st, a);
     if (need <= 16) return launch_mm_EG<16, G>(dead, rows, st, a);
@@ -3088,9 +2950,9 @@ static void launch_mm_G(int need, int dead, int rows, hipStream_t st, const MMAr
         return launch_mm_EG<32, G>(dead, rows, st, a);
     }
 }
-// registers per lane launch_mm_G<G> picks for `need`
-static int mm_regs_of(int need, int G) {
-    if ((G < 32 || need <= 8) && need <= 8) return need;
+// registers per lane launch_mm_G picks for `need`
+static int mm_regs_of(int need) {
+    if (need <= 8) return need;
     if (need <= 10) return 10;
     if (need <= 13) return 13;
     if (need <= 16) return 16;
@@ -3100,43 +2962,25 @@ static int mm_regs_of(int need, int G) {
 }
 // does launch_mm(kMMSplit, K, ..) start k_mm_split (true) or fall back to k_mm_live (no instantiation for this row length)?
 static bool mm_has_split(int K) {
-    const bool wide = g_rowset_min_rows == 0;
-    int E;
-    if (K >= TCLIP_G64_MIN_K && K >= 512 && !wide && TCLIP_G64_MIN_K > 0) E = 16;
-    else if (K <= TCLIP_G8_MAX_K && !wide) E = mm_regs_of((K + 7) / 8, 8);            // launch_mm's order of tests
-    else if (K <= TCLIP_G16_MAX_K && !wide) E = mm_regs_of((K + 15) / 16, 16);
-    else E = mm_regs_of((K + 31) / 32, 32);
-    return E <= TCLIP_SPLIT_MAX_E && E >= TCLIP_SPLIT_MIN_E;
+    const int G = mm_lanes_per_row(K);
+    const int E = G == 64 ? 16 : mm_regs_of((K + G - 1) / G);
+    return E <= kSplitMaxE && E >= kSplitMinE;
 }
 // Row lengths the MM kernels are also compiled for as constants - the class counts of the reference's datasets that BASELINE.json
 // runs (ImageNet 1000, SUN397 397, Caltech101-sized 100): same code, same layout as the run-time-K kernel of the row length's
 // bucket, with every mask and tail of a ragged last register resolved by the compiler (round 4: the run-time forms kept
-// 2 x 4 lane masks per row sum in spilled scalar registers).  g_fixed_k_kernels == 0 (tclip_debug_set_fixed_k_kernels, tests):
-// the run-time-K kernels for every row length, which must give the same bits.
-#ifndef TCLIP_FIXED_K_DEFAULT
-#define TCLIP_FIXED_K_DEFAULT 1
-#endif
-static int g_fixed_k_kernels = TCLIP_FIXED_K_DEFAULT;
+// 2 x 4 lane masks per row sum in spilled scalar registers).  g_fixed_k_kernels == 0 (tclip_debug_set_fixed_k_kernels, tests)
+// or the 32-lane test hook: the run-time-K kernels for every row length, which must give the same bits.
+static int g_fixed_k_kernels = 1;
 static void launch_mm(int dead, int K, int rows, hipStream_t st, const MMArgs& a) {
-    const bool wide = g_rowset_min_rows == 0;              // test hook: the 32-lane layout for every row length
-    if (!wide && g_fixed_k_kernels && dead != kMMProbe && dead != kMMProbeHead) {
-#if TCLIP_G64_MIN_K > 0 && TCLIP_G64_MIN_K <= 1000
+    if (g_rowset_min_rows != 0 && g_fixed_k_kernels && dead != kMMProbe && dead != kMMProbeHead) {
         if (K == 1000) return launch_mm_EG<16, 64, 1000>(dead, rows, st, a);
-#endif
-#if TCLIP_G16_MAX_K < 397
         if (K == 397) return launch_mm_EG<13, 32, 397>(dead, rows, st, a);
-#endif
-#if TCLIP_G16_MAX_K >= 100 && TCLIP_G8_MAX_K < 100
         if (K == 100) return launch_mm_EG<7, 16, 100>(dead, rows, st, a);
-#endif
     }
-#if TCLIP_G64_MIN_K > 0
-    if (K >= TCLIP_G64_MIN_K && K >= 512 && !wide) return launch_mm_EG<16, 64>(dead, rows, st, a);   // 512: the cascade's first dump
-#endif
-#if TCLIP_G8_MAX_K > 0
-    if (K <= TCLIP_G8_MAX_K && !wide) return launch_mm_G<8>((K + 7) / 8, dead, rows, st, a);
-#endif
-    if (K <= TCLIP_G16_MAX_K && !wide) launch_mm_G<16>((K + 15) / 16, dead, rows, st, a);
+    const int G = mm_lanes_per_row(K);
+    if (G == 64) launch_mm_EG<16, 64>(dead, rows, st, a);
+    else if (G == 16) launch_mm_G<16>((K + 15) / 16, dead, rows, st, a);
     else launch_mm_G<32>((K + 31) / 32, dead, rows, st, a);
 }
 template <int E> struct LaunchRowConsts {
@@ -3144,6 +2988,8 @@ template <int E> struct LaunchRowConsts {
         hipLaunchKernelGGL(k_row_consts<E>, dim3(grid), dim3(256), 0, st, alpha, rows, n, K, rowc);
     }
 };
+// k_logits blocks per launch at most (the kernel strides over the rows beyond)
+constexpr int kLogitsGrid = 16384;
 template <int E> struct LaunchLogits {
     static void run(int grid, hipStream_t st, const float* alpha, const float* logz, const float* rowc,
                     const int32_t* rows, const int32_t* n, int Q, int K, float* logit0, const int32_t* only_if) {
@@ -3176,7 +3022,8 @@ template <int E> struct LaunchKmeansLogitsRows {
     }
 };
 
-static int g_kmeans_tile = -1;       // tclip_debug_set_kmeans_tile: 0 = k_kmeans_logits_rows for every K, negative: the default rule
+static int g_kmeans_tile = -1;       // tclip_debug_set_kmeans_tile: 0 = the round-3 kernels for every shape (k_kmeans_logits_rows, k_mstats_rows,
+                                     // ...) instead of the tile and 75-column kernels, negative: the default rule
 // squared distances to the centroids: one lane per class where the row length allows it (k_kmeans_logits_tile), else 32 lanes per class
 // the tile kernels' dynamic LDS goes beyond the 64 KB a kernel gets without asking (once per kernel and process)
 static bool kmeans_tile_lds_raised(const void* kernel) {
@@ -3211,21 +3058,14 @@ static void launch_kmeans_logits(int T, hipStream_t st, const float* w, const fl
 // consecutive workgroups to the eight XCDs in turn and every XCD has its own L2: with the task as the slowest grid dimension
 // the (K/64)^2 blocks of one task landed on all eight XCDs and each L2 fetched the task's u and f (2 x 119 KB at K = 397)
 // for itself.  Here the grid is one-dimensional: block L runs on XCD L % 8 and works on task 8 (L / 8 / tiles) + L % 8, tile
-// (L / 8) % tiles of it - the blocks of ONE task go to ONE XCD, whose L2 holds the operands once.
-// TCLIP_XCD_MAP=0 (A/B builds): the plain order, task slowest.
-#ifndef TCLIP_XCD_MAP
-#define TCLIP_XCD_MAP 1
-#endif
+// (L / 8) % tiles of it - the blocks of ONE task go to ONE XCD, whose L2 holds the operands once (against the plain order,
+// task slowest: profiles/r06_ab_xcd_map.txt).
 constexpr int kXcds = 8;
 struct TaskTile { int t, bx, by; };
 __device__ __forceinline__ TaskTile task_tile_of_block(int nx, int ny) {
     const int per_task = nx * ny;
-#if TCLIP_XCD_MAP
     const int slot = blockIdx.x / kXcds, xcd = blockIdx.x % kXcds;
     const int t = (slot / per_task) * kXcds + xcd, inner = slot % per_task;
-#else
-    const int t = blockIdx.x / per_task, inner = blockIdx.x % per_task;
-#endif
     return TaskTile{t, inner % nx, inner / nx};                 // the caller returns at once when t >= T
 }
 static unsigned task_tile_grid(int nx, int ny, int T) { return (unsigned)((long)((T + kXcds - 1) / kXcds) * kXcds * nx * ny); }
@@ -3389,16 +3229,8 @@ __global__ __launch_bounds__(256) void k_live_class_lists(const uint8_t* __restr
 // per task alive and stays with the column kernel, which skips by eight.
 // Blocks of one task share an XCD (task_tile_of_block).
 constexpr int kTileQ = 75, kTileBlock = 64;
-#ifndef TCLIP_TILE_STAGE_BOTH
-#define TCLIP_TILE_STAGE_BOTH 1
-#endif
-#ifndef TCLIP_TILE_PREFETCH
-#define TCLIP_TILE_PREFETCH 1
-#endif
-#ifndef TCLIP_TILE_WAVES
-#define TCLIP_TILE_WAVES 3
-#endif
-__global__ __launch_bounds__(256, TCLIP_TILE_WAVES) void k_mstats_tile75(const float* __restrict__ u, const float* __restrict__ f,
+constexpr int kTileWaves = 3;   // wavefronts per SIMD: 160 VGPRs (bounded to 128 for four, the epilogue spills: +11 %)
+__global__ __launch_bounds__(256, kTileWaves) void k_mstats_tile75(const float* __restrict__ u, const float* __restrict__ f,
                                                        const float* __restrict__ cs, const uint8_t* __restrict__ live,
                                                        const float* __restrict__ sup, const float* __restrict__ cnt, int K, int T,
                                                        int k_rows, int tiles_d, int tiles_k, float* __restrict__ y, int paddle,
@@ -3421,7 +3253,6 @@ __global__ __launch_bounds__(256, TCLIP_TILE_WAVES) void k_mstats_tile75(const f
         const int dc = d0 + lane < K ? d0 + lane : K - 1;
         const float* fp = f + ((size_t)t * kTileQ + wave) * K + dc;
         const float* upg = u + ((size_t)t * kTileQ + wave) * K + kc;
-#if TCLIP_TILE_STAGE_BOTH
         float fr[19], ur[19];
 #pragma unroll
         for (int j = 0; j < 19; j++) {
@@ -3436,20 +3267,6 @@ __global__ __launch_bounds__(256, TCLIP_TILE_WAVES) void k_mstats_tile75(const f
                 ut[(4 * j + wave) * kTileBlock + lane] = ur[j];
             }
         }
-#else
-        // one operand at a time: nineteen loads in flight, then their nineteen LDS writes (both operands at once were 38 registers
-        // that the accumulators' 32 and the double-buffered reads did not leave room for at four wavefronts per SIMD)
-        auto stage = [&](const float* src, float* dst) {
-            float r[19];
-#pragma unroll
-            for (int j = 0; j < 19; j++) r[j] = (j < 18 || wave < kTileQ - 72) ? src[(size_t)4 * j * K] : 0.0f;   // 4 * 18 + wave < 75
-#pragma unroll
-            for (int j = 0; j < 19; j++)
-                if (j < 18 || wave < kTileQ - 72) dst[(4 * j + wave) * kTileBlock + lane] = r[j];
-        };
-        stage(fp, zt);
-        stage(upg, ut);
-#endif
     }
     __syncthreads();
     const int kw = kb + 32 * (wave >> 1), dw = d0 + 32 * (wave & 1);       // this wavefront's 32 x 32 tile (kw: its first slot)
@@ -3461,7 +3278,7 @@ __global__ __launch_bounds__(256, TCLIP_TILE_WAVES) void k_mstats_tile75(const f
 #pragma unroll
     for (int i = 0; i < 4; i++) a0[i][0] = a0[i][1] = a1[i][0] = a1[i][1] = pk(0.0f);
     // the operands of query q + 1 are requested before the sixteen packed instructions of query q (the LDS answers in order,
-    // so the wait before them is for the older pair only)
+    // so the wait before them is for the older pair only; without this prefetch the kernel is 2.5 % slower)
     auto fetch = [&](int q, float4& uv, float4& fv) {
         uv = *(const float4*)(up + q * kTileBlock);
         fv = *(const float4*)(zp + q * kTileBlock);
@@ -3481,15 +3298,9 @@ __global__ __launch_bounds__(256, TCLIP_TILE_WAVES) void k_mstats_tile75(const f
     for (int g = 0; g < kTileQ / 16; g++) {                                 // four groups of sixteen queries, a dump after each
 #pragma unroll
         for (int i = 0; i < 16; i++) {
-#if TCLIP_TILE_PREFETCH
             const float4 uc = un, fc = fn;
             fetch(16 * g + i + 1, un, fn);                                  // (query 64 after the last group: the leftovers' first)
             apply(uc, fc);
-#else
-            float4 uc, fc;
-            fetch(16 * g + i, uc, fc);
-            apply(uc, fc);
-#endif
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -3499,15 +3310,9 @@ __global__ __launch_bounds__(256, TCLIP_TILE_WAVES) void k_mstats_tile75(const f
     }
 #pragma unroll
     for (int q = 16 * (kTileQ / 16); q < kTileQ; q++) {                     // the last eleven
-#if TCLIP_TILE_PREFETCH
         const float4 uc = un, fc = fn;
         if (q + 1 < kTileQ) fetch(q + 1, un, fn);
         apply(uc, fc);
-#else
-        float4 uc, fc;
-        fetch(q, uc, fc);
-        apply(uc, fc);
-#endif
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -3594,11 +3399,6 @@ __global__ __launch_bounds__(64 * kColsWaves) void k_kl_centroids_cols75(const f
     }
 }
 
-static int g_mstats_cols = -1;          // tclip_debug_set_kmeans_tile also switches this kernel (0: k_mstats_rows for every shape)
-#ifndef TCLIP_MSTATS_TILE
-#define TCLIP_MSTATS_TILE -1
-#endif
-static int g_mstats_tile = TCLIP_MSTATS_TILE;          // tclip_debug_set_kmeans_tile switches this kernel too (0: never)
 template <bool kCov>
 static void launch_mstats_mode(hipStream_t st, const float* u, const float* f, const float* cs, const uint8_t* live,
                                const float* sup, const float* cnt, int T, int Q, int K, float* y, int paddle, const float* wc,
@@ -3606,7 +3406,7 @@ static void launch_mstats_mode(hipStream_t st, const float* u, const float* f, c
     const long ncols = (long)K * K;
     const int full_rows = ncols >= 8 ? (int)(((ncols / 32) * 32) / K) : 0;      // rows 0 .. full_rows-1 are all-cascade
     int groups = full_rows / kMstatsRows;
-    if (!kCov && (dense || cls) && Q == kTileQ && full_rows >= 32 && g_mstats_tile != 0) {
+    if (!kCov && (dense || cls) && Q == kTileQ && full_rows >= 32 && g_kmeans_tile != 0) {
         // 32 x 32 register tiles, both operands through LDS: over all classes where (nearly) every class is alive (the caller's
         // word), over the compacted list of the live ones where the caller provides room for it (cls, n_live)
         const int tiles_d = (K + kTileBlock - 1) / kTileBlock, tiles_k = (full_rows + kTileBlock - 1) / kTileBlock;
@@ -3618,7 +3418,7 @@ static void launch_mstats_mode(hipStream_t st, const float* u, const float* f, c
                                paddle, full_rows, wc);
         return;
     }
-    if (Q == kColsQ && full_rows >= kColsChunk && g_mstats_cols != 0) {
+    if (Q == kColsQ && full_rows >= kColsChunk && g_kmeans_tile != 0) {
         // the column kernel takes every row of the cascade region; enough blocks to fill the machine, at least 32 rows each
         const int dtiles = (K + 63) / 64;
         int splits = (int)((8192 + (long)T * dtiles - 1) / ((long)T * dtiles));
@@ -3770,7 +3570,7 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
             a.has_check = (a.l1 > 0 && a.l1 % 50 == 0) ? 1 : 0;
             a.n_checks = n_checks > 0 ? n_checks : 1;
             // class-split kernel once the parameters have moved away from their start at 1 (k_mm_split)
-            const bool split = g_mm_split < 0 ? it >= TCLIP_SPLIT_FROM : (g_mm_split >= 100 ? it >= g_mm_split - 100 : g_mm_split != 0);
+            const bool split = g_mm_split < 0 ? it >= kSplitFrom : (g_mm_split >= 100 ? it >= g_mm_split - 100 : g_mm_split != 0);
             const bool split_runs = split && mm_has_split(K);
             a.work_counter = g_prof.on ? g_prof.counter + (split_runs ? 1 : 0) : nullptr;
             hipEvent_t e0 = g_prof.on ? prof_event() : nullptr, e1 = g_prof.on ? prof_event() : nullptr;
@@ -3787,7 +3587,7 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
             if (zs && a.has_check) {          // dead rows only matter through their stop-test terms
                 a.rows = dead_list[c & 1]; a.n_rows = dead_counts + c; a.work_counter = nullptr;
                 if (c == 0 && g_dead_head > 0 && g_probe_chunks > 0) {
-                    // rows that have just died: TCLIP_DEAD_HEAD iterations, then the early probe (k_mm_probe_head), which finishes
+                    // rows that have just died: g_dead_head iterations, then the early probe (k_mm_probe_head), which finishes
                     // every row it finds on its cycle; what is left over takes the path below from the start
                     MMArgs h = a;
                     h.l0 = 0; h.l1 = g_dead_head - 1; h.has_check = 0; h.next_rows = nullptr; h.next_count = nullptr;
@@ -3820,7 +3620,7 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
             const int g8 = (TK + 7) / 8 > 65535 * 8 ? 65535 * 8 : (TK + 7) / 8;
             dispatch_E<LaunchRowConsts>(K, g8 > 4096 ? 4096 : g8, st, (const float*)alpha, (const int32_t*)live_rows,
                                         (const int32_t*)(counts + 1), K, rowc);
-            dispatch_E<LaunchLogits>(K, TK > TCLIP_LOGITS_GRID ? TCLIP_LOGITS_GRID : TK, st, (const float*)alpha, (const float*)logz, (const float*)rowc,
+            dispatch_E<LaunchLogits>(K, TK > kLogitsGrid ? kLogitsGrid : TK, st, (const float*)alpha, (const float*)logz, (const float*)rowc,
                                      (const int32_t*)live_rows, (const int32_t*)(counts + 1), Q, K, logit0, (const int32_t*)nullptr);
         }
         hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
@@ -4375,7 +4175,7 @@ int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, flo
     for (int it = 0; it < p.iters; it++) {
         hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
                            live, (float*)nullptr, (int32_t*)nullptr);
-        if (Q == kColsQ && K >= kColsChunk && g_mstats_cols != 0) {
+        if (Q == kColsQ && K >= kColsChunk && g_kmeans_tile != 0) {
             const int dtiles = (K + 63) / 64;
             int splits = (int)((8192 + (long)T * dtiles - 1) / ((long)T * dtiles));
             if (splits > K / (kColsWaves * kColsChunk)) splits = K / (kColsWaves * kColsChunk);
@@ -4431,8 +4231,6 @@ int tclip_debug_set_rowset_min_rows(int32_t rows) {
 
 int tclip_debug_set_kmeans_tile(int32_t mode) {
     g_kmeans_tile = mode;
-    g_mstats_cols = mode;
-    g_mstats_tile = mode < 0 ? TCLIP_MSTATS_TILE : mode;
     return TCLIP_OK;
 }
 
@@ -4454,11 +4252,11 @@ int tclip_debug_set_split_keep_placement(int32_t on) {
 int tclip_debug_set_dead_head(int32_t iterations) {
     // the early probe needs its last snapshot (32 iterations in) to lie at or before the first checkpoint (iteration 50)
     if (iterations > 18) return fail(TCLIP_ERR_ARG, "tclip_debug_set_dead_head: at most 18 iterations");
-    g_dead_head = iterations < 0 ? TCLIP_DEAD_HEAD : iterations;
+    g_dead_head = iterations < 0 ? kDeadHead : iterations;
     return TCLIP_OK;
 }
 int tclip_debug_set_probe_chunks(int32_t chunks) {
-    g_probe_chunks = chunks < 0 ? TCLIP_PROBE_CHUNKS : chunks;
+    g_probe_chunks = chunks < 0 ? kProbeChunks : chunks;
     return TCLIP_OK;
 }
 
@@ -4534,26 +4332,6 @@ int tclip_profile_last_kernels(double* busy_ms, double* launch_ms_sum, int64_t* 
     return TCLIP_OK;
 }
 
-#ifdef TCLIP_COUNT_SMALL
-int tclip_debug_small_count(uint64_t* out) {        // reads and clears g_small_count (only in builds with -DTCLIP_COUNT_SMALL)
-    unsigned long long h[4];
-    TCLIP_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(tclip::g_small_count), sizeof h));
-    for (int i = 0; i < 4; i++) { out[i] = h[i]; h[i] = 0; }
-    TCLIP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(tclip::g_small_count), h, sizeof h));
-    return TCLIP_OK;
-}
-#endif
-#ifdef TCLIP_PHASE_CLOCK
-int tclip_debug_phase_clock(uint64_t* out) {        // reads and clears g_phase_clock (only in builds with -DTCLIP_PHASE_CLOCK)
-    TCLIP_HIP(hipDeviceSynchronize());
-    unsigned long long h[8];
-    TCLIP_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(tclip::g_phase_clock), sizeof h));
-    for (int i = 0; i < 8; i++) out[i] = h[i];
-    memset(h, 0, sizeof h);
-    TCLIP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(tclip::g_phase_clock), h, sizeof h));
-    return TCLIP_OK;
-}
-#endif
 int tclip_profile_last_split_sorts(int64_t* wave_iterations, int64_t* sorts) {
     if (wave_iterations) *wave_iterations = g_prof.last_split_iterations;
     if (sorts) *sorts = g_prof.last_split_sorts;
@@ -4645,4 +4423,3 @@ int tclip_gather_rows(const float* table, int64_t n_rows, int32_t K, const int64
 
 #include "tclip_tim.inc"
 #include "tclip_lshot.inc"
-#endif  // TCLIP_ISA_ONLY

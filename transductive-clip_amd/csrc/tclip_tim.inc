@@ -69,10 +69,7 @@ __global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int K, f
 //   kTN = true  (dW):      C[m][n] = sum_i G[i][m] X_i[n]         both operands contiguous along the tile dimension
 // Epilogue: the logits' scaling and norms, or (dW) the column sums of G by the blocks of the first column tile.
 // TILE = 128 (2 x 2 MFMA tiles per wavefront) loses to partial tiles and to fewer blocks: K = 397 25.4, K = 1000 48.9 TFLOP/s.
-#ifndef TCLIP_TIM_MFMA_DEPTH
-#define TCLIP_TIM_MFMA_DEPTH 16      // measured at 64 x 64 tiles: depth 16 52.7, 32 45.9, 64 25.2 TFLOP/s (K = 1000, S = 4000, 4 tasks)
-#endif
-constexpr int kTimMfmaDepth = TCLIP_TIM_MFMA_DEPTH;
+constexpr int kTimMfmaDepth = 16;    // measured at 64 x 64 tiles: depth 16 52.7, 32 45.9, 64 25.2 TFLOP/s (K = 1000, S = 4000, 4 tasks)
 typedef float tim_f16x __attribute__((ext_vector_type(16)));
 
 // TILE = 64: one 32 x 32 MFMA tile per wavefront (more, smaller blocks: few tasks, class counts just above a multiple of 64);
