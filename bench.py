@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: transductive tasks/sec of the EM-Dirichlet hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Headline workload = the north-star shape, BASELINE.json configs[3] as it lands on one GPU:
@@ -17,11 +17,14 @@ feature table resident in HBM (indices drawn beforehand, identically on every ra
 reference's sampler), one engine call for the rank's batches, the accuracy tail (device prototypes,
 host assignment), and for N>1 the single RCCL all_gather of the per-task accuracies onto rank 0.
 
-stdout carries ONE compact JSON line (the contract's fields, `roofline`, `cpu_baseline`, one figure per secondary
-workload; a few kB - round 5's 20 kB line was more than the driver's reader takes); the full record described below
-goes to gpurun_out/bench_full.json and to stderr (`full_record` on the line names the file).
+A plain run does what the headline figure needs and no more: set-up, the warm-up and timed steps, the files of
+--dump-outputs if asked for, and ONE compact JSON line on stdout (the contract's fields and `roofline`, which comes from
+the timed steps' own launch profile).  `--full` adds the measurements that take runs of their own, several minutes
+more: the `secondary` workloads and the `cpu_baseline` figures (`--no-secondary` / `--no-cpu-baseline` leave one of
+them out), one figure per workload on the line, which stays a few kB.  The full record described below goes to a
+JSON file and to stderr (`full_record` on the line names the file).
 
-Objects of the full record (the line carries their essential fields):
+Objects of the full record (the line carries their essential fields; `secondary` and `cpu_baseline` with --full only):
   roofline     the dominant kernels - k_mm_live (first outer iteration) and k_mm_split (the later ones), the MM loop of
                the live rows (`per_kernel`: each of the two alone) - timed live with HIP events around each of their launches on the streams they run on
                (independent batches use a few internal streams, so launches overlap: `achieved` divides by the time
@@ -406,13 +409,16 @@ def roofline_of(prof, steps, K, pmc_key):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary workloads (one GPU, --workload k1000) and the CPU baselines "
+                         "(one GPU): several minutes more; a plain run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary workloads")
     ap.add_argument("--workload", choices=["k1000", "k100", "k397_hard", "fs_k1000"], default="k1000",
                     help="k1000: the headline (default); k100: the round-1 shape as the headline; k397_hard / fs_k1000: only that "
                          "secondary workload (BASELINE configs[2] / configs[4]), for profiling")
@@ -424,11 +430,18 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the headline path delivered in its last step to DIR/<name>.npy "
                          "(float32 / float64, at most 64 MB; the inputs are the same on every run with the same arguments)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_outputs and args.workload in ("k397_hard", "fs_k1000"):
         ap.error("--dump-outputs records the headline path (--workload k1000 or k100)")
+    args.with_secondary = args.full and not args.no_secondary
+    args.with_cpu_baseline = args.full and not args.no_cpu_baseline
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -538,7 +551,7 @@ def main():
 
     def run_k100():                                      # configs[1]: K = 100
         obj, keep, sched = zero_shot_secondary(SECONDARY)
-        if not args.no_cpu_baseline:
+        if args.with_cpu_baseline:
             obj["cpu_baseline"] = cpu_baseline(SECONDARY, sched, budget_s=60)
         del keep
         torch.cuda.empty_cache()
@@ -562,7 +575,7 @@ def main():
                                            "fp32_tflops_of_the_two_contractions": skm_flop / (e3 / 2) / 1e12,
                                            "note": "sums rebuilt in torch's association order (no MFMA): L2-resident re-reads of the "
                                                    "task's feature block, not HBM, bound this step"}}
-        if not args.no_cpu_baseline:
+        if args.with_cpu_baseline:
             obj["cpu_baseline"] = cpu_baseline(K397_HARD, sched, budget_s=60)
         del ev2, ev3, table2, labels2, idx2
         torch.cuda.empty_cache()
@@ -601,7 +614,7 @@ def main():
                "support_rows_per_task": K4 * w["shots"],
                "note": "few-shot has no dead rows: all K rows of every task iterate in every outer iteration "
                        "(roofline.element_updates_executed_per_step counts them)"}
-        if not args.no_cpu_baseline:
+        if args.with_cpu_baseline:
             obj["cpu_baseline"] = cpu_baseline(w, sched, budget_s=90)
         del ev4, vis_s, vis_q
         torch.cuda.empty_cache()
@@ -663,12 +676,12 @@ def main():
     del ev, table, labels, idx
     torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_secondary and args.workload == "k1000":
+    if world == 1 and args.with_secondary and args.workload == "k1000":
         sec = {name: fn() for name, fn in runners.items()}
         line["secondary"] = sec
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.with_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(head, mm_iters[0].tolist(), budget_s=120)
         print(short_line(line, write_record(line)), flush=True)
     if dist_on:
