@@ -30,6 +30,8 @@ extern "C" {
  * 4: tclip_check_task_indices, tclip_profile_last_split_sorts, tclip_debug_set_split_keep_placement added
  * 5: TCLIP_ERR_INDEX: tclip_check_task_indices reports an out-of-range VALUE with its own code (bad arguments stay TCLIP_ERR_ARG);
  *    tclip_debug_set_dead_head added
+ *    later, without a new number (additions only; a client that needs them looks the symbols up):
+ *    tclip_visual_workspace_bytes, tclip_kmeans_visual_run, tclip_cluster_prototypes_visual, tclip_visual_init
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -276,6 +278,48 @@ int tclip_argmax_rows(const float* x, int64_t n_rows, int32_t n_class, int32_t* 
  * ValueError on features outside the simplex, em_dirichlet.py:204-208). */
 int tclip_probability_features(const float* visual, const float* text, int64_t n_rows, int32_t dim, int32_t n_class,
                                float temperature, float* out, void* stream);
+
+/* Zero-shot k-means on VISUAL features (the reference's use_softmax_feature == False: raw CLIP image embeddings, e.g.
+ * <split>_visual_<backbone>.plk), reference src/methods/zero_shot/soft_kmeans.py:126-220, hard_kmeans.py:137-204,
+ * em_gaussian.py:117-229.  The clustering runs in the D-dimensional embedding space, dim = D independent of K = p->n_class:
+ * centroids are [T, K, D], the squared distances sum over D in torch's last-dim order (any D in 1..1024) and the centroid
+ * statistics over the queries in torch's outer-sum order of K*D columns, so that a run from the reference's own u0 gives its
+ * bits.  The loop starts from a given responsibility tensor u0 instead of building it from text prompts: the reference's
+ * initialisation u0[t] = softmax_k(T * (x_q[t]/||x_q[t]||) . text_k) is a GEMM (tclip_visual_init).
+ *   method TCLIP_VISUAL_SOFT_KMEANS: w_init, then iters x (w_update keeping empty clusters, u = softmax_k(T * -1/2 ||w_k - z||^2))
+ *   method TCLIP_VISUAL_HARD_KMEANS: iters x (w = member means with 0 for empty clusters, u = one_hot(argmin_k softmax_k
+ *          ||w_k - z||^2)); criterions as tclip_hard_kmeans_run (the reference logs each value twice)
+ *   method TCLIP_VISUAL_EM_GAUSSIAN: SOFT_KMEANS with the term lambd v_k / Q in the softmax, v = log(mean_q u + eps) + 1
+ *          (p->lambd: int(K/5) * n_query)
+ * Uses n_batches, tasks_per_batch, n_query, n_class, iters (n_support must be 0; the other fields are ignored).
+ *   x_q device [T,Q,D] f32 raw embeddings (not normalised, as the reference's loop reads them);  u0 device [T,Q,K] f32;
+ *   u device [T,Q,K] out (one-hot for HARD_KMEANS);  w device [T,K,D] out;  preds device [T,Q] i32 out (first maximum of u;
+ *   HARD_KMEANS: the first minimum of its softmax);  v device [T,K] out (EM_GAUSSIAN only, NULL otherwise);
+ *   criterions device [n_batches, iters] out (HARD_KMEANS only, NULL otherwise).  SOFT_KMEANS and EM_GAUSSIAN log 0.
+ *   workspace: tclip_visual_workspace_bytes(p, dim) bytes, 256-byte aligned (0 on bad input). */
+#define TCLIP_VISUAL_SOFT_KMEANS 0
+#define TCLIP_VISUAL_HARD_KMEANS 1
+#define TCLIP_VISUAL_EM_GAUSSIAN 2
+size_t tclip_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_kmeans_visual_run(const tclip_problem* p, int32_t dim, int32_t method, const float* x_q, const float* u0,
+                            float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* Accuracy tail of the visual k-means methods, device half: tclip_cluster_prototypes for D-dim features
+ * (soft_kmeans.py:36-44): the clusters present in `preds` in first-appearance order and the mean raw embedding of each.
+ *   x_q device [T,Q,dim] f32, preds device [T,Q] i32
+ *   n_clusters device [T] i32 out; cluster_ids device [T, Cmax] i32 out (-1 padded); prototypes device [T, Cmax, dim] f32 out
+ *   (rows beyond a task's cluster count are not written), Cmax = min(Q, K).  Needs no workspace.
+ * The reference then scores softmax_k(T * (p/||p||) . text_k) of each prototype (tclip_probability_features) and matches
+ * those rows to classes (tclip_match_clusters_host_strided). */
+int tclip_cluster_prototypes_visual(int32_t n_task, int32_t n_query, int32_t n_class, int32_t dim, const float* x_q,
+                                    const int32_t* preds, int32_t* n_clusters, int32_t* cluster_ids, float* prototypes, void* stream);
+
+/* The visual k-means initialisation (soft_kmeans.py:185-197, also CLIP's u, inductive_clip.py:115-124):
+ * out[n,:] = softmax_k(T * ((visual[n]/||visual[n]||) . text[k])) - the scale AFTER the dot product, where
+ * tclip_probability_features scales before it.  Same arguments and limits as tclip_probability_features. */
+int tclip_visual_init(const float* visual, const float* text, int64_t n_rows, int32_t dim, int32_t n_class,
+                      float temperature, float* out, void* stream);
 
 /* Optional instrumentation used by bench.py (thread-local, off by default).  While enabled,
  * every launch of the live-row majorize-minimize kernel (k_mm_live, the dominant kernel) issued by

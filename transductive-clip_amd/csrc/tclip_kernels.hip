@@ -2565,6 +2565,9 @@ __global__ void k_gather_rows(const float* __restrict__ table, int64_t n_rows, i
 //   z = softmax_k( (T * f/||f||) . text_k ),  text_k unit-norm class text embeddings.
 // One block per image; the scaled embedding is staged in LDS, each thread owns classes
 // k = tid, tid+256, ... and sweeps the text matrix (K x D, L2-resident) with 16-byte loads.
+// kScaleAfter: the visual k-means initialisation (soft_kmeans.py:185-197) scales the dot product instead,
+//   z = softmax_k( T * ((f/||f||) . text_k) )  (tclip_visual_init).
+template <bool kScaleAfter = false>
 __global__ __launch_bounds__(256) void k_probability_features(const float* __restrict__ f, const float* __restrict__ text,
                                                               int D, int K, float temperature, float* __restrict__ z) {
     extern __shared__ float sh[];                 // D floats: scaled embedding; then K floats: logits
@@ -2579,7 +2582,7 @@ __global__ __launch_bounds__(256) void k_probability_features(const float* __res
     if (lane == 0) red[wave] = ss;
     __syncthreads();
     const float nrm = __builtin_sqrtf(red[0] + red[1] + red[2] + red[3]);
-    for (int d = tid; d < D; d += blockDim.x) emb[d] = temperature * (fr[d] / nrm);
+    for (int d = tid; d < D; d += blockDim.x) emb[d] = kScaleAfter ? fr[d] / nrm : temperature * (fr[d] / nrm);
     __syncthreads();
     float mx = -__builtin_inff();
     for (int k = tid; k < K; k += blockDim.x) {
@@ -2596,6 +2599,7 @@ __global__ __launch_bounds__(256) void k_probability_features(const float* __res
             }
         }
         for (; d < D; d++) acc = __builtin_fmaf(emb[d], tr[d], acc);
+        if (kScaleAfter) acc = temperature * acc;
         logit[k] = acc;
         mx = acc > mx ? acc : mx;
     }
@@ -4218,7 +4222,7 @@ int tclip_probability_features(const float* visual, const float* text, int64_t n
     if (n_rows == 0) return TCLIP_OK;
     const size_t lds = ((size_t)dim + (size_t)n_class) * sizeof(float);
     if (lds > 60000 || n_rows > 0x7fffffff) return fail(TCLIP_ERR_ARG, "dim + n_class must be <= 15000");
-    hipLaunchKernelGGL(k_probability_features, dim3((unsigned)n_rows), dim3(256), lds, (hipStream_t)stream, visual, text,
+    hipLaunchKernelGGL(k_probability_features<false>, dim3((unsigned)n_rows), dim3(256), lds, (hipStream_t)stream, visual, text,
                        dim, n_class, temperature, out);
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
@@ -4423,3 +4427,4 @@ int tclip_gather_rows(const float* table, int64_t n_rows, int32_t K, const int64
 
 #include "tclip_tim.inc"
 #include "tclip_lshot.inc"
+#include "tclip_visual.inc"

@@ -1,0 +1,409 @@
+// Zero-shot SOFT_KMEANS, HARD_KMEANS and EM_GAUSSIAN on VISUAL features (the reference's use_softmax_feature == False;
+// src/methods/zero_shot/{soft_kmeans,hard_kmeans,em_gaussian}.py): included at the end of tclip_kernels.hip, uses its helpers
+// (fail, check_problem, align_up, ew_grid, k_copy, k_fill, k_cluster_sizes, k_softmax, k_hard_assign, k_criterion_mean,
+// dsum_outer, outer_column_is_cascade).
+//
+// The loop is the one of the probability-feature path, but the clustering runs in the D-dimensional embedding space, D
+// independent of the class count K: centroids w are [T, K, D], queries z are the raw embeddings [T, Q, D].  The two kernels
+// whose work grows with D are new here; the softmax, the first-minimum one-hot, the criterion and the v term only see
+// [T, Q, K] / [T, K] tensors and are the library's own.
+//   * k_vis_dist: logit[t,q,k] = temperature * (pre * sum_d (w[t,k,d] - z[t,q,d])^2) in torch's last-dim order for every D
+//     in 1..1024, including the cascade dumps after 16 and 32 eight-float steps per accumulator (D >= 512, D = 1024).
+//   * k_vis_mstats: the centroid statistics sum_q u[t,q,k] z[t,q,d] in the order of torch's
+//     (z.unsqueeze(2) * u.unsqueeze(3)).sum(1): an outer sum over K*D contiguous columns (k_mstats for D = K).
+//   * k_vis_prototypes: the accuracy tail's cluster prototypes (one-hot statistics of the predictions) of D-dim rows.
+
+namespace tclip {
+
+// ---- squared distances ------------------------------------------------------------------------------------------------
+// One lane per class as k_kmeans_logits_tile: a block stages up to 64 centroids in LDS (odd row stride), each wavefront takes
+// one query at a time (wave-uniform: its values arrive through the scalar cache), lane k keeps torch's 32 partial sums
+// (accumulator r = 0..3, vector lane j = 0..7: element d = 32 m + 8 r + j belongs to slot 8 r + j at step m) plus the
+// cascade's second level in registers.  Rows of up to 512 elements are staged once; longer rows (at most 1024) in two
+// chunks of 512 elements, which is where torch's 16-step cascade block ends: the chunks are restaged for every group of
+// n_waves queries, so that each wavefront carries one query's 64 accumulators across the chunk boundary and no more.
+// Rows of fewer than 8 elements take torch's 4-way scalar row sum instead (cascade_sum: no vector is complete).
+constexpr int kVisTile = 64, kVisChunk = 512, kVisThreads = 1024;
+constexpr int kVisLds = kVisTile * (kVisChunk + 1) * (int)sizeof(float);
+
+__global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restrict__ w, const float* __restrict__ z,
+                                                          const uint8_t* __restrict__ need, int Q, int K, int D, float pre,
+                                                          float temperature, float* __restrict__ logit0) {
+    extern __shared__ float wt[];                                   // [kVisTile][stride]
+    const int t = blockIdx.y, k0 = blockIdx.x * kVisTile;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = blockDim.x >> 6;
+    const int k = k0 + lane;
+    const bool ok = k < K && need[(size_t)t * K + k];
+    if (!__syncthreads_or(ok)) return;                              // no class of the tile moved
+    const int rows = K - k0 < kVisTile ? K - k0 : kVisTile;
+    const int n_chunks = D > kVisChunk ? 2 : 1;
+    const int stride = (D < kVisChunk ? D : kVisChunk) | 1;
+    const float* wsrc = w + ((size_t)t * K + k0) * D;
+    auto stage = [&](int c0, int clen) {                            // rows x clen words, eight loads in flight per thread
+        const int n = rows * clen, step = blockDim.x;
+        for (int i0 = threadIdx.x; i0 < n; i0 += 8 * step) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int i = i0 + j * step;
+                v[j] = i < n ? wsrc[(size_t)(i / clen) * D + c0 + i % clen] : 0.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int i = i0 + j * step;
+                if (i < n) wt[(i / clen) * stride + i % clen] = v[j];
+            }
+        }
+    };
+    const float* wl = wt + (lane < rows ? lane : rows - 1) * stride;    // lanes beyond the last class recompute it; nothing is stored
+    const int vec_size = D >> 3, size_ilp = vec_size >> 2, nleft = vec_size - 4 * size_ilp, ntail = D - 8 * vec_size;
+    if (n_chunks == 1) {
+        stage(0, D);
+        __syncthreads();
+    }
+    for (int qb = 0; qb < Q; qb += n_waves) {                       // the same trip count in every wavefront (block barriers inside)
+        const int q = qb + wave;
+        const float* zq = z + ((size_t)t * Q + (q < Q ? q : Q - 1)) * D;     // wave-uniform: scalar loads
+        float a0[32], a1[32];
+#pragma unroll
+        for (int sl = 0; sl < 32; sl++) a0[sl] = a1[sl] = 0.0f;
+        for (int c = 0; c < n_chunks; c++) {
+            const int c0 = c * kVisChunk;
+            if (n_chunks > 1) {
+                __syncthreads();                                    // every wavefront is done with the previous chunk
+                stage(c0, c == 0 ? kVisChunk : D - kVisChunk);
+                __syncthreads();
+            }
+            const float* wc = wl - c0;                              // element d of the row at wc[d]
+            const int m_end = size_ilp < (c + 1) * 16 ? size_ilp : (c + 1) * 16;
+            for (int m = c * 16; m < m_end; m++) {
+                float zc[32];
+#pragma unroll
+                for (int sl = 0; sl < 32; sl++) zc[sl] = zq[32 * m + sl];
+#pragma unroll
+                for (int sl = 0; sl < 32; sl++) {
+                    const float df = wc[32 * m + sl] - zc[sl];
+                    a0[sl] += df * df;
+                }
+                if ((m & 15) == 15) {                               // end of a 16-step cascade block: level 0 into level 1
+#pragma unroll
+                    for (int sl = 0; sl < 32; sl++) { a1[sl] += a0[sl]; a0[sl] = 0.0f; }
+                }
+            }
+        }
+        if (q >= Q) continue;                                       // wave-uniform; after the last barrier of this query group
+        const float* wc = wl - (n_chunks - 1) * kVisChunk;          // the leftovers and the tail lie in the last chunk
+        float fin = 0.0f;
+        if (vec_size == 0) {                                        // D < 8: row_sum of 4 interleaved scalar partials
+            const int ilp = D >> 2;
+            float p[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float x = 0.0f;
+                if (r < 4 * ilp) { const float df = wc[r] - zq[r]; x += df * df; }
+                p[r] = x;
+            }
+            for (int i = 4 * ilp; i < D; i++) { const float df = wc[i] - zq[i]; p[0] += df * df; }
+            fin = p[0];
+            fin += p[1];
+            fin += p[2];
+            fin += p[3];
+        } else {
+#pragma unroll
+            for (int sl = 0; sl < 32; sl++) a0[sl] += a1[sl];       // multi_row_sum's finish (levels 2 and 3 hold +0)
+            int d = 32 * size_ilp;
+            for (int i = 0; i < nleft; i++, d += 8) {               // whole vectors beyond the 4-way part join accumulator 0
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const float df = wc[d + j] - zq[d + j];
+                    a0[j] += df * df;
+                }
+            }
+            for (int i = 0; i < ntail; i++) {                       // the D mod 8 tail first
+                const float df = wc[d + i] - zq[d + i];
+                fin += df * df;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                float p0 = a0[j];
+                p0 += a0[8 + j];
+                p0 += a0[16 + j];
+                p0 += a0[24 + j];
+                fin += p0;
+            }
+        }
+        if (ok) logit0[((size_t)t * Q + q) * K + k] = temperature * (pre * fin);
+    }
+}
+
+static bool vis_dist_lds_raised() {
+    struct Seen { int device; bool ok; };
+    static std::mutex mu;
+    static std::vector<Seen> seen;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    std::lock_guard<std::mutex> lock(mu);
+    for (auto& e : seen)
+        if (e.device == dev) return e.ok;
+    const bool ok = hipFuncSetAttribute((const void*)k_vis_dist, hipFuncAttributeMaxDynamicSharedMemorySize, kVisLds) == hipSuccess;
+    seen.push_back(Seen{dev, ok});
+    return ok;
+}
+
+static int launch_vis_dist(int T, hipStream_t st, const float* w, const float* z, const uint8_t* need, int Q, int K, int D,
+                           float pre, float temperature, float* logit0) {
+    const int stride = (D < kVisChunk ? D : kVisChunk) | 1;
+    const size_t lds = (size_t)kVisTile * stride * sizeof(float);
+    if (lds > 65536 && !vis_dist_lds_raised()) return fail(TCLIP_ERR_HIP, "k_vis_dist: cannot raise the LDS limit to %s bytes", "131328");
+    hipLaunchKernelGGL(k_vis_dist, dim3((K + kVisTile - 1) / kVisTile, T), dim3(kVisThreads), lds, st, w, z, need, Q, K, D, pre,
+                       temperature, logit0);
+    return TCLIP_OK;
+}
+
+// ---- centroid statistics ---------------------------------------------------------------------------------------------
+// y[t,k,d] = sum_q u[t,q,k] z[t,q,d] / max(cs[t,k], eps) with the sum in torch's outer-sum order over the K*D contiguous
+// columns of a task (dsum_outer).  mode 0: only rows `live` marks are written (w_init passes all-ones, w_update of SOFT_KMEANS /
+// EM_GAUSSIAN keeps the centroid of an empty cluster); mode 1: HARD_KMEANS, rows that are not live get the quotient times 0
+// (num / den * nonzero_clusters, hard_kmeans.py:148-150), whose sign torch keeps.
+// The rows kernel: one thread per column d, kVisRows classes per thread (u wave-uniform, each z value read once per
+// kVisRows classes), for the classes whose columns all take the cascade order; k_vis_mstats_one the last few.
+constexpr int kVisRows = 16;
+
+__device__ __forceinline__ void vis_mstats_put(float* y, size_t idx, float s, float c, bool alive, int mode) {
+    const float r = s / (c < kEpsF ? kEpsF : c);
+    if (alive) y[idx] = r;
+    else if (mode == 1) y[idx] = r * 0.0f;
+}
+
+__global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, const float* __restrict__ z,
+                                                   const float* __restrict__ cs, const uint8_t* __restrict__ live, int Q, int K,
+                                                   int D, int mode, float* __restrict__ y) {
+    const int t = blockIdx.z, k0 = blockIdx.y * kVisRows;
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= D) return;
+    if (mode == 0) {   // nothing is stored for rows that are not live: skip the group when none of its rows is (block-uniform)
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < kVisRows; j++) any = any || (k0 + j < K && live[(size_t)t * K + k0 + j]);
+        if (!any) return;
+    }
+    const float* ut = u + (size_t)t * Q * K + k0;
+    const float* zt = z + (size_t)t * Q * D + d;
+    const int nj = K - k0 < kVisRows ? K - k0 : kVisRows;
+    const int cl = dev_ceil_log2(Q) / 4;
+    const int level_power = cl > 4 ? cl : 4;
+    const int step = 1 << level_power, mask = step - 1;
+    float a0[kVisRows], a1[kVisRows], a2[kVisRows], a3[kVisRows];
+#pragma unroll
+    for (int j = 0; j < kVisRows; j++) a0[j] = a1[j] = a2[j] = a3[j] = 0.0f;
+    int i = 0;
+    for (; i + step <= Q;) {
+        for (int jj = 0; jj < step; ++jj, ++i) {
+            const float fv = zt[(size_t)i * D];
+#pragma unroll
+            for (int j = 0; j < kVisRows; j++) a0[j] += (j < nj ? ut[(size_t)i * K + j] : 0.0f) * fv;
+        }
+        const bool l2 = (i & (mask << level_power)) == 0, l3 = l2 && (i & (mask << (2 * level_power))) == 0;
+#pragma unroll
+        for (int j = 0; j < kVisRows; j++) {
+            a1[j] += a0[j]; a0[j] = 0.0f;
+            if (l2) { a2[j] += a1[j]; a1[j] = 0.0f; }
+            if (l3) { a3[j] += a2[j]; a2[j] = 0.0f; }
+        }
+    }
+    for (; i < Q; ++i) {
+        const float fv = zt[(size_t)i * D];
+#pragma unroll
+        for (int j = 0; j < kVisRows; j++) a0[j] += (j < nj ? ut[(size_t)i * K + j] : 0.0f) * fv;
+    }
+#pragma unroll
+    for (int j = 0; j < kVisRows; j++) {
+        if (j >= nj) continue;
+        const size_t row = (size_t)t * K + k0 + j;
+        float s = a0[j];
+        s += a1[j];
+        s += a2[j];
+        s += a3[j];
+        vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode);
+    }
+}
+
+// One output per thread, any column (the rows of the 4-way row-sum columns: at most the last 31 of K*D).
+__global__ void k_vis_mstats_one(const float* __restrict__ u, const float* __restrict__ z, const float* __restrict__ cs,
+                                 const uint8_t* __restrict__ live, int Q, int K, int D, int k_first, int mode, float* __restrict__ y) {
+    const int t = blockIdx.z, k = blockIdx.y + k_first;
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= D) return;
+    const size_t row = (size_t)t * K + k;
+    if (mode == 0 && !live[row]) return;
+    const float* ut = u + (size_t)t * Q * K + k;
+    const float* zt = z + (size_t)t * Q * D + d;
+    const float s = dsum_outer(Q, (long)k * D + d, (long)K * D, [&](int q) { return ut[(size_t)q * K] * zt[(size_t)q * D]; });
+    vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode);
+}
+
+static void launch_vis_mstats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, int T, int Q,
+                              int K, int D, int mode, float* y) {
+    const long ncols = (long)K * D;
+    const int full_rows = ncols >= 8 ? (int)(((ncols / 32) * 32) / D) : 0;     // rows 0 .. full_rows-1 are all-cascade
+    const int groups = full_rows / kVisRows;
+    if (groups > 0)
+        hipLaunchKernelGGL(k_vis_mstats, dim3((D + 63) / 64, groups, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, mode, y);
+    const int k_first = groups * kVisRows;
+    if (k_first < K)
+        hipLaunchKernelGGL(k_vis_mstats_one, dim3((D + 63) / 64, K - k_first, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, k_first,
+                           mode, y);
+}
+
+// ---- accuracy-tail prototypes -----------------------------------------------------------------------------------------
+// Per task the clusters present in preds in first-appearance order and their mean raw feature, as compute_acc_clustering
+// builds it (soft_kmeans.py:36-44): (one_hot(preds).unsqueeze(-1) * z.unsqueeze(2)).sum(1) / clamp(sizes, eps), the sum in
+// the outer-sum order of K*D columns (the one-hot's zero products included: they decide nothing but are added all the same).
+// One block per task; only the present clusters' rows are computed.
+__global__ __launch_bounds__(256) void k_vis_prototypes(const int32_t* __restrict__ preds, const float* __restrict__ z, int Q, int K,
+                                                        int D, int Cmax, int32_t* __restrict__ n_clusters,
+                                                        int32_t* __restrict__ cluster_ids, float* __restrict__ protos) {
+    const int t = blockIdx.x;
+    __shared__ int ids[1024];
+    __shared__ int cnt;
+    __shared__ float sizes[1024];
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int q = 0; q < Q; q++) {
+            int p = preds[(size_t)t * Q + q];
+            p = p < 0 ? 0 : (p >= K ? K - 1 : p);          // never index outside the task (the host side rejects such labels)
+            bool seen = false;
+            for (int i = 0; i < c; i++) seen |= ids[i] == p;
+            if (!seen) ids[c++] = p;
+        }
+        cnt = c;
+        n_clusters[t] = c;
+        for (int i = 0; i < Cmax; i++) cluster_ids[(size_t)t * Cmax + i] = i < c ? ids[i] : -1;
+    }
+    __syncthreads();
+    const int c = cnt;
+    const int32_t* pt = preds + (size_t)t * Q;
+    for (int ci = threadIdx.x; ci < c; ci += blockDim.x) {
+        const int k = ids[ci];
+        sizes[ci] = dsum_outer(Q, k, K, [&](int q) { return pt[q] == k ? 1.0f : 0.0f; });
+    }
+    __syncthreads();
+    const float* zt = z + (size_t)t * Q * D;
+    for (int i = threadIdx.x; i < c * D; i += blockDim.x) {
+        const int ci = i / D, d = i % D, k = ids[ci];
+        const float s = dsum_outer(Q, (long)k * D + d, (long)K * D, [&](int q) { return (pt[q] == k ? 1.0f : 0.0f) * zt[(size_t)q * D + d]; });
+        const float sz = sizes[ci];
+        protos[((size_t)t * Cmax + ci) * D + d] = s / (sz < kEpsF ? kEpsF : sz);
+    }
+}
+
+static size_t visual_ws_parts(const tclip_problem& p, size_t* o_cs, size_t* o_live, size_t* o_ones, size_t* o_logit,
+                              size_t* o_change) {
+    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
+    *o_cs = take(T * K * 4);
+    *o_live = take(T * K);
+    *o_ones = take(T * K);
+    *o_logit = take(T * Q * K * 4);
+    *o_change = take(T * 4);
+    return o;
+}
+
+}  // namespace tclip
+
+extern "C" {
+
+size_t tclip_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (dim < 1 || dim > 1024) { fail(TCLIP_ERR_ARG, "dim must be in 1..1024"); return 0; }
+    size_t a, b, c, d, e;
+    return visual_ws_parts(*p, &a, &b, &c, &d, &e);
+}
+
+int tclip_kmeans_visual_run(const tclip_problem* pp, int32_t dim, int32_t method, const float* x_q, const float* u0,
+                            float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
+    if (method != TCLIP_VISUAL_SOFT_KMEANS && method != TCLIP_VISUAL_HARD_KMEANS && method != TCLIP_VISUAL_EM_GAUSSIAN)
+        return fail(TCLIP_ERR_ARG, "unknown method");
+    const bool hard = method == TCLIP_VISUAL_HARD_KMEANS, emg = method == TCLIP_VISUAL_EM_GAUSSIAN;
+    if (!x_q || !u0 || !u || !w || !preds || !workspace || (hard && !criterions) || (emg && !v))
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "the visual k-means methods are zero-shot: n_support must be 0");
+    size_t o_cs, o_live, o_ones, o_logit, o_change;
+    const size_t total = visual_ws_parts(p, &o_cs, &o_live, &o_ones, &o_logit, &o_change);
+    if (workspace_bytes < total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_visual_workspace_bytes()");
+    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const int Q = p.n_query, K = p.n_class, D = dim, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
+    const size_t TQK = (size_t)T * Q * K;
+    float* cs = (float*)(ws + o_cs);
+    uint8_t* live = (uint8_t*)(ws + o_live);
+    uint8_t* ones = (uint8_t*)(ws + o_ones);
+    float* logit0 = (float*)(ws + o_logit);
+    float* change = (float*)(ws + o_change);
+    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, u0, u, TQK);           // u = u0 (the text-prompt init)
+    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
+    if (emg) hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
+    if (!hard) {
+        // w_init: every centroid = u^T z / clamp(sum u)                          (soft_kmeans.py:126-136, em_gaussian.py:145-155)
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
+                           (float*)nullptr, (int32_t*)nullptr);
+        launch_vis_mstats(st, u, x_q, cs, ones, T, Q, K, D, 0, w);
+    }
+    for (int it = 0; it < p.iters; it++) {
+        // w_update (EM_GAUSSIAN: the same pass over u yields v of the previous iteration's v_update)
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
+                           (emg && it > 0) ? v : (float*)nullptr, (int32_t*)nullptr);
+        launch_vis_mstats(st, u, x_q, cs, live, T, Q, K, D, hard ? 1 : 0, w);
+        if (hard) {
+            // u_update + hard assignment: softmax of the squared distances, first minimum; criterion, u <- one-hot
+            if (int rc = launch_vis_dist(T, st, w, x_q, ones, Q, K, D, 1.0f, 1.0f, logit0)) return rc;
+            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
+                               (const float*)nullptr, T * Q, Q, K, 0.0f, 0, 1, logit0, preds);
+            hipLaunchKernelGGL(k_hard_assign, dim3(T), dim3(256), 0, st, (const int32_t*)preds, Q, K, u, change);
+            hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)change, N, 0, criterions + it, p.iters);
+        } else {
+            // distances only for centroids that moved (all of them in the first iteration), E-step softmax
+            if (int rc = launch_vis_dist(T, st, w, x_q, it == 0 ? ones : live, Q, K, D, -0.5f, temperature, logit0)) return rc;
+            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
+                               (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
+        }
+    }
+    if (emg)      // the last v_update
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
+                           (int32_t*)nullptr);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+int tclip_cluster_prototypes_visual(int32_t T, int32_t Q, int32_t K, int32_t dim, const float* x_q, const int32_t* preds,
+                                    int32_t* n_clusters, int32_t* cluster_ids, float* prototypes, void* stream) {
+    if (T < 1 || Q < 1 || K < 2 || K > 1024 || dim < 1 || !x_q || !preds || !n_clusters || !cluster_ids || !prototypes)
+        return fail(TCLIP_ERR_ARG, "bad argument to tclip_cluster_prototypes_visual");
+    if ((size_t)K * dim > 0x7fffffffu) return fail(TCLIP_ERR_ARG, "n_class * dim must fit in int32");
+    const int Cmax = Q < K ? Q : K;
+    hipLaunchKernelGGL(k_vis_prototypes, dim3(T), dim3(256), 0, (hipStream_t)stream, preds, x_q, Q, K, dim, Cmax, n_clusters,
+                       cluster_ids, prototypes);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+int tclip_visual_init(const float* visual, const float* text, int64_t n_rows, int32_t dim, int32_t n_class, float temperature,
+                      float* out, void* stream) {
+    if (!visual || !text || !out || n_rows < 0 || dim < 1 || n_class < 1) return fail(TCLIP_ERR_ARG, "bad argument to tclip_visual_init");
+    if (n_rows == 0) return TCLIP_OK;
+    const size_t lds = ((size_t)dim + (size_t)n_class) * sizeof(float);
+    if (lds > 60000 || n_rows > 0x7fffffff) return fail(TCLIP_ERR_ARG, "dim + n_class must be <= 15000");
+    hipLaunchKernelGGL(k_probability_features<true>, dim3((unsigned)n_rows), dim3(256), lds, (hipStream_t)stream, visual, text, dim,
+                       n_class, temperature, out);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+}  // extern "C"

@@ -67,6 +67,13 @@ class EMDirichletBase(object):
         self.matched_preds = new_preds
         self.test_acc.append(acc.view(-1, 1))
 
+    def compute_acc_clustering_visual(self, query, y_q, text):
+        """the accuracy tail on visual features (soft_kmeans.py:36-66): D-dim prototypes, scored against the text features"""
+        acc, new_preds = engine.clustering_accuracy_visual(query, self.preds, y_q, text, self.args.T,
+                                                           graph_matching=bool(self.args.graph_matching))
+        self.matched_preds = new_preds
+        self.test_acc.append(acc.view(-1, 1))
+
     # -- the loop ---------------------------------------------------------------------------
     def _run_engine(self, query, support=None, y_s=None, n_batches=1, tables=None):
         """`tables` = dict(table_q, q_idx[, table_s, s_idx, cols]): the task rows are read from the feature tables through the

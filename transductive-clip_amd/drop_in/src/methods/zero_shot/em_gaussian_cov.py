@@ -25,7 +25,7 @@ class EM_GAUSSIAN_COV(BASE):
 
     def run_method(self, query, y_q, n_batches=1):
         if not self.args.use_softmax_feature:
-            raise NotImplementedError("EM_GAUSSIAN_COV on visual features needs CLIP text prompts (out of scope)")
+            raise NotImplementedError("EM_GAUSSIAN_COV on visual features is not supported: use probability features (use_softmax_feature: True)")
         dev = torch.device(self.device)
         if dev.type != "cuda":
             raise RuntimeError("EM_GAUSSIAN_COV on MI355X needs device='cuda': there is no CPU fallback in this package")

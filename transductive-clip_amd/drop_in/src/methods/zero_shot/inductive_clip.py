@@ -1,13 +1,20 @@
 """Inductive zero-shot CLIP on probability features, drop-in for the reference's
 src/methods/zero_shot/inductive_clip.py (the baseline every transductive method is compared with):
 no adaptation, u = the query features, prediction = their arg-max, plain accuracy (no cluster
-matching).  The arg-max runs in libtclip.so (tclip_argmax_rows).  Visual features need CLIP text
-prompts (reference :115-124) and are out of scope."""
+matching).  The arg-max runs in libtclip.so (tclip_argmax_rows).  On visual features (use_softmax_feature: False)
+u = softmax_k(T * (x/||x||) . text_k) (reference :115-124; tclip_visual_init) with the text features of
+src/methods/_visual.py."""
 import numpy as np
 import torch
 
 from src.utils import Logger
 from tclip_amd import engine
+
+
+def _text_features(model, args, device):
+    # imported here: a Level-1 overlay that copies only the modules of the probability-feature path keeps working
+    from src.methods._visual import text_features
+    return text_features(model, args, device)
 
 
 class BASE(object):
@@ -56,11 +63,10 @@ class BASE(object):
 
 class CLIP(BASE):
     def run_method(self, query, y_q, n_batches=1):
-        if not self.args.use_softmax_feature:
-            raise NotImplementedError("CLIP on visual features needs CLIP text prompts (out of scope)")
         if torch.device(self.device).type != "cuda":
             raise RuntimeError("CLIP on MI355X needs device='cuda': there is no CPU fallback in this package")
+        text = None if self.args.use_softmax_feature else _text_features(self.model, self.args, torch.device(self.device))
         self.logger.info(" ==> Executing CLIP")
-        self.u = query
+        self.u = query if text is None else engine.visual_init(query, text, self.args.T)
         self.record_convergence(new_time=0, criterions=torch.zeros(()))      # ||u - copy of u|| (:126-128)
         self.compute_acc(y_q)

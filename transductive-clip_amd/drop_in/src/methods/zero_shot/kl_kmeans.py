@@ -24,7 +24,7 @@ class KL_KMEANS(BASE):
 
     def run_method(self, query, y_q, n_batches=1):
         if not self.args.use_softmax_feature:
-            raise NotImplementedError("KL_KMEANS on visual features needs CLIP text prompts (out of scope)")
+            raise NotImplementedError("KL_KMEANS needs probability features: the KL divergence of visual embeddings (not on the simplex) is undefined")
         dev = torch.device(self.device)
         if dev.type != "cuda":
             raise RuntimeError("KL_KMEANS on MI355X needs device='cuda': there is no CPU fallback in this package")

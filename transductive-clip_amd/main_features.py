@@ -67,6 +67,8 @@ def parse_args(argv=None):
     ap.add_argument("--results-root", default=".")
     ap.add_argument("--config-root", default=None, help="directory with main_config.yaml, datasets_config/, methods_config/ "
                                                         "(default: ./config if it exists, else the built-in defaults)")
+    ap.add_argument("--text-features", default=None, help="(K, D) text features of the classes, a .pt or .npy file: what the "
+                                                          "zero-shot methods need on visual features (use_softmax_feature False)")
     ap.add_argument("--opts", default=None, nargs=argparse.REMAINDER)
     ns = ap.parse_args(argv)
     opts = ns.opts or []
@@ -83,6 +85,8 @@ def parse_args(argv=None):
         cfg.update(METHOD_DEFAULTS[cfg.method])
         cfg = merge_cfg_from_list(cfg, opts)           # command line wins, as in main.py:32-33
     cfg.results_root = ns.results_root
+    if ns.text_features is not None:
+        cfg.text_features = ns.text_features
     return ns, cfg
 
 
@@ -108,6 +112,9 @@ def main(argv=None, keep_process_group=False):
         raise SystemExit(f"{query_path} not found: extract the features with the reference first (CLIP is out of scope here)")
     feats_q, labels_q = features.load_features(query_path)
     args.num_classes_test = int(feats_q.shape[1]) if args.use_softmax_feature else int(labels_q.max()) + 1
+    if not args.use_softmax_feature and getattr(args, "text_features", None) is not None:
+        from src.methods._visual import load_text_features
+        args.num_classes_test = int(load_text_features(args.text_features).shape[0])      # one row per class
     args.n_class = args.num_classes_test
     logger = Logger(__name__, None)
     if int(args.shots) > 0:

@@ -37,9 +37,9 @@ class _Call:
     the inputs' device, the entry point launched on the current stream, the workspace kept alive until that
     stream has consumed it.  `args(ws_ptr, ws_bytes, stream)` builds the C argument tuple."""
 
-    def __init__(self, dev, problem, ws_query):
+    def __init__(self, dev, problem, ws_query, *ws_args):
         self.dev, self.p, self.lib = dev, problem, _capi.lib()
-        self.ws_bytes = getattr(self.lib, ws_query)(ctypes.byref(problem))
+        self.ws_bytes = getattr(self.lib, ws_query)(ctypes.byref(problem), *ws_args)
         if self.ws_bytes == 0:
             raise RuntimeError(f"{ws_query} rejected the problem: " + self.lib.tclip_last_error().decode())
 
@@ -339,6 +339,120 @@ def clustering_accuracy(x_q, preds, y_q, graph_matching=True):
                                                int(bool(graph_matching)), used, _ptr(new_preds), _ptr(acc))
     _capi.check(rc, "tclip_match_clusters_host_strided")
     return acc, new_preds
+
+
+VISUAL_METHODS = {"soft_kmeans": 0, "hard_kmeans": 1, "em_gaussian": 2}     # TCLIP_VISUAL_* of include/tclip.h
+
+
+def visual_init(x_q, text, T):
+    """The visual k-means / CLIP initialisation (soft_kmeans.py:185-197): u0[t] = softmax_k(T * (x_q[t]/||x_q[t]|| @ text.T)),
+    the scale after the dot product.  x_q (..., D) f32 cuda raw embeddings, text (K, D) unit-norm text features ->
+    (..., K) f32 cuda, not synchronised (tclip_visual_init)."""
+    _require_cuda(x_q, "x_q")
+    x_q = x_q.contiguous().float()
+    text = text.to(x_q.device).contiguous().float()
+    D = x_q.shape[-1]
+    if text.dim() != 2 or text.shape[1] != D:
+        raise ValueError(f"text features must be (K, {D}) for {D}-dim embeddings, got {tuple(text.shape)}")
+    K = text.shape[0]
+    rows = x_q.numel() // D
+    out = torch.empty(*x_q.shape[:-1], K, device=x_q.device)
+    with torch.cuda.device(x_q.device):
+        rc = _capi.lib().tclip_visual_init(_ptr(x_q), _ptr(text), ctypes.c_int64(rows), ctypes.c_int32(D), ctypes.c_int32(K),
+                                           ctypes.c_float(float(T)), _ptr(out), _stream())
+    _capi.check(rc, "tclip_visual_init")
+    return out
+
+
+def _run_visual(method, x_q, u0, iters, temperature, lambd=0, n_batches=1):
+    x_q = _query(x_q)
+    _require_cuda(u0, "u0")
+    u0 = u0.to(x_q.device).contiguous().float()
+    T, Q, D = x_q.shape
+    if u0.dim() != 3 or u0.shape[0] != T or u0.shape[1] != Q:
+        raise ValueError("u0 must be (T,Q,K) with the T and Q of x_q")
+    K = u0.shape[2]
+    if T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+    p = _capi.Problem(n_batches, T // n_batches, Q, K, 0, iters, 1, int(lambd), 0)
+    c = _Call(x_q.device, p, "tclip_visual_workspace_bytes", ctypes.c_int32(D))
+    hard, emg = method == "hard_kmeans", method == "em_gaussian"
+    u, w, preds = c.empty(T, Q, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
+    v = c.empty(T, K) if emg else None
+    crit = c.empty(n_batches, max(iters, 1))[:, :iters].contiguous() if hard else None
+    c.launch("tclip_kmeans_visual_run", lambda ws, n, st: (ctypes.c_int32(D), ctypes.c_int32(VISUAL_METHODS[method]), _ptr(x_q),
+                                                           _ptr(u0), ctypes.c_float(float(temperature)), _ptr(u), _ptr(v), _ptr(w),
+                                                           _ptr(preds), _ptr(crit), ws, n, st))
+    return u, v, w, preds, crit
+
+
+def run_soft_kmeans_visual(x_q, u0, *, iters, temperature):
+    """SOFT_KMEANS on visual features: x_q (T,Q,D) raw embeddings, u0 (T,Q,K) the initial responsibilities (visual_init) ->
+    (u (T,Q,K), w (T,K,D), preds (T,Q) i32), cuda, not synchronised."""
+    u, _, w, preds, _ = _run_visual("soft_kmeans", x_q, u0, iters, temperature)
+    return u, w, preds
+
+
+def run_hard_kmeans_visual(x_q, u0, *, iters, n_batches=1):
+    """HARD_KMEANS on visual features -> (u one-hot (T,Q,K), w (T,K,D), preds (T,Q) i32, criterions (n_batches, iters)), cuda,
+    not synchronised.  The reference's HARD_KMEANS loop has no temperature."""
+    u, _, w, preds, crit = _run_visual("hard_kmeans", x_q, u0, iters, 1.0, n_batches=n_batches)
+    return u, w, preds, crit
+
+
+def run_em_gaussian_visual(x_q, u0, *, iters, temperature, lambd):
+    """EM_GAUSSIAN on visual features -> (u (T,Q,K), v (T,K), w (T,K,D), preds (T,Q) i32), cuda, not synchronised."""
+    u, v, w, preds, _ = _run_visual("em_gaussian", x_q, u0, iters, temperature, lambd=lambd)
+    return u, v, w, preds
+
+
+def _match(lib, T, Q, K, preds, n_clusters, ids, rows, y_q, graph_matching, cmax, dev):
+    """host half of the accuracy tail: copies the rows of the fullest task to the host and matches clusters to classes"""
+    preds_h, nc_h = preds.cpu(), n_clusters.cpu()
+    used = max(1, min(cmax, int(nc_h.max())))
+    ids_h = torch.empty((T, used), dtype=torch.int32, pin_memory=True)
+    rows_h = torch.empty((T, used, K), dtype=torch.float32, pin_memory=True)
+    with torch.cuda.device(dev):
+        ids_h.copy_(ids[:, :used], non_blocking=True)
+        rows_h.copy_(rows[:, :used], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    y_h = y_q.reshape(T, Q).long().cpu().contiguous()
+    new_preds = torch.empty(T, Q, dtype=torch.int32)
+    acc = torch.empty(T, dtype=torch.float32)
+    rc = lib.tclip_match_clusters_host_strided(T, Q, K, _ptr(preds_h), _ptr(nc_h), _ptr(ids_h), _ptr(rows_h), _ptr(y_h),
+                                               int(bool(graph_matching)), used, _ptr(new_preds), _ptr(acc))
+    _capi.check(rc, "tclip_match_clusters_host_strided")
+    return acc, new_preds
+
+
+def clustering_accuracy_visual(x_q, preds, y_q, text, T, graph_matching=True):
+    """Accuracy tail of the visual k-means methods (soft_kmeans.py:36-66): D-dim prototypes of the predicted clusters
+    (tclip_cluster_prototypes_visual), probs = softmax_k(T * (p/||p||) . text_k) of each (tclip_probability_features: the
+    scale before the dot product, as the reference's tail has it), host matching of clusters to classes on those rows.
+    x_q (T,Q,D) cuda f32, preds (T,Q) cuda i32, y_q (T,Q) int64, text (K,D).  Returns (acc (T,) f32 cpu, new_preds (T,Q) i32 cpu)."""
+    _require_cuda(x_q, "x_q")
+    x_q = x_q.contiguous().float()
+    n_task, Q, D = x_q.shape
+    dev = x_q.device
+    text = text.to(dev).contiguous().float()
+    if text.dim() != 2 or text.shape[1] != D:
+        raise ValueError(f"text features must be (K, {D}) for {D}-dim embeddings, got {tuple(text.shape)}")
+    K = text.shape[0]
+    lib = _capi.lib()
+    cmax = min(Q, K)
+    with torch.cuda.device(dev):
+        preds = preds.to(dev).int().contiguous()
+        n_clusters = torch.empty(n_task, dtype=torch.int32, device=dev)
+        ids = torch.empty(n_task, cmax, dtype=torch.int32, device=dev)
+        protos = torch.ones(n_task, cmax, D, device=dev)      # rows beyond a task's cluster count are scored but never read
+        rc = lib.tclip_cluster_prototypes_visual(n_task, Q, K, D, _ptr(x_q), _ptr(preds), _ptr(n_clusters), _ptr(ids), _ptr(protos),
+                                                 _stream())
+        _capi.check(rc, "tclip_cluster_prototypes_visual")
+        probs = torch.empty(n_task, cmax, K, device=dev)
+        rc = lib.tclip_probability_features(_ptr(protos), _ptr(text), ctypes.c_int64(n_task * cmax), ctypes.c_int32(D),
+                                            ctypes.c_int32(K), ctypes.c_float(float(T)), _ptr(probs), _stream())
+        _capi.check(rc, "tclip_probability_features")
+    return _match(lib, n_task, Q, K, preds, n_clusters, ids, probs, y_q, graph_matching, cmax, dev)
 
 
 def gather_rows(table, idx):
