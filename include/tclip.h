@@ -31,7 +31,8 @@ extern "C" {
  * 5: TCLIP_ERR_INDEX: tclip_check_task_indices reports an out-of-range VALUE with its own code (bad arguments stay TCLIP_ERR_ARG);
  *    tclip_debug_set_dead_head added
  *    later, without a new number (additions only; a client that needs them looks the symbols up):
- *    tclip_visual_workspace_bytes, tclip_kmeans_visual_run, tclip_cluster_prototypes_visual, tclip_visual_init
+ *    tclip_visual_workspace_bytes, tclip_kmeans_visual_run, tclip_cluster_prototypes_visual, tclip_visual_init;
+ *    tclip_paddle_visual_workspace_bytes, tclip_paddle_visual_run, tclip_bdcspn_visual_workspace_bytes, tclip_bdcspn_visual_run
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -320,6 +321,28 @@ int tclip_cluster_prototypes_visual(int32_t n_task, int32_t n_query, int32_t n_c
  * tclip_probability_features scales before it.  Same arguments and limits as tclip_probability_features. */
 int tclip_visual_init(const float* visual, const float* text, int64_t n_rows, int32_t dim, int32_t n_class,
                       float temperature, float* out, void* stream);
+
+/* Few-shot PADDLE and BD-CSPN on VISUAL features (use_softmax_feature == False; reference src/methods/few_shot/paddle.py:94-219,
+ * bdcspn.py:42-200): tclip_paddle_run / tclip_bdcspn_run with feature rows of `dim` elements, dim independent of n_class.
+ * PADDLE needs no text features: the reference's text-prompt u is overwritten by the first u_update before anything reads it
+ * (paddle.py:183-203), and w starts from the support class means.
+ *   x_q device [T, n_query, dim] f32, x_s device [T, n_support, dim] f32, y_s device [T, n_support] int64 in 0..n_class-1 (a
+ *   label outside that range is never used as an index: its row joins no class; callers reject such labels),
+ *   T = n_batches * tasks_per_batch.
+ *   PADDLE: u [T, n_query, n_class], v [T, n_class], w [T, n_class, dim] the centroids, preds [T, n_query] int32 = argmax_k u;
+ *   p->iters iterations, lambd the method's float (paddle.yaml).
+ *   BD-CSPN: prototypes [T, n_class, dim] the rectified prototypes, u [T, n_query, n_class], preds; temp and norm_type
+ *   (0 UN, 1 L2N, 2 CL2N) as tclip_bdcspn_run.
+ *   Limits: dim in 1..1024, n_class in 2..1024, n_support >= 1; anything else is TCLIP_ERR_ARG.
+ *   workspace: tclip_*_visual_workspace_bytes(p, dim) bytes, 256-byte aligned (0 on bad input). */
+size_t tclip_paddle_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_paddle_visual_run(const tclip_problem* p, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s,
+                            float lambd, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t tclip_bdcspn_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_bdcspn_visual_run(const tclip_problem* p, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
+                            int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* Optional instrumentation used by bench.py (thread-local, off by default).  While enabled,
  * every launch of the live-row majorize-minimize kernel (k_mm_live, the dominant kernel) issued by

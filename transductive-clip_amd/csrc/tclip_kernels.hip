@@ -4428,3 +4428,4 @@ int tclip_gather_rows(const float* table, int64_t n_rows, int32_t K, const int64
 #include "tclip_tim.inc"
 #include "tclip_lshot.inc"
 #include "tclip_visual.inc"
+#include "tclip_visual_fs.inc"

@@ -166,11 +166,17 @@ static int launch_vis_dist(int T, hipStream_t st, const float* w, const float* z
 // columns of a task (dsum_outer).  mode 0: only rows `live` marks are written (w_init passes all-ones, w_update of SOFT_KMEANS /
 // EM_GAUSSIAN keeps the centroid of an empty cluster); mode 1: HARD_KMEANS, rows that are not live get the quotient times 0
 // (num / den * nonzero_clusters, hard_kmeans.py:148-150), whose sign torch keeps.
+// The few-shot modes write every row and ignore `live`: mode 2, PADDLE's w_update (few_shot/paddle.py:154-158), adds the support
+// class sums to the query sum and the class counts to cs, one add_ each, then divides; mode 3, BD-CSPN's rectified prototypes
+// (few_shot/bdcspn.py:139-141), is the plain quotient.  Q is then any row count (BD-CSPN: S + n_query augmented rows).
 // The rows kernel: one thread per column d, kVisRows classes per thread (u wave-uniform, each z value read once per
 // kVisRows classes), for the classes whose columns all take the cascade order; k_vis_mstats_one the last few.
 constexpr int kVisRows = 16;
 
-__device__ __forceinline__ void vis_mstats_put(float* y, size_t idx, float s, float c, bool alive, int mode) {
+__device__ __forceinline__ void vis_mstats_put(float* y, size_t idx, float s, float c, bool alive, int mode,
+                                               const float* __restrict__ sup, const float* __restrict__ cnt, size_t row) {
+    if (mode == 2) { y[idx] = (s + sup[idx]) / (c + cnt[row]); return; }
+    if (mode == 3) { y[idx] = s / c; return; }
     const float r = s / (c < kEpsF ? kEpsF : c);
     if (alive) y[idx] = r;
     else if (mode == 1) y[idx] = r * 0.0f;
@@ -178,7 +184,8 @@ __device__ __forceinline__ void vis_mstats_put(float* y, size_t idx, float s, fl
 
 __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, const float* __restrict__ z,
                                                    const float* __restrict__ cs, const uint8_t* __restrict__ live, int Q, int K,
-                                                   int D, int mode, float* __restrict__ y) {
+                                                   int D, int mode, float* __restrict__ y, const float* __restrict__ sup,
+                                                   const float* __restrict__ cnt) {
     const int t = blockIdx.z, k0 = blockIdx.y * kVisRows;
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
@@ -225,13 +232,14 @@ __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, 
         s += a1[j];
         s += a2[j];
         s += a3[j];
-        vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode);
+        vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode, sup, cnt, row);
     }
 }
 
 // One output per thread, any column (the rows of the 4-way row-sum columns: at most the last 31 of K*D).
 __global__ void k_vis_mstats_one(const float* __restrict__ u, const float* __restrict__ z, const float* __restrict__ cs,
-                                 const uint8_t* __restrict__ live, int Q, int K, int D, int k_first, int mode, float* __restrict__ y) {
+                                 const uint8_t* __restrict__ live, int Q, int K, int D, int k_first, int mode, float* __restrict__ y,
+                                 const float* __restrict__ sup, const float* __restrict__ cnt) {
     const int t = blockIdx.z, k = blockIdx.y + k_first;
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
@@ -240,20 +248,21 @@ __global__ void k_vis_mstats_one(const float* __restrict__ u, const float* __res
     const float* ut = u + (size_t)t * Q * K + k;
     const float* zt = z + (size_t)t * Q * D + d;
     const float s = dsum_outer(Q, (long)k * D + d, (long)K * D, [&](int q) { return ut[(size_t)q * K] * zt[(size_t)q * D]; });
-    vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode);
+    vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode, sup, cnt, row);
 }
 
 static void launch_vis_mstats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, int T, int Q,
-                              int K, int D, int mode, float* y) {
+                              int K, int D, int mode, float* y, const float* sup = nullptr, const float* cnt = nullptr) {
     const long ncols = (long)K * D;
     const int full_rows = ncols >= 8 ? (int)(((ncols / 32) * 32) / D) : 0;     // rows 0 .. full_rows-1 are all-cascade
     const int groups = full_rows / kVisRows;
     if (groups > 0)
-        hipLaunchKernelGGL(k_vis_mstats, dim3((D + 63) / 64, groups, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, mode, y);
+        hipLaunchKernelGGL(k_vis_mstats, dim3((D + 63) / 64, groups, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, mode, y, sup,
+                           cnt);
     const int k_first = groups * kVisRows;
     if (k_first < K)
         hipLaunchKernelGGL(k_vis_mstats_one, dim3((D + 63) / 64, K - k_first, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, k_first,
-                           mode, y);
+                           mode, y, sup, cnt);
 }
 
 // ---- accuracy-tail prototypes -----------------------------------------------------------------------------------------

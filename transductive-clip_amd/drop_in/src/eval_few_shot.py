@@ -169,7 +169,10 @@ class Evaluator_few_shot:
         n_batches, N, S = s_idx.shape
         Q = q_idx.shape[2]
         mine = sharding.my_batches(n_batches)
-        K = tab_q.shape[1]
+        # the feature width and the class count: one number on softmax features, the embedding length D and args.n_class on
+        # visual features (use_softmax_feature: False; PADDLE and BDCSPN run there, the labels are not re-indexed)
+        W = tab_q.shape[1]
+        K = W if a.use_softmax_feature else int(a.n_class)
         # The parameter tuned on the validation split, when the test split is evaluated.  The reference builds the
         # method of a batch FIRST and reads the sweep file afterwards (eval_few_shot.py:250-254), and every method
         # copies its parameter in __init__ (paddle.py:26, bdcspn.py:18, tim.py:198, laplacian_shot.py:32): its batch 0
@@ -204,8 +207,8 @@ class Evaluator_few_shot:
                     parts = sharding.concat_parts(parts, sharding.method_parts(a, m, logs, len(ids), N, Q, dev))
                     timestamps += [float(logs['timestamps'])] * len(ids)
                     continue
-            x_s = engine.gather_rows(tab_s, si).view(len(ids) * N, S, K)
-            x_q = engine.gather_rows(tab_q, qi).view(len(ids) * N, Q, K)
+            x_s = engine.gather_rows(tab_s, si).view(len(ids) * N, S, W)
+            x_q = engine.gather_rows(tab_q, qi).view(len(ids) * N, Q, W)
             y_s, y_q = lab_s[si].view(-1, S), lab_q[qi].view(-1, Q)
             # label re-indexing / column permutation of Tasks_Generator_few_shot.get_task, per task
             x_s, x_q, y_s, y_q = relabel_batch(x_s, x_q, y_s, y_q, a.use_softmax_feature)

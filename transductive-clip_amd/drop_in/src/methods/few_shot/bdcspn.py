@@ -1,8 +1,9 @@
-"""Few-shot BD-CSPN (prototype rectification) on probability features, drop-in for the reference's
+"""Few-shot BD-CSPN (prototype rectification) on probability features and on visual features, drop-in for the reference's
 src/methods/few_shot/bdcspn.py.  Same constructor / run_task / logs contract
 (args.norm_type, args.temp, args.n_class; one timestamp, one zero criterion, plain accuracy); the
-whole pass runs in libtclip.so (tclip_bdcspn_run), all tasks of the batch at once instead of the
-reference's per-task Python loop (:124-141)."""
+whole pass runs in libtclip.so, all tasks of the batch at once instead of the reference's per-task
+Python loop (:124-141): tclip_bdcspn_run when the feature width equals args.n_class, tclip_bdcspn_visual_run
+for D-dim embeddings otherwise (the reference never looks at use_softmax_feature here)."""
 import time
 
 import numpy as np
@@ -70,12 +71,14 @@ class BDCSPN(object):
         dev = torch.device(self.device)
         if dev.type != "cuda":
             raise RuntimeError("BDCSPN on MI355X needs device='cuda': there is no CPU fallback in this package")
-        if query.shape[2] != self.n_class:
-            raise NotImplementedError("BDCSPN here takes probability features (feature dimension = n_class)")
         self.logger.info(" ==> Executing BD-CSPN")
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        self.prototypes, self.u, self.preds = engine.run_bdcspn(query, support, y_s, temp=self.temp, norm_type=norm_type)
+        if query.shape[2] == self.n_class:
+            self.prototypes, self.u, self.preds = engine.run_bdcspn(query, support, y_s, temp=self.temp, norm_type=norm_type)
+        else:
+            self.prototypes, self.u, self.preds = engine.run_bdcspn_visual(query, support, y_s, n_class=self.n_class,
+                                                                           temp=self.temp, norm_type=norm_type)
         torch.cuda.synchronize(dev)
         self.record_convergence(new_time=time.time() - t0, criterions=torch.zeros(1))
         self.compute_acc(y_q, self.preds)

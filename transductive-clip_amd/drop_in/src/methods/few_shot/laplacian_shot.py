@@ -55,7 +55,7 @@ class LAPLACIAN_SHOT(object):
 
     def run_method(self, support, query, y_s, y_q, n_batches=1):
         if query.shape[2] != self.args.num_classes_test:
-            raise NotImplementedError("LAPLACIAN_SHOT here takes probability features (feature dimension = n_class)")
+            raise NotImplementedError("LAPLACIAN_SHOT here takes probability features (use_softmax_feature: True, feature dimension = n_class)")
         dev = torch.device(self.device)
         if dev.type != "cuda":
             raise RuntimeError("LAPLACIAN_SHOT on MI355X needs device='cuda': there is no CPU fallback in this package")

@@ -1,8 +1,10 @@
-"""Few-shot PADDLE on probability features, drop-in for the reference's
+"""Few-shot PADDLE on probability features and on visual features, drop-in for the reference's
 src/methods/few_shot/paddle.py.  Same constructor / run_task / logs contract; the
-loop runs in libtclip.so (tclip_paddle_run).  `args.lambd` is the method's own float (paddle.yaml),
-not the class-count formula of EM-Dirichlet.  Visual (non-simplex) features need CLIP text prompts
-for the initial assignment (reference :186-196) and are out of scope."""
+loop runs in libtclip.so (tclip_paddle_run; tclip_paddle_visual_run when args.use_softmax_feature
+is False).  `args.lambd` is the method's own float (paddle.yaml), not the class-count formula of
+EM-Dirichlet.  On visual features the rows are D-dim embeddings and the class count is
+args.num_classes_test, as in the reference; the reference's text-prompt u (:186-196) is overwritten by
+the first u_update before anything reads it, so no text features are asked for."""
 import time
 
 import torch
@@ -25,8 +27,6 @@ class PADDLE(BASE):
         self.lambd = args.lambd       # paddle.py:26
 
     def run_method(self, support, query, y_s, y_q, n_batches=1):
-        if not self.args.use_softmax_feature:
-            raise NotImplementedError("PADDLE on visual features needs CLIP text prompts (out of scope)")
         dev = torch.device(self.device)
         if dev.type != "cuda":
             raise RuntimeError("PADDLE on MI355X needs device='cuda': there is no CPU fallback in this package")
@@ -34,7 +34,11 @@ class PADDLE(BASE):
         n_task = query.shape[0]
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        self.u, self.v, self.w, self.preds = engine.run_paddle(query, support, y_s, iters=self.iter, lambd=self.lambd)
+        if self.args.use_softmax_feature:
+            self.u, self.v, self.w, self.preds = engine.run_paddle(query, support, y_s, iters=self.iter, lambd=self.lambd)
+        else:
+            self.u, self.v, self.w, self.preds = engine.run_paddle_visual(query, support, y_s, n_class=self.args.num_classes_test,
+                                                                          iters=self.iter, lambd=self.lambd)
         torch.cuda.synchronize(dev)
         total = time.time() - t0
         for i in range(self.iter):

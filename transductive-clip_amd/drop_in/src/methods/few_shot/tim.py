@@ -32,7 +32,7 @@ class ALPHA_TIM(BASE):
 
     def run_method(self, support, query, y_s, y_q, n_batches=1):
         if query.shape[2] != self.args.num_classes_test:
-            raise NotImplementedError("ALPHA_TIM here takes probability features (feature dimension = n_class)")
+            raise NotImplementedError("ALPHA_TIM here takes probability features (use_softmax_feature: True, feature dimension = n_class)")
         dev = torch.device(self.device)
         if dev.type != "cuda":
             raise RuntimeError("ALPHA_TIM on MI355X needs device='cuda': there is no CPU fallback in this package")

@@ -21,6 +21,9 @@ the command line wins over all three files (values are literal-eval'ed, an overr
 the value it replaces).  Without a config directory the built-in copies of the reference's defaults below are
 used the same way.  Test-split runs of a tunable few-shot method (PADDLE, BDCSPN) need the validation sweep
 file under <results-root>/results_few_shot/val/, exactly as the reference does; runs with `used_test_set val` append to it.
+With `use_softmax_feature False` the zero-shot k-means family and CLIP (with --text-features) and the few-shot PADDLE and
+BDCSPN (no text features needed) run on the raw embeddings of <split>_visual_<backbone>.plk; the class count is read from
+the labels and the sweep and result files carry `_visual` in their names.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse
@@ -125,6 +128,8 @@ def main(argv=None, keep_process_group=False):
         if not os.path.exists(support_path):
             raise SystemExit(f"{support_path} not found: extract the features with the reference first")
         feats_s, labels_s = features.load_features(support_path)
+        if not args.use_softmax_feature:       # visual features: the class count comes from the labels of both splits
+            args.num_classes_test = args.n_class = max(args.num_classes_test, int(labels_s.max()) + 1)
         ev = Evaluator_few_shot(device=device, args=args, log_file=None)
         acc, t = ev.evaluate_tasks(None, feats_s, labels_s, feats_q, labels_q)
     else:

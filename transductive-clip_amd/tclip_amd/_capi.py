@@ -58,6 +58,12 @@ _SIGNATURES = {
                                                _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_cluster_prototypes_visual": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P] * 6),
     "tclip_visual_init": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P]),
+    "tclip_paddle_visual_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_paddle_visual_run": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, _P, _P, _P, ctypes.c_float, _P, _P, _P, _P,
+                                               _P, ctypes.c_size_t, _P]),
+    "tclip_bdcspn_visual_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_bdcspn_visual_run": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, _P, _P, _P, ctypes.c_float, ctypes.c_int32,
+                                               _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_selftest_primitives": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "tclip_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "tclip_debug_set_probe_chunks": (ctypes.c_int, [ctypes.c_int32]),

@@ -406,6 +406,51 @@ def run_em_gaussian_visual(x_q, u0, *, iters, temperature, lambd):
     return u, v, w, preds
 
 
+def _support_visual(x_q, x_s, y_s, n_class):
+    """_support for D-wide rows: the width of x_s is checked against D, the labels against n_class (on the device: one
+    reduction, its result read back, so that no kernel ever sees a label outside 0..n_class-1)."""
+    x_s, y_s = _support(x_q, x_s, y_s.to(x_q.device))
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    if y_s.numel() and not bool(((y_s >= 0) & (y_s < n_class)).all()):
+        raise ValueError(f"y_s holds a label outside 0..{n_class - 1}")
+    return x_s, y_s, n_class
+
+
+def run_paddle_visual(x_q, x_s, y_s, *, n_class, iters, lambd):
+    """PADDLE on visual features: x_q (T,Q,D), x_s (T,S,D) raw embeddings f32 cuda, y_s (T,S) int64 cuda with labels in
+    0..n_class-1 -> (u (T,Q,K), v (T,K), w (T,K,D), preds (T,Q) i32), cuda, not synchronised.  K = n_class cannot be read off a
+    tensor shape here.  No text features: the reference's text-prompt u is dead (paddle.py:183-203)."""
+    x_q = _query(x_q)
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    T, Q, D = x_q.shape
+    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), "tclip_paddle_visual_workspace_bytes",
+              ctypes.c_int32(D))
+    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
+    c.launch("tclip_paddle_visual_run", lambda ws, n, st: (ctypes.c_int32(D), _ptr(x_q), _ptr(x_s), _ptr(y_s),
+                                                           ctypes.c_float(float(lambd)), _ptr(u), _ptr(v), _ptr(w), _ptr(preds),
+                                                           ws, n, st))
+    return u, v, w, preds
+
+
+def run_bdcspn_visual(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
+    """BD-CSPN on visual features: x_q (T,Q,D), x_s (T,S,D) f32 cuda, y_s (T,S) int64 cuda with labels in 0..n_class-1 ->
+    (rectified prototypes (T,K,D), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised."""
+    if norm_type not in NORM_TYPES:
+        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
+    x_q = _query(x_q)
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    T, Q, D = x_q.shape
+    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], 1, 1, 0, 0), "tclip_bdcspn_visual_workspace_bytes",
+              ctypes.c_int32(D))
+    prototypes, u, preds = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
+    c.launch("tclip_bdcspn_visual_run", lambda ws, n, st: (ctypes.c_int32(D), _ptr(x_q), _ptr(x_s), _ptr(y_s),
+                                                           ctypes.c_float(float(temp)), ctypes.c_int32(NORM_TYPES[norm_type]),
+                                                           _ptr(prototypes), _ptr(u), _ptr(preds), ws, n, st))
+    return prototypes, u, preds
+
+
 def _match(lib, T, Q, K, preds, n_clusters, ids, rows, y_q, graph_matching, cmax, dev):
     """host half of the accuracy tail: copies the rows of the fullest task to the host and matches clusters to classes"""
     preds_h, nc_h = preds.cpu(), n_clusters.cpu()
