@@ -2787,6 +2787,13 @@ static int fail(int code, const char* fmt, const char* detail = "") {
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The end of every entry's argument checks: the caller's workspace holds what `query_name` returns and is 256-byte aligned.
+static int check_workspace(const void* ws, size_t have, size_t need, const char* query_name) {
+    if (have < need) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than %s()", query_name);
+    if (((uintptr_t)ws & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    return TCLIP_OK;
+}
+
 // Optional instrumentation (bench.py): HIP events around every k_mm_live launch and a device
 // counter of the element-updates it executes.  Thread-local, off by default, never touched otherwise.
 struct Profile {
@@ -3831,382 +3838,6 @@ int tclip_em_dirichlet_run_tasks(const tclip_problem* pp, const tclip_task_sourc
                             u, v, alpha, preds, criterions, mm_iters, workspace, workspace_bytes, stream);
 }
 
-// ---- SOFT_KMEANS (BASELINE config 3's second method)
-static size_t kmeans_ws_parts(const tclip_problem& p, size_t* o_cs, size_t* o_live, size_t* o_ones, size_t* o_logit,
-                              size_t* o_rows, size_t* o_scratch_rows, size_t* o_counts) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    *o_cs = take(T * K * 4);
-    *o_live = take(T * K);
-    *o_ones = take(T * K);
-    *o_logit = take(T * Q * K * 4);
-    *o_rows = take(T * K * 4);
-    *o_scratch_rows = take(T * K * 4);
-    *o_counts = take(256);
-    return o;
-}
-
-size_t tclip_soft_kmeans_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    size_t a, b, c, d, e, f, g;
-    return kmeans_ws_parts(*p, &a, &b, &c, &d, &e, &f, &g);
-}
-
-// SOFT_KMEANS (v == nullptr) and EM_GAUSSIAN (v given: the class-proportion term lambd * v / Q in the
-// softmax and the v update of em_gaussian.py:129-143) share everything else.
-static int soft_kmeans_core(const tclip_problem& p, const float* x_q, float temperature, float* v, float* u, float* w,
-                            int32_t* preds, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
-    if (!x_q || !u || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "%s is a zero-shot method: n_support must be 0", who);
-    size_t o_cs, o_live, o_ones, o_logit, o_rows, o_scratch, o_counts;
-    const size_t total = kmeans_ws_parts(p, &o_cs, &o_live, &o_ones, &o_logit, &o_rows, &o_scratch, &o_counts);
-    if (workspace_bytes < total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_soft_kmeans_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o_cs);
-    uint8_t* live = (uint8_t*)(ws + o_live);
-    uint8_t* ones = (uint8_t*)(ws + o_ones);
-    float* logit0 = (float*)(ws + o_logit);
-    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
-    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
-    if (v) hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    // w_init: every centroid = u^T z / clamp(sum u)                             (soft_kmeans.py:137-149)
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
-                       (float*)nullptr, (int32_t*)nullptr);
-    launch_mstats(st, (const float*)u, (const float*)x_q, (const float*)cs, (const uint8_t*)ones, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0, true);
-    // SOFT_KMEANS keeps its clusters alive (every query spreads its responsibility over all of them); EM_GAUSSIAN's class-proportion
-    // term leaves a handful per task after two iterations (profiles/r05_kmeans_live_clusters.txt): only the former is "dense"
-    const bool dense = v == nullptr;
-    for (int it = 0; it < p.iters; it++) {
-        // w_update: live clusters get the new mean, empty ones keep their centroid   (:151-168)
-        // EM_GAUSSIAN: the same pass over u also yields v of the previous iteration's v_update (v stays 0 before the first)
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
-                           live, it > 0 ? v : (float*)nullptr, (int32_t*)nullptr);
-        launch_mstats(st, (const float*)u, (const float*)x_q, (const float*)cs, (const uint8_t*)live, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0, dense);
-        // distances only for centroids that moved (all of them in the first iteration)
-        launch_kmeans_logits(T, st, (const float*)w, x_q, (const uint8_t*)(it == 0 ? ones : live), Q, K, -0.5f,
-                                           temperature, logit0);
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
-                           (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
-    }
-    if (v)      // the last v_update
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
-                           v, (int32_t*)nullptr);
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
-
-int tclip_soft_kmeans_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* w,
-                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    return soft_kmeans_core(*pp, x_q, temperature, nullptr, u, w, preds, workspace, workspace_bytes, stream, "SOFT_KMEANS");
-}
-
-int tclip_em_gaussian_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* v, float* w,
-                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (!v) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    return soft_kmeans_core(*pp, x_q, temperature, v, u, w, preds, workspace, workspace_bytes, stream, "EM_GAUSSIAN");
-}
-
-// ---- EM_GAUSSIAN_COV: EM_GAUSSIAN with a diagonal inverse covariance per cluster; no temperature
-int tclip_em_gaussian_cov_run(const tclip_problem* pp, const float* x_q, float* u, float* v, float* w, float* s,
-                              int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !v || !w || !s || !preds || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "EM_GAUSSIAN_COV is a zero-shot method: n_support must be 0");
-    size_t o_cs, o_live, o_ones, o_logit, o_rows, o_scratch, o_counts;
-    const size_t total = kmeans_ws_parts(p, &o_cs, &o_live, &o_ones, &o_logit, &o_rows, &o_scratch, &o_counts);
-    if (workspace_bytes < total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_soft_kmeans_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o_cs);
-    uint8_t* live = (uint8_t*)(ws + o_live);
-    uint8_t* ones = (uint8_t*)(ws + o_ones);
-    float* logit0 = (float*)(ws + o_logit);
-    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
-    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    // w_init, s_init: every cluster                                                (em_gaussian_cov.py:146-180)
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
-                       (float*)nullptr, (int32_t*)nullptr);
-    launch_mstats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)ones, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
-    launch_cov_stats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)ones, (const float*)w, T, Q, K, s);
-    for (int it = 0; it < p.iters; it++) {
-        // w_update, s_update: non-empty clusters move, empty ones keep w and s        (:160-193); v of the previous v_update
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
-                           live, it > 0 ? v : (float*)nullptr, (int32_t*)nullptr);
-        launch_mstats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)live, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
-        launch_cov_stats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)live, (const float*)w, T, Q, K, s);
-        // u_update: Mahalanobis distances + log-determinants of the clusters that moved, softmax with lambd v / Q   (:106-129)
-        dispatch_E<LaunchCovLogitsRows>(K, T, st, (const float*)w, (const float*)s, x_q, (const uint8_t*)(it == 0 ? ones : live), Q, K,
-                                        logit0);
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
-                           (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
-    }
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
-                       (int32_t*)nullptr);                                              // the last v_update
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
-
-size_t tclip_hard_kmeans_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    size_t a, b, c, d, e, f, g;
-    return kmeans_ws_parts(*p, &a, &b, &c, &d, &e, &f, &g) + align_up((size_t)p->n_batches * p->tasks_per_batch * 4);
-}
-
-int tclip_hard_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
-                          float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !w || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "HARD_KMEANS is a zero-shot method: n_support must be 0");
-    size_t o_cs, o_live, o_ones, o_logit, o_rows, o_scratch, o_counts;
-    const size_t o_change = kmeans_ws_parts(p, &o_cs, &o_live, &o_ones, &o_logit, &o_rows, &o_scratch, &o_counts);
-    if (workspace_bytes < tclip_hard_kmeans_workspace_bytes(pp)) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_hard_kmeans_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
-    const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o_cs);
-    uint8_t* live = (uint8_t*)(ws + o_live);
-    uint8_t* ones = (uint8_t*)(ws + o_ones);
-    float* logit0 = (float*)(ws + o_logit);
-    float* change = (float*)(ws + o_change);
-    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
-    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));                                     // every centroid moves every iteration
-    for (int it = 0; it < p.iters; it++) {
-        // w_update: mean of the members, zero for empty clusters                            (hard_kmeans.py:138-152)
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
-                           live, (float*)nullptr, (int32_t*)nullptr);
-        launch_mstats(st, (const float*)u, (const float*)x_q, (const float*)cs, (const uint8_t*)live, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
-        hipLaunchKernelGGL(k_zero_dead_rows, dim3(ew_grid((size_t)TK * K)), dim3(256), 0, st, (const uint8_t*)live, TK, K, w);
-        // u_update + hard assignment: softmax of the squared distances, first minimum    (:128-136, :193-195)
-        launch_kmeans_logits(T, st, (const float*)w, x_q, (const uint8_t*)ones, Q, K, 1.0f, 1.0f, logit0);
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
-                           (const float*)nullptr, T * Q, Q, K, 0.0f, 0, 1, logit0, preds);
-        // criterion mean_n ||u_old - u||_F, u <- one-hot                                       (:197-199)
-        hipLaunchKernelGGL(k_hard_assign, dim3(T), dim3(256), 0, st, (const int32_t*)preds, Q, K, u, change);
-        hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)change, N, 0, criterions + it, p.iters);
-    }
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
-
-// ---- PADDLE: few-shot soft k-means with the class-proportion penalty
-static size_t paddle_ws_parts(const tclip_problem& p, size_t* o_sup, size_t* o_cnt, size_t* o_cs, size_t* o_live,
-                              size_t* o_logit, size_t* o_rows, size_t* o_scratch_rows, size_t* o_counts) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    *o_sup = take(T * K * K * 4);
-    *o_cnt = take(T * K * 4);
-    *o_cs = take(T * K * 4);
-    *o_live = take(T * K);
-    *o_logit = take(T * Q * K * 4);
-    *o_rows = take(T * K * 4);
-    *o_scratch_rows = take(T * K * 4);
-    *o_counts = take(256);
-    return o;
-}
-
-size_t tclip_paddle_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    size_t a, b, c, d, e, f, g, h;
-    return paddle_ws_parts(*p, &a, &b, &c, &d, &e, &f, &g, &h);
-}
-
-int tclip_paddle_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float lambd,
-                     float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
-                     void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "PADDLE is a few-shot method: n_support must be positive");
-    size_t o_sup, o_cnt, o_cs, o_live, o_logit, o_rows, o_scratch, o_counts;
-    const size_t total = paddle_ws_parts(p, &o_sup, &o_cnt, &o_cs, &o_live, &o_logit, &o_rows, &o_scratch, &o_counts);
-    if (workspace_bytes < total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_paddle_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    float* sup = (float*)(ws + o_sup);
-    float* cnt = (float*)(ws + o_cnt);
-    float* cs = (float*)(ws + o_cs);
-    uint8_t* live = (uint8_t*)(ws + o_live);
-    float* logit0 = (float*)(ws + o_logit);
-    // init (paddle.py:180-197): v = 0, prototypes = class means of the support set; every centroid moves every iteration
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(x_s), y_s, S, K, 0, sup, cnt);
-    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * K)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
-                       (size_t)TK * K, K, w);
-    TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
-    for (int it = 0; it < p.iters; it++) {
-        // u_update (:105-116): softmax_k(-1/2 ||w_k - z_q||^2 + lambd v_k / Q)
-        launch_kmeans_logits(T, st, (const float*)w, x_q, (const uint8_t*)live, Q, K, -0.5f, 1.0f, logit0);
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
-                           T * Q, Q, K, lambd, 0, 0, u, preds);
-        // v_update (:118-124) and w_update (:142-158)
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 0, cs, live,
-                           v, (int32_t*)nullptr);
-        launch_mstats(st, (const float*)u, (const float*)x_q, (const float*)cs, (const uint8_t*)live, (const float*)sup, (const float*)cnt, T, Q, K, w, 1);
-    }
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
-
-// ---- BD-CSPN: one pass, no loop
-struct BdcspnWs { size_t zs, zq, zqn, mean, eta, sup, cnt, wn, aug, logit, cs, live, dummy, total; };
-static BdcspnWs bdcspn_ws(const tclip_problem& p) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q;
-    BdcspnWs w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    w.zs = take(T * S * K * 4);
-    w.zq = take(T * Q * K * 4);
-    w.zqn = take(T * Q * K * 4);
-    w.mean = take(T * K * 4);
-    w.eta = take(T * K * 4);
-    w.sup = take(T * K * K * 4);
-    w.cnt = take(T * K * 4);
-    w.wn = take(T * K * K * 4);
-    w.aug = take(T * R * K * 4);
-    w.logit = take(T * R * K * 4);
-    w.cs = take(T * K * 4);
-    w.live = take(T * K);
-    w.dummy = take(T * R * 4);
-    w.total = o;
-    return w;
-}
-
-size_t tclip_bdcspn_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    return bdcspn_ws(*p).total;
-}
-
-int tclip_bdcspn_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
-                     int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
-                     size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !x_s || !y_s || !prototypes || !u || !preds || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "BDCSPN is a few-shot method: n_support must be positive");
-    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, "norm_type must be 0 (UN), 1 (L2N) or 2 (CL2N)");
-    const BdcspnWs o = bdcspn_ws(p);
-    if (workspace_bytes < o.total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_bdcspn_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    float* zs = (float*)(ws + o.zs);
-    float* zq = (float*)(ws + o.zq);
-    float* zqn = (float*)(ws + o.zqn);
-    float* mean = (float*)(ws + o.mean);
-    float* eta = (float*)(ws + o.eta);
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* wn = (float*)(ws + o.wn);
-    float* aug = (float*)(ws + o.aug);
-    float* logit = (float*)(ws + o.logit);
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    int32_t* dummy = (int32_t*)(ws + o.dummy);
-    auto rows_grid = [](int n_rows) { return dim3((unsigned)(((size_t)n_rows * 8 + 255) / 256)); };
-    auto normalize = [&](const float* x, const float* x2, int R0, int Rr, int mode, const float* mn, const float* sh, float* out) {
-        hipLaunchKernelGGL(k_bdcspn_normalize, rows_grid(T * Rr), dim3(256), 0, st, x, x2, R0, Rr, K, mode, mn, sh, T * Rr, out);
-    };
-    // normalization (bdcspn.py:77-100, :165-166): train_mean = support.mean(1); CL2N / L2N / none
-    if (norm_type == 2) hipLaunchKernelGGL(k_col_mean, dim3((TK + 255) / 256), dim3(256), 0, st, x_s, T, S, K, mean);
-    normalize(x_s, x_s, S, S, norm_type, (const float*)mean, (const float*)nullptr, zs);
-    normalize(x_q, x_q, Q, Q, norm_type, (const float*)mean, (const float*)nullptr, zq);
-    // initial prototypes: support class means (:117-120), L2-normalised for get_logits (:50)
-    hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(zs), y_s, S, K, 0, sup, cnt);
-    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * K)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
-                       (size_t)TK * K, K, prototypes);
-    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
-    // augmented set: support rows, then query rows shifted by eta = mean(support) - mean(query); normalised (:127-131, :51, :137)
-    hipLaunchKernelGGL(k_bdcspn_eta, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)zs, (const float*)zq, T, S, Q, K, eta);
-    normalize((const float*)zs, (const float*)zq, S, R, 1, (const float*)nullptr, (const float*)eta, aug);
-    // soft assignment of the augmented set to the initial prototypes (:133-134)
-    TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
-    launch_kmeans_logits(T, st, (const float*)wn, (const float*)aug, (const uint8_t*)live, R, K, -0.5f, temp, logit);
-    hipLaunchKernelGGL(k_softmax, dim3((T * R * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
-                       T * R, R, K, 0.0f, 0, 0, logit, dummy);
-    // rectified prototypes = assignment-weighted means of the normalised augmented set (:137-141)
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)logit, T, R, K, 0, cs, live,
-                       (float*)nullptr, (int32_t*)nullptr);
-    launch_mstats(st, (const float*)logit, (const float*)aug, (const float*)cs, (const uint8_t*)live, (const float*)nullptr,
-                  (const float*)nullptr, T, R, K, prototypes, 2);
-    // prediction (:190-193): softmax(temp * get_logits(prototypes, query)), argmax
-    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
-    normalize((const float*)zq, (const float*)zq, Q, Q, 1, (const float*)nullptr, (const float*)nullptr, zqn);
-    launch_kmeans_logits(T, st, (const float*)wn, (const float*)zqn, (const uint8_t*)live, Q, K, -0.5f, temp, logit);
-    hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
-                       T * Q, Q, K, 0.0f, 0, 0, u, preds);
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
-
-int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
-                        float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !w || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "KL_KMEANS is a zero-shot method: n_support must be 0");
-    size_t o_cs, o_live, o_ones, o_logit, o_rows, o_scratch, o_counts;
-    const size_t o_change = kmeans_ws_parts(p, &o_cs, &o_live, &o_ones, &o_logit, &o_rows, &o_scratch, &o_counts);
-    if (workspace_bytes < tclip_hard_kmeans_workspace_bytes(pp)) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_hard_kmeans_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
-    const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o_cs);
-    uint8_t* live = (uint8_t*)(ws + o_live);
-    float* divs = (float*)(ws + o_logit);
-    float* change = (float*)(ws + o_change);
-    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
-    for (int it = 0; it < p.iters; it++) {
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
-                           live, (float*)nullptr, (int32_t*)nullptr);
-        if (Q == kColsQ && K >= kColsChunk && g_kmeans_tile != 0) {
-            const int dtiles = (K + 63) / 64;
-            int splits = (int)((8192 + (long)T * dtiles - 1) / ((long)T * dtiles));
-            if (splits > K / (kColsWaves * kColsChunk)) splits = K / (kColsWaves * kColsChunk);
-            if (splits < 1) splits = 1;
-            const int rows_per_block = ((K + splits - 1) / splits + kColsChunk - 1) / kColsChunk * kColsChunk;
-            const int ksplits = (K + rows_per_block - 1) / rows_per_block;
-            hipLaunchKernelGGL(k_kl_centroids_cols75, dim3(task_tile_grid(dtiles, ksplits, T)), dim3(64 * kColsWaves), 0,
-                               st, (const float*)u, x_q, (const float*)cs, K, rows_per_block, w, T, dtiles, ksplits);
-        } else {
-            hipLaunchKernelGGL(k_kl_centroids, dim3((K + 63) / 64, (K + kMstatsRows - 1) / kMstatsRows, T), dim3(64), 0, st,
-                               (const float*)u, x_q, (const float*)cs, Q, K, w);
-        }
-        if (g_kmeans_tile != 0 && K >= 32 && K <= 511 && kmeans_tile_lds_raised((const void*)k_kl_divergences_tile)) {
-            const int stride = K | 1;
-            hipLaunchKernelGGL(k_kl_divergences_tile, dim3((K + kKmeansTile - 1) / kKmeansTile, T), dim3(kKmeansTileThreads),
-                               (size_t)kKmeansTile * stride * sizeof(float), st, (const float*)w, x_q, Q, K, stride, divs);
-        } else {
-            dispatch_E<LaunchKlDivergences>(K, T, st, (const float*)w, x_q, Q, K, divs);
-        }
-        hipLaunchKernelGGL(k_argmin_rows, dim3((T * Q + 255) / 256), dim3(256), 0, st, (const float*)divs, T * Q, K, preds);
-        hipLaunchKernelGGL(k_hard_assign, dim3(T), dim3(256), 0, st, (const int32_t*)preds, Q, K, u, change);
-        hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)change, N, 0, criterions + it, p.iters);
-    }
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
-
 int tclip_argmax_rows(const float* x, int64_t n_rows, int32_t n_class, int32_t* labels, void* stream) {
     if (!x || !labels || n_rows < 0 || n_class < 1) return fail(TCLIP_ERR_ARG, "bad argument to tclip_argmax_rows");
     if (n_rows == 0) return TCLIP_OK;
@@ -4429,3 +4060,4 @@ int tclip_gather_rows(const float* table, int64_t n_rows, int32_t K, const int64
 #include "tclip_lshot.inc"
 #include "tclip_visual.inc"
 #include "tclip_visual_fs.inc"
+#include "tclip_methods.inc"

@@ -251,8 +251,7 @@ int tclip_laplacian_shot_run(const tclip_problem* pp, const float* x_q, const fl
     if (knn < 2 || knn > p.n_query) return fail(TCLIP_ERR_ARG, "knn must be in 2..n_query (the nearest neighbour of a query is the query itself)");
     if (p.n_query > kLshotMaxQ) return fail(TCLIP_ERR_ARG, "n_query must be <= 1024 for LAPLACIAN_SHOT");
     const LshotWs o = lshot_ws(p);
-    if (workspace_bytes < o.total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_laplacian_shot_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_laplacian_shot_workspace_bytes")) return rc;
     const size_t smem = (((size_t)p.n_query * (knn - 1) * sizeof(int) + 7) & ~(size_t)7) + (size_t)p.n_query * sizeof(double);
     if (smem > 60000) return fail(TCLIP_ERR_ARG, "n_query * knn too large for the neighbour lists in LDS");
     hipStream_t st = (hipStream_t)stream;

@@ -1,0 +1,503 @@
+// Host drivers of the k-means family and of few-shot PADDLE / BD-CSPN, one per algorithm for both feature kinds: included
+// last by tclip_kernels.hip, after the kernels and launchers of tclip_visual.inc / tclip_visual_fs.inc.
+//
+// Probability features (the reference's use_softmax_feature == True) have rows of K = n_class elements; visual features (raw
+// CLIP embeddings) rows of D elements, D independent of K.  The op sequences are the same; a FeatureSpace picks the three
+// launchers whose work depends on the row length, everything else ([T, Q, K] / [T, K] tensors: the softmax, the cluster sizes,
+// v, the first-minimum one-hot, the criterion) is shared as it stands.  EM_GAUSSIAN_COV and KL_KMEANS exist on probability
+// features only and keep their own loops below.  EM-Dirichlet does not come through here.
+
+namespace tclip {
+
+// which rows the centroid statistics write and what they divide by (the values are k_vis_mstats's modes)
+enum class Mstats {
+    LiveOnly = 0,        // quotient by clamp(cs, eps); rows `live` does not mark keep their value   (SOFT_KMEANS, EM_GAUSSIAN)
+    HardZeroDead = 1,    // the same quotient; rows that are not live get it times 0                 (HARD_KMEANS)
+    PaddleAdd = 2,       // (sum + support class sums) / (cs + support counts), every row           (PADDLE's w_update)
+    PlainQuotient = 3,   // sum / cs, every row                                                      (BD-CSPN's rectified prototypes)
+};
+
+struct FeatureSpace {
+    int D;               // elements of a feature row; n_class for probability features
+    bool visual;
+
+    // out[t,r,k] = temperature * (pre * ||w[t,k,:] - z[t,r,:]||^2) for the classes `need` marks
+    int dist(int T, hipStream_t st, const float* w, const float* z, const uint8_t* need, int R, int K, float pre, float temperature,
+             float* out) const {
+        if (visual) return launch_vis_dist(T, st, w, z, need, R, K, D, pre, temperature, out);
+        launch_kmeans_logits(T, st, w, z, need, R, K, pre, temperature, out);
+        return TCLIP_OK;
+    }
+
+    // y[t,k,:] = sum_r u[t,r,k] z[t,r,:] over R rows, divided as `kind` says; `dense` (probability features only): the caller
+    // expects nearly every class alive
+    void mstats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, int T, int R, int K, Mstats kind,
+                float* y, const float* sup, const float* cnt, bool dense) const {
+        if (visual) {
+            launch_vis_mstats(st, u, z, cs, live, T, R, K, D, (int)kind, y, sup, cnt);
+            return;
+        }
+        launch_mstats(st, u, z, cs, live, sup, cnt, T, R, K, y, kind == Mstats::PaddleAdd ? 1 : kind == Mstats::PlainQuotient ? 2 : 0, dense);
+        if (kind == Mstats::HardZeroDead) {
+            const int TK = T * K;
+            hipLaunchKernelGGL(k_zero_dead_rows, dim3(ew_grid((size_t)TK * K)), dim3(256), 0, st, live, TK, K, y);
+        }
+    }
+
+    // sup[t,k,:] = sum of the support rows of class k, cnt[t,k] = their number
+    void support_stats(hipStream_t st, const float* x_s, const int64_t* y_s, int T, int S, int K, float* sup, float* cnt) const {
+        if (visual) launch_vis_support_stats(st, x_s, y_s, T, S, K, D, sup, cnt);
+        else hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(x_s), y_s, S, K, 0, sup, cnt);
+    }
+};
+
+// ---- workspace layouts: byte offsets of 256-byte aligned regions, `total` their sum ------------------------------------
+// The k-means loops hold no feature rows of their own: no region depends on the row length.
+struct KmeansWs {
+    size_t cs, live, ones, logit, change, total;      // change [T] f32: HARD_KMEANS and KL_KMEANS only
+    static KmeansWs layout(const tclip_problem& p) {
+        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
+        KmeansWs w;
+        size_t o = 0;
+        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
+        w.cs = take(T * K * 4);
+        w.live = take(T * K);
+        w.ones = take(T * K);
+        w.logit = take(T * Q * K * 4);
+        w.change = take(T * 4);
+        w.total = o;
+        return w;
+    }
+};
+
+struct PaddleWs {
+    size_t sup, cnt, cs, live, logit, total;
+    static PaddleWs layout(const tclip_problem& p, int dim) {
+        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, D = dim;
+        PaddleWs w;
+        size_t o = 0;
+        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
+        w.sup = take(T * K * D * 4);
+        w.cnt = take(T * K * 4);
+        w.cs = take(T * K * 4);
+        w.live = take(T * K);
+        w.logit = take(T * Q * K * 4);
+        w.total = o;
+        return w;
+    }
+};
+
+struct BdcspnWs {
+    size_t zs, zq, zqn, mean, eta, sup, cnt, wn, aug, logit, cs, live, dummy, total;
+    static BdcspnWs layout(const tclip_problem& p, int dim) {
+        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
+        BdcspnWs w;
+        size_t o = 0;
+        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
+        w.zs = take(T * S * D * 4);
+        w.zq = take(T * Q * D * 4);
+        w.zqn = take(T * Q * D * 4);
+        w.mean = take(T * D * 4);
+        w.eta = take(T * D * 4);
+        w.sup = take(T * K * D * 4);
+        w.cnt = take(T * K * 4);
+        w.wn = take(T * K * D * 4);
+        w.aug = take(T * R * D * 4);
+        w.logit = take(T * R * K * 4);
+        w.cs = take(T * K * 4);
+        w.live = take(T * K);
+        w.dummy = take(T * R * 4);
+        w.total = o;
+        return w;
+    }
+};
+
+// ---- SOFT_KMEANS, EM_GAUSSIAN, HARD_KMEANS (SURVEY.md section 8f, F1; BASELINE config 3's second method) ----------------
+// Soft and EmGaussian share everything but the class-proportion term lambd * v / Q in the softmax and the v update
+// (em_gaussian.py:129-143).  u_init: the features themselves for probability features, the text-prompt u0 for visual ones.
+enum class Kmeans { Soft, EmGaussian, Hard };
+
+static int kmeans_loop(const FeatureSpace& sp, Kmeans kind, const tclip_problem& p, const float* x_q, const float* u_init,
+                       float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, char* ws, hipStream_t st) {
+    const KmeansWs o = KmeansWs::layout(p);
+    const bool hard = kind == Kmeans::Hard, emg = kind == Kmeans::EmGaussian;
+    const int Q = p.n_query, K = p.n_class, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
+    const size_t TQK = (size_t)T * Q * K;
+    float* cs = (float*)(ws + o.cs);
+    uint8_t* live = (uint8_t*)(ws + o.live);
+    uint8_t* ones = (uint8_t*)(ws + o.ones);
+    float* logit0 = (float*)(ws + o.logit);
+    float* change = (float*)(ws + o.change);
+    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, u_init, u, TQK);       // u = z / u = u0
+    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));                                     // HARD_KMEANS: every centroid moves every iteration
+    if (emg) hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
+    if (!hard) {
+        // w_init: every centroid = u^T z / clamp(sum u)                  (soft_kmeans.py:126-149, em_gaussian.py:145-155)
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
+                           (float*)nullptr, (int32_t*)nullptr);
+        sp.mstats(st, u, x_q, cs, ones, T, Q, K, Mstats::LiveOnly, w, nullptr, nullptr, true);
+    }
+    // SOFT_KMEANS keeps its clusters alive (every query spreads its responsibility over all of them); EM_GAUSSIAN's class-proportion
+    // term leaves a handful per task after two iterations (profiles/r05_kmeans_live_clusters.txt): only the former is "dense"
+    const bool dense = kind == Kmeans::Soft;
+    for (int it = 0; it < p.iters; it++) {
+        // w_update: live clusters get the new mean; empty ones keep their centroid (soft_kmeans.py:151-168) or, HARD_KMEANS, become
+        // zero (hard_kmeans.py:138-152).  EM_GAUSSIAN: the same pass over u also yields v of the previous iteration's v_update
+        // (v stays 0 before the first)
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
+                           (emg && it > 0) ? v : (float*)nullptr, (int32_t*)nullptr);
+        sp.mstats(st, u, x_q, cs, live, T, Q, K, hard ? Mstats::HardZeroDead : Mstats::LiveOnly, w, nullptr, nullptr, dense);
+        if (hard) {
+            // u_update + hard assignment: softmax of the squared distances, first minimum      (hard_kmeans.py:128-136, :193-195)
+            if (int rc = sp.dist(T, st, w, x_q, ones, Q, K, 1.0f, 1.0f, logit0)) return rc;
+            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
+                               (const float*)nullptr, T * Q, Q, K, 0.0f, 0, 1, logit0, preds);
+            // criterion mean_n ||u_old - u||_F, u <- one-hot                                                      (:197-199)
+            hipLaunchKernelGGL(k_hard_assign, dim3(T), dim3(256), 0, st, (const int32_t*)preds, Q, K, u, change);
+            hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)change, N, 0, criterions + it, p.iters);
+        } else {
+            // distances only for centroids that moved (all of them in the first iteration), E-step softmax
+            if (int rc = sp.dist(T, st, w, x_q, it == 0 ? ones : live, Q, K, -0.5f, temperature, logit0)) return rc;
+            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
+                               (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
+        }
+    }
+    if (emg)      // the last v_update
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
+                           (int32_t*)nullptr);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+// ---- PADDLE (SURVEY.md section 8f, F4): few-shot soft k-means with the class-proportion penalty -------------------------
+static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const float* x_s, const int64_t* y_s,
+                       float lambd, float* u, float* v, float* w, int32_t* preds, char* ws, hipStream_t st) {
+    const PaddleWs o = PaddleWs::layout(p, sp.D);
+    const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
+    float* sup = (float*)(ws + o.sup);
+    float* cnt = (float*)(ws + o.cnt);
+    float* cs = (float*)(ws + o.cs);
+    uint8_t* live = (uint8_t*)(ws + o.live);
+    float* logit0 = (float*)(ws + o.logit);
+    // init (paddle.py:180-197): v = 0, w = class means of the support set (on visual features the text-prompt u is overwritten
+    // before it is read); every centroid moves every iteration
+    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
+    sp.support_stats(st, x_s, y_s, T, S, K, sup, cnt);
+    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
+                       (size_t)TK * D, D, w);
+    TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
+    for (int it = 0; it < p.iters; it++) {
+        // u_update (:105-116): softmax_k(-1/2 ||w_k - z_q||^2 + lambd v_k / Q)
+        if (int rc = sp.dist(T, st, w, x_q, live, Q, K, -0.5f, 1.0f, logit0)) return rc;
+        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
+                           T * Q, Q, K, lambd, 0, 0, u, preds);
+        // v_update (:118-124) and w_update (:142-158)
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 0, cs, live, v,
+                           (int32_t*)nullptr);
+        sp.mstats(st, u, x_q, cs, live, T, Q, K, Mstats::PaddleAdd, w, sup, cnt, false);
+    }
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+// ---- BD-CSPN (SURVEY.md F4): one pass, no loop ------------------------------------------------------------------------
+// k_col_mean, k_bdcspn_normalize, k_bdcspn_eta and k_div_rows take the row length where their signatures say K.
+static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
+                       int norm_type, float* prototypes, float* u, int32_t* preds, char* ws, hipStream_t st) {
+    const BdcspnWs o = BdcspnWs::layout(p, sp.D);
+    const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, R = S + Q, T = p.n_batches * p.tasks_per_batch, TK = T * K;
+    const int TD = T * D;
+    float* zs = (float*)(ws + o.zs);
+    float* zq = (float*)(ws + o.zq);
+    float* zqn = (float*)(ws + o.zqn);
+    float* mean = (float*)(ws + o.mean);
+    float* eta = (float*)(ws + o.eta);
+    float* sup = (float*)(ws + o.sup);
+    float* cnt = (float*)(ws + o.cnt);
+    float* wn = (float*)(ws + o.wn);
+    float* aug = (float*)(ws + o.aug);
+    float* logit = (float*)(ws + o.logit);
+    float* cs = (float*)(ws + o.cs);
+    uint8_t* live = (uint8_t*)(ws + o.live);
+    int32_t* dummy = (int32_t*)(ws + o.dummy);
+    auto rows_grid = [](int n_rows) { return dim3((unsigned)(((size_t)n_rows * 8 + 255) / 256)); };
+    auto normalize = [&](const float* x, const float* x2, int R0, int Rr, int mode, const float* mn, const float* sh, float* out) {
+        hipLaunchKernelGGL(k_bdcspn_normalize, rows_grid(T * Rr), dim3(256), 0, st, x, x2, R0, Rr, D, mode, mn, sh, T * Rr, out);
+    };
+    // normalization (bdcspn.py:77-100, :165-166): train_mean = support.mean(1), an outer sum over D columns; CL2N / L2N / none
+    if (norm_type == 2) hipLaunchKernelGGL(k_col_mean, dim3((TD + 255) / 256), dim3(256), 0, st, x_s, T, S, D, mean);
+    normalize(x_s, x_s, S, S, norm_type, (const float*)mean, (const float*)nullptr, zs);
+    normalize(x_q, x_q, Q, Q, norm_type, (const float*)mean, (const float*)nullptr, zq);
+    // initial prototypes: support class means (:117-120), L2-normalised for get_logits (:50)
+    sp.support_stats(st, zs, y_s, T, S, K, sup, cnt);
+    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
+                       (size_t)TK * D, D, prototypes);
+    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
+    // augmented set: support rows, then query rows shifted by eta = mean(support) - mean(query); normalised (:127-131, :51, :137)
+    hipLaunchKernelGGL(k_bdcspn_eta, dim3((TD + 255) / 256), dim3(256), 0, st, (const float*)zs, (const float*)zq, T, S, Q, D, eta);
+    normalize((const float*)zs, (const float*)zq, S, R, 1, (const float*)nullptr, (const float*)eta, aug);
+    // soft assignment of the augmented set to the initial prototypes (:133-134)
+    TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
+    if (int rc = sp.dist(T, st, wn, aug, live, R, K, -0.5f, temp, logit)) return rc;
+    hipLaunchKernelGGL(k_softmax, dim3((T * R * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
+                       T * R, R, K, 0.0f, 0, 0, logit, dummy);
+    // rectified prototypes = assignment-weighted means of the normalised augmented set (:137-141)
+    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)logit, T, R, K, 0, cs, live,
+                       (float*)nullptr, (int32_t*)nullptr);
+    sp.mstats(st, logit, aug, cs, live, T, R, K, Mstats::PlainQuotient, prototypes, nullptr, nullptr, false);
+    // prediction (:190-193): softmax(temp * get_logits(prototypes, query)), argmax
+    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
+    normalize((const float*)zq, (const float*)zq, Q, Q, 1, (const float*)nullptr, (const float*)nullptr, zqn);
+    if (int rc = sp.dist(T, st, wn, zqn, live, Q, K, -0.5f, temp, logit)) return rc;
+    hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
+                       T * Q, Q, K, 0.0f, 0, 0, u, preds);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+static const char* const kNullArg = "null pointer argument";
+static const char* const kZeroShotOnly = "%s is a zero-shot method: n_support must be 0";
+static const char* const kFewShotOnly = "%s is a few-shot method: n_support must be positive";
+static const char* const kNormType = "norm_type must be 0 (UN), 1 (L2N) or 2 (CL2N)";
+static const char* const kDimRange = "dim must be in 1..1024";
+
+// the checks the two visual few-shot entries and their workspace queries share
+static int check_visual_fs(const tclip_problem* p, int32_t dim, const char* who) {
+    if (int rc = check_problem(p)) return rc;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, kDimRange);
+    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, who);
+    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)p->n_support + p->n_query;
+    if (T * R * 16 > 0x7fffffffu || T * (size_t)dim > 0x7fffffffu)
+        return fail(TCLIP_ERR_ARG, "%s: tasks * (n_support + n_query) * 16 and tasks * dim must fit in int32", who);
+    return TCLIP_OK;
+}
+
+}  // namespace tclip
+
+extern "C" {
+
+// ---- zero-shot, probability features ------------------------------------------------------------------------------------
+size_t tclip_soft_kmeans_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    return KmeansWs::layout(*p).total;
+}
+
+size_t tclip_hard_kmeans_workspace_bytes(const tclip_problem* p) { return tclip_soft_kmeans_workspace_bytes(p); }
+
+int tclip_soft_kmeans_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* w,
+                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !u || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "SOFT_KMEANS");
+    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_soft_kmeans_workspace_bytes")) return rc;
+    return kmeans_loop(FeatureSpace{p.n_class, false}, Kmeans::Soft, p, x_q, x_q, temperature, u, nullptr, w, preds, nullptr,
+                       (char*)workspace, (hipStream_t)stream);
+}
+
+int tclip_em_gaussian_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* v, float* w,
+                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN");
+    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_soft_kmeans_workspace_bytes")) return rc;
+    return kmeans_loop(FeatureSpace{p.n_class, false}, Kmeans::EmGaussian, p, x_q, x_q, temperature, u, v, w, preds, nullptr,
+                       (char*)workspace, (hipStream_t)stream);
+}
+
+int tclip_hard_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
+                          float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !u || !w || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "HARD_KMEANS");
+    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_hard_kmeans_workspace_bytes")) return rc;
+    return kmeans_loop(FeatureSpace{p.n_class, false}, Kmeans::Hard, p, x_q, x_q, 1.0f, u, nullptr, w, preds, criterions,
+                       (char*)workspace, (hipStream_t)stream);
+}
+
+// ---- EM_GAUSSIAN_COV (SURVEY.md F1): EM_GAUSSIAN with a diagonal inverse covariance per cluster; no temperature
+int tclip_em_gaussian_cov_run(const tclip_problem* pp, const float* x_q, float* u, float* v, float* w, float* s,
+                              int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !u || !v || !w || !s || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV");
+    const KmeansWs o = KmeansWs::layout(p);
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_soft_kmeans_workspace_bytes")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const int Q = p.n_query, K = p.n_class, T = p.n_batches * p.tasks_per_batch, TK = T * K;
+    const size_t TQK = (size_t)T * Q * K;
+    float* cs = (float*)(ws + o.cs);
+    uint8_t* live = (uint8_t*)(ws + o.live);
+    uint8_t* ones = (uint8_t*)(ws + o.ones);
+    float* logit0 = (float*)(ws + o.logit);
+    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
+    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
+    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
+    // w_init, s_init: every cluster                                                (em_gaussian_cov.py:146-180)
+    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
+                       (float*)nullptr, (int32_t*)nullptr);
+    launch_mstats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)ones, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
+    launch_cov_stats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)ones, (const float*)w, T, Q, K, s);
+    for (int it = 0; it < p.iters; it++) {
+        // w_update, s_update: non-empty clusters move, empty ones keep w and s        (:160-193); v of the previous v_update
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
+                           live, it > 0 ? v : (float*)nullptr, (int32_t*)nullptr);
+        launch_mstats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)live, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
+        launch_cov_stats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)live, (const float*)w, T, Q, K, s);
+        // u_update: Mahalanobis distances + log-determinants of the clusters that moved, softmax with lambd v / Q   (:106-129)
+        dispatch_E<LaunchCovLogitsRows>(K, T, st, (const float*)w, (const float*)s, x_q, (const uint8_t*)(it == 0 ? ones : live), Q, K,
+                                        logit0);
+        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
+                           (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
+    }
+    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
+                       (int32_t*)nullptr);                                              // the last v_update
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+// ---- KL_KMEANS: HARD_KMEANS's outputs with KL centroids and divergences
+int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
+                        float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !u || !w || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "KL_KMEANS");
+    const KmeansWs o = KmeansWs::layout(p);
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_hard_kmeans_workspace_bytes")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const int Q = p.n_query, K = p.n_class, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
+    const size_t TQK = (size_t)T * Q * K;
+    float* cs = (float*)(ws + o.cs);
+    uint8_t* live = (uint8_t*)(ws + o.live);
+    float* divs = (float*)(ws + o.logit);
+    float* change = (float*)(ws + o.change);
+    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
+    for (int it = 0; it < p.iters; it++) {
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
+                           live, (float*)nullptr, (int32_t*)nullptr);
+        if (Q == kColsQ && K >= kColsChunk && g_kmeans_tile != 0) {
+            const int dtiles = (K + 63) / 64;
+            int splits = (int)((8192 + (long)T * dtiles - 1) / ((long)T * dtiles));
+            if (splits > K / (kColsWaves * kColsChunk)) splits = K / (kColsWaves * kColsChunk);
+            if (splits < 1) splits = 1;
+            const int rows_per_block = ((K + splits - 1) / splits + kColsChunk - 1) / kColsChunk * kColsChunk;
+            const int ksplits = (K + rows_per_block - 1) / rows_per_block;
+            hipLaunchKernelGGL(k_kl_centroids_cols75, dim3(task_tile_grid(dtiles, ksplits, T)), dim3(64 * kColsWaves), 0,
+                               st, (const float*)u, x_q, (const float*)cs, K, rows_per_block, w, T, dtiles, ksplits);
+        } else {
+            hipLaunchKernelGGL(k_kl_centroids, dim3((K + 63) / 64, (K + kMstatsRows - 1) / kMstatsRows, T), dim3(64), 0, st,
+                               (const float*)u, x_q, (const float*)cs, Q, K, w);
+        }
+        if (g_kmeans_tile != 0 && K >= 32 && K <= 511 && kmeans_tile_lds_raised((const void*)k_kl_divergences_tile)) {
+            const int stride = K | 1;
+            hipLaunchKernelGGL(k_kl_divergences_tile, dim3((K + kKmeansTile - 1) / kKmeansTile, T), dim3(kKmeansTileThreads),
+                               (size_t)kKmeansTile * stride * sizeof(float), st, (const float*)w, x_q, Q, K, stride, divs);
+        } else {
+            dispatch_E<LaunchKlDivergences>(K, T, st, (const float*)w, x_q, Q, K, divs);
+        }
+        hipLaunchKernelGGL(k_argmin_rows, dim3((T * Q + 255) / 256), dim3(256), 0, st, (const float*)divs, T * Q, K, preds);
+        hipLaunchKernelGGL(k_hard_assign, dim3(T), dim3(256), 0, st, (const int32_t*)preds, Q, K, u, change);
+        hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)change, N, 0, criterions + it, p.iters);
+    }
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+// ---- zero-shot, visual features ---------------------------------------------------------------------------------------
+size_t tclip_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (dim < 1 || dim > 1024) { fail(TCLIP_ERR_ARG, kDimRange); return 0; }
+    return KmeansWs::layout(*p).total;
+}
+
+int tclip_kmeans_visual_run(const tclip_problem* pp, int32_t dim, int32_t method, const float* x_q, const float* u0,
+                            float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, kDimRange);
+    if (method != TCLIP_VISUAL_SOFT_KMEANS && method != TCLIP_VISUAL_HARD_KMEANS && method != TCLIP_VISUAL_EM_GAUSSIAN)
+        return fail(TCLIP_ERR_ARG, "unknown method");
+    const Kmeans kind = method == TCLIP_VISUAL_HARD_KMEANS ? Kmeans::Hard : method == TCLIP_VISUAL_EM_GAUSSIAN ? Kmeans::EmGaussian : Kmeans::Soft;
+    if (!x_q || !u0 || !u || !w || !preds || !workspace || (kind == Kmeans::Hard && !criterions) || (kind == Kmeans::EmGaussian && !v))
+        return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "the visual k-means methods are zero-shot: n_support must be 0");
+    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_visual_workspace_bytes")) return rc;
+    return kmeans_loop(FeatureSpace{dim, true}, kind, p, x_q, u0, temperature, u, v, w, preds, criterions, (char*)workspace,
+                       (hipStream_t)stream);
+}
+
+// ---- few-shot, both feature kinds -------------------------------------------------------------------------------------
+size_t tclip_paddle_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    return PaddleWs::layout(*p, p->n_class).total;
+}
+
+int tclip_paddle_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float lambd,
+                     float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE");
+    if (int rc = check_workspace(workspace, workspace_bytes, PaddleWs::layout(p, p.n_class).total, "tclip_paddle_workspace_bytes")) return rc;
+    return paddle_loop(FeatureSpace{p.n_class, false}, p, x_q, x_s, y_s, lambd, u, v, w, preds, (char*)workspace, (hipStream_t)stream);
+}
+
+size_t tclip_paddle_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_visual_fs(p, dim, "PADDLE") != TCLIP_OK) return 0;
+    return PaddleWs::layout(*p, dim).total;
+}
+
+int tclip_paddle_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s,
+                            float lambd, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    if (int rc = check_visual_fs(pp, dim, "PADDLE")) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (int rc = check_workspace(workspace, workspace_bytes, PaddleWs::layout(p, dim).total, "tclip_paddle_visual_workspace_bytes")) return rc;
+    return paddle_loop(FeatureSpace{dim, true}, p, x_q, x_s, y_s, lambd, u, v, w, preds, (char*)workspace, (hipStream_t)stream);
+}
+
+size_t tclip_bdcspn_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    return BdcspnWs::layout(*p, p->n_class).total;
+}
+
+int tclip_bdcspn_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
+                     int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !x_s || !y_s || !prototypes || !u || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN");
+    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
+    if (int rc = check_workspace(workspace, workspace_bytes, BdcspnWs::layout(p, p.n_class).total, "tclip_bdcspn_workspace_bytes")) return rc;
+    return bdcspn_pass(FeatureSpace{p.n_class, false}, p, x_q, x_s, y_s, temp, norm_type, prototypes, u, preds, (char*)workspace,
+                       (hipStream_t)stream);
+}
+
+size_t tclip_bdcspn_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_visual_fs(p, dim, "BDCSPN") != TCLIP_OK) return 0;
+    return BdcspnWs::layout(*p, dim).total;
+}
+
+int tclip_bdcspn_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
+                            int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (int rc = check_visual_fs(pp, dim, "BDCSPN")) return rc;
+    const tclip_problem p = *pp;
+    if (!x_q || !x_s || !y_s || !prototypes || !u || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
+    if (int rc = check_workspace(workspace, workspace_bytes, BdcspnWs::layout(p, dim).total, "tclip_bdcspn_visual_workspace_bytes")) return rc;
+    return bdcspn_pass(FeatureSpace{dim, true}, p, x_q, x_s, y_s, temp, norm_type, prototypes, u, preds, (char*)workspace,
+                       (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -392,8 +392,7 @@ int tclip_alpha_tim_run(const tclip_problem* pp, const tclip_tim_params* prm, co
     const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
     if (any_alpha && !(prm->alpha_value != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
     const TimWs o = tim_ws(p);
-    if (workspace_bytes < o.total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_alpha_tim_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_alpha_tim_workspace_bytes")) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;

@@ -1,10 +1,10 @@
-// Zero-shot SOFT_KMEANS, HARD_KMEANS and EM_GAUSSIAN on VISUAL features (the reference's use_softmax_feature == False;
-// src/methods/zero_shot/{soft_kmeans,hard_kmeans,em_gaussian}.py): included at the end of tclip_kernels.hip, uses its helpers
-// (fail, check_problem, align_up, ew_grid, k_copy, k_fill, k_cluster_sizes, k_softmax, k_hard_assign, k_criterion_mean,
-// dsum_outer, outer_column_is_cascade).
+// Kernels and launchers of zero-shot SOFT_KMEANS, HARD_KMEANS and EM_GAUSSIAN on VISUAL features (the reference's
+// use_softmax_feature == False; src/methods/zero_shot/{soft_kmeans,hard_kmeans,em_gaussian}.py): included at the end of
+// tclip_kernels.hip, uses its helpers (fail, dsum_outer, dev_ceil_log2, k_probability_features).
 //
-// The loop is the one of the probability-feature path, but the clustering runs in the D-dimensional embedding space, D
-// independent of the class count K: centroids w are [T, K, D], queries z are the raw embeddings [T, Q, D].  The two kernels
+// The loop is the one of the probability-feature path (kmeans_loop, tclip_methods.inc), but the clustering runs in the
+// D-dimensional embedding space, D independent of the class count K: centroids w are [T, K, D], queries z are the raw
+// embeddings [T, Q, D].  The two kernels
 // whose work grows with D are new here; the softmax, the first-minimum one-hot, the criterion and the v term only see
 // [T, Q, K] / [T, K] tensors and are the library's own.
 //   * k_vis_dist: logit[t,q,k] = temperature * (pre * sum_d (w[t,k,d] - z[t,q,d])^2) in torch's last-dim order for every D
@@ -307,89 +307,9 @@ __global__ __launch_bounds__(256) void k_vis_prototypes(const int32_t* __restric
     }
 }
 
-static size_t visual_ws_parts(const tclip_problem& p, size_t* o_cs, size_t* o_live, size_t* o_ones, size_t* o_logit,
-                              size_t* o_change) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    *o_cs = take(T * K * 4);
-    *o_live = take(T * K);
-    *o_ones = take(T * K);
-    *o_logit = take(T * Q * K * 4);
-    *o_change = take(T * 4);
-    return o;
-}
-
 }  // namespace tclip
 
 extern "C" {
-
-size_t tclip_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (dim < 1 || dim > 1024) { fail(TCLIP_ERR_ARG, "dim must be in 1..1024"); return 0; }
-    size_t a, b, c, d, e;
-    return visual_ws_parts(*p, &a, &b, &c, &d, &e);
-}
-
-int tclip_kmeans_visual_run(const tclip_problem* pp, int32_t dim, int32_t method, const float* x_q, const float* u0,
-                            float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
-    if (method != TCLIP_VISUAL_SOFT_KMEANS && method != TCLIP_VISUAL_HARD_KMEANS && method != TCLIP_VISUAL_EM_GAUSSIAN)
-        return fail(TCLIP_ERR_ARG, "unknown method");
-    const bool hard = method == TCLIP_VISUAL_HARD_KMEANS, emg = method == TCLIP_VISUAL_EM_GAUSSIAN;
-    if (!x_q || !u0 || !u || !w || !preds || !workspace || (hard && !criterions) || (emg && !v))
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "the visual k-means methods are zero-shot: n_support must be 0");
-    size_t o_cs, o_live, o_ones, o_logit, o_change;
-    const size_t total = visual_ws_parts(p, &o_cs, &o_live, &o_ones, &o_logit, &o_change);
-    if (workspace_bytes < total) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_visual_workspace_bytes()");
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, D = dim, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
-    const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o_cs);
-    uint8_t* live = (uint8_t*)(ws + o_live);
-    uint8_t* ones = (uint8_t*)(ws + o_ones);
-    float* logit0 = (float*)(ws + o_logit);
-    float* change = (float*)(ws + o_change);
-    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, u0, u, TQK);           // u = u0 (the text-prompt init)
-    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
-    if (emg) hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    if (!hard) {
-        // w_init: every centroid = u^T z / clamp(sum u)                          (soft_kmeans.py:126-136, em_gaussian.py:145-155)
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
-                           (float*)nullptr, (int32_t*)nullptr);
-        launch_vis_mstats(st, u, x_q, cs, ones, T, Q, K, D, 0, w);
-    }
-    for (int it = 0; it < p.iters; it++) {
-        // w_update (EM_GAUSSIAN: the same pass over u yields v of the previous iteration's v_update)
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
-                           (emg && it > 0) ? v : (float*)nullptr, (int32_t*)nullptr);
-        launch_vis_mstats(st, u, x_q, cs, live, T, Q, K, D, hard ? 1 : 0, w);
-        if (hard) {
-            // u_update + hard assignment: softmax of the squared distances, first minimum; criterion, u <- one-hot
-            if (int rc = launch_vis_dist(T, st, w, x_q, ones, Q, K, D, 1.0f, 1.0f, logit0)) return rc;
-            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
-                               (const float*)nullptr, T * Q, Q, K, 0.0f, 0, 1, logit0, preds);
-            hipLaunchKernelGGL(k_hard_assign, dim3(T), dim3(256), 0, st, (const int32_t*)preds, Q, K, u, change);
-            hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)change, N, 0, criterions + it, p.iters);
-        } else {
-            // distances only for centroids that moved (all of them in the first iteration), E-step softmax
-            if (int rc = launch_vis_dist(T, st, w, x_q, it == 0 ? ones : live, Q, K, D, -0.5f, temperature, logit0)) return rc;
-            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
-                               (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
-        }
-    }
-    if (emg)      // the last v_update
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
-                           (int32_t*)nullptr);
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
-}
 
 int tclip_cluster_prototypes_visual(int32_t T, int32_t Q, int32_t K, int32_t dim, const float* x_q, const int32_t* preds,
                                     int32_t* n_clusters, int32_t* cluster_ids, float* prototypes, void* stream) {

@@ -163,12 +163,20 @@ def run_em_dirichlet_tasks(table_q, q_idx, table_s=None, s_idx=None, y_s=None, c
     return EMDirichletResult(u=u, v=v, alpha=alpha, preds=preds, criterions=crit, mm_iters=mm)
 
 
+def _kmeans_call(x_q, K, ws_query, *ws_args, iters, lambd=0, n_batches=1):
+    """What the zero-shot k-means calls share on either feature kind: the problem, the workspace query and the outputs every
+    method has.  x_q (T,Q,D), D = K for probability features -> (call, u (T,Q,K), w (T,K,D), preds (T,Q) i32)."""
+    T, Q, D = x_q.shape
+    if T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+    c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, 0, iters, 1, int(lambd), 0), ws_query, *ws_args)
+    return c, c.empty(T, Q, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
+
+
 def run_soft_kmeans(x_q, *, iters, temperature):
     """SOFT_KMEANS: x_q (T,Q,K) f32 cuda -> (u (T,Q,K), w (T,K,K), preds (T,Q) i32), cuda, not synchronised."""
     x_q = _query(x_q)
-    T, Q, K = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, 0, iters, 1, 0, 0), "tclip_soft_kmeans_workspace_bytes")
-    u, w, preds = c.empty(T, Q, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
+    c, u, w, preds = _kmeans_call(x_q, x_q.shape[2], "tclip_soft_kmeans_workspace_bytes", iters=iters)
     c.launch("tclip_soft_kmeans_run", lambda ws, n, st: (_ptr(x_q), ctypes.c_float(float(temperature)), _ptr(u), _ptr(w),
                                                          _ptr(preds), ws, n, st))
     return u, w, preds
@@ -178,9 +186,9 @@ def run_em_gaussian(x_q, *, iters, temperature, lambd):
     """EM_GAUSSIAN: x_q (T,Q,K) f32 cuda -> (u (T,Q,K), v (T,K), w (T,K,K), preds (T,Q) i32), cuda,
     not synchronised."""
     x_q = _query(x_q)
-    T, Q, K = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, 0, iters, 1, int(lambd), 0), "tclip_soft_kmeans_workspace_bytes")
-    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
+    T, _, K = x_q.shape
+    c, u, w, preds = _kmeans_call(x_q, K, "tclip_soft_kmeans_workspace_bytes", iters=iters, lambd=lambd)
+    v = c.empty(T, K)
     c.launch("tclip_em_gaussian_run", lambda ws, n, st: (_ptr(x_q), ctypes.c_float(float(temperature)), _ptr(u), _ptr(v),
                                                          _ptr(w), _ptr(preds), ws, n, st))
     return u, v, w, preds
@@ -190,29 +198,43 @@ def run_em_gaussian_cov(x_q, *, iters, lambd):
     """EM_GAUSSIAN_COV: x_q (T,Q,K) f32 cuda -> (u (T,Q,K), v (T,K), w (T,K,K), s (T,K,K), preds (T,Q) i32),
     cuda, not synchronised."""
     x_q = _query(x_q)
-    T, Q, K = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, 0, iters, 1, int(lambd), 0), "tclip_soft_kmeans_workspace_bytes")
-    u, v, w, s, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
+    T, _, K = x_q.shape
+    c, u, w, preds = _kmeans_call(x_q, K, "tclip_soft_kmeans_workspace_bytes", iters=iters, lambd=lambd)
+    v, s = c.empty(T, K), c.empty(T, K, K)
     c.launch("tclip_em_gaussian_cov_run", lambda ws, n, st: (_ptr(x_q), _ptr(u), _ptr(v), _ptr(w), _ptr(s), _ptr(preds), ws, n, st))
     return u, v, w, s, preds
 
 
+def _run_hard(entry, x_q, iters, n_batches):
+    """HARD_KMEANS and KL_KMEANS: the same arguments, workspace and outputs"""
+    x_q = _query(x_q)
+    c, u, w, preds = _kmeans_call(x_q, x_q.shape[2], "tclip_hard_kmeans_workspace_bytes", iters=iters, n_batches=n_batches)
+    crit = c.empty(n_batches, iters)
+    c.launch(entry, lambda ws, n, st: (_ptr(x_q), _ptr(u), _ptr(w), _ptr(preds), _ptr(crit), ws, n, st))
+    return u, w, preds, crit
+
+
 def run_kl_kmeans(x_q, *, iters, n_batches=1):
     """KL_KMEANS: same outputs as run_hard_kmeans."""
-    return run_hard_kmeans(x_q, iters=iters, n_batches=n_batches, _entry="tclip_kl_kmeans_run")
+    return _run_hard("tclip_kl_kmeans_run", x_q, iters, n_batches)
 
 
-def run_hard_kmeans(x_q, *, iters, n_batches=1, _entry="tclip_hard_kmeans_run"):
+def run_hard_kmeans(x_q, *, iters, n_batches=1):
     """HARD_KMEANS: x_q (T,Q,K) f32 cuda -> (u one-hot (T,Q,K), w (T,K,K), preds (T,Q) i32,
     criterions (n_batches, iters)), cuda, not synchronised."""
-    x_q = _query(x_q)
-    T, Q, K = x_q.shape
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, 0, iters, 1, 0, 0), "tclip_hard_kmeans_workspace_bytes")
-    u, w, preds, crit = c.empty(T, Q, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32), c.empty(n_batches, iters)
-    c.launch(_entry, lambda ws, n, st: (_ptr(x_q), _ptr(u), _ptr(w), _ptr(preds), _ptr(crit), ws, n, st))
-    return u, w, preds, crit
+    return _run_hard("tclip_hard_kmeans_run", x_q, iters, n_batches)
+
+
+def _run_paddle(x_q, x_s, y_s, K, iters, lambd, visual):
+    """PADDLE on rows of D elements: D = K and tclip_paddle_run for probability features, tclip_paddle_visual_run with D as its
+    first argument for visual ones."""
+    T, Q, D = x_q.shape
+    stem, dim = ("tclip_paddle_visual", (ctypes.c_int32(D),)) if visual else ("tclip_paddle", ())
+    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), stem + "_workspace_bytes", *dim)
+    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
+    c.launch(stem + "_run", lambda ws, n, st: (*dim, _ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_float(float(lambd)), _ptr(u),
+                                               _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
+    return u, v, w, preds
 
 
 def run_paddle(x_q, x_s, y_s, *, iters, lambd):
@@ -220,12 +242,7 @@ def run_paddle(x_q, x_s, y_s, *, iters, lambd):
     (u (T,Q,K), v (T,K), w (T,K,K), preds (T,Q) i32), cuda, not synchronised."""
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
-    T, Q, K = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), "tclip_paddle_workspace_bytes")
-    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
-    c.launch("tclip_paddle_run", lambda ws, n, st: (_ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_float(float(lambd)), _ptr(u),
-                                                    _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
-    return u, v, w, preds
+    return _run_paddle(x_q, x_s, y_s, x_q.shape[2], iters, lambd, visual=False)
 
 
 ENTROPIES = {"Shannon": 0, "Alpha": 1}
@@ -286,6 +303,19 @@ def argmax_rows(x):
 NORM_TYPES = {"UN": 0, "L2N": 1, "CL2N": 2}
 
 
+def _run_bdcspn(x_q, x_s, y_s, K, temp, norm_type, visual):
+    """BD-CSPN on rows of D elements: D = K and tclip_bdcspn_run for probability features, tclip_bdcspn_visual_run with D as its
+    first argument for visual ones."""
+    T, Q, D = x_q.shape
+    stem, dim = ("tclip_bdcspn_visual", (ctypes.c_int32(D),)) if visual else ("tclip_bdcspn", ())
+    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], 1, 1, 0, 0), stem + "_workspace_bytes", *dim)
+    prototypes, u, preds = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
+    c.launch(stem + "_run", lambda ws, n, st: (*dim, _ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_float(float(temp)),
+                                               ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u), _ptr(preds),
+                                               ws, n, st))
+    return prototypes, u, preds
+
+
 def run_bdcspn(x_q, x_s, y_s, *, temp, norm_type="L2N"):
     """BD-CSPN: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda ->
     (prototypes (T,K,K), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised."""
@@ -293,13 +323,7 @@ def run_bdcspn(x_q, x_s, y_s, *, temp, norm_type="L2N"):
         raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
-    T, Q, K = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], 1, 1, 0, 0), "tclip_bdcspn_workspace_bytes")
-    prototypes, u, preds = c.empty(T, K, K), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
-    c.launch("tclip_bdcspn_run", lambda ws, n, st: (_ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_float(float(temp)),
-                                                    ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u),
-                                                    _ptr(preds), ws, n, st))
-    return prototypes, u, preds
+    return _run_bdcspn(x_q, x_s, y_s, x_q.shape[2], temp, norm_type, visual=False)
 
 
 def clustering_accuracy(x_q, preds, y_q, graph_matching=True):
@@ -324,21 +348,7 @@ def clustering_accuracy(x_q, preds, y_q, graph_matching=True):
         rc = lib.tclip_cluster_prototypes(T, Q, K, _ptr(x_q), _ptr(preds), _ptr(n_clusters), _ptr(ids), _ptr(protos),
                                           ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, _stream())
         _capi.check(rc, "tclip_cluster_prototypes")
-        preds_h, nc_h = preds.cpu(), n_clusters.cpu()
-        used = max(1, min(cmax, int(nc_h.max())))          # rows of the fullest task: only those travel to the host
-        # page-locked staging buffers (torch caches them): the prototype block is the one sizeable device-to-host copy of a step
-        ids_h = torch.empty((T, used), dtype=torch.int32, pin_memory=True)
-        protos_h = torch.empty((T, used, K), dtype=torch.float32, pin_memory=True)
-        ids_h.copy_(ids[:, :used], non_blocking=True)
-        protos_h.copy_(protos[:, :used], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    y_h = y_q.reshape(T, Q).long().cpu().contiguous()
-    new_preds = torch.empty(T, Q, dtype=torch.int32)
-    acc = torch.empty(T, dtype=torch.float32)
-    rc = lib.tclip_match_clusters_host_strided(T, Q, K, _ptr(preds_h), _ptr(nc_h), _ptr(ids_h), _ptr(protos_h), _ptr(y_h),
-                                               int(bool(graph_matching)), used, _ptr(new_preds), _ptr(acc))
-    _capi.check(rc, "tclip_match_clusters_host_strided")
-    return acc, new_preds
+    return _match(lib, T, Q, K, preds, n_clusters, ids, protos, y_q, graph_matching, cmax, dev)
 
 
 VISUAL_METHODS = {"soft_kmeans": 0, "hard_kmeans": 1, "em_gaussian": 2}     # TCLIP_VISUAL_* of include/tclip.h
@@ -372,12 +382,9 @@ def _run_visual(method, x_q, u0, iters, temperature, lambd=0, n_batches=1):
     if u0.dim() != 3 or u0.shape[0] != T or u0.shape[1] != Q:
         raise ValueError("u0 must be (T,Q,K) with the T and Q of x_q")
     K = u0.shape[2]
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    p = _capi.Problem(n_batches, T // n_batches, Q, K, 0, iters, 1, int(lambd), 0)
-    c = _Call(x_q.device, p, "tclip_visual_workspace_bytes", ctypes.c_int32(D))
+    c, u, w, preds = _kmeans_call(x_q, K, "tclip_visual_workspace_bytes", ctypes.c_int32(D), iters=iters, lambd=lambd,
+                                  n_batches=n_batches)
     hard, emg = method == "hard_kmeans", method == "em_gaussian"
-    u, w, preds = c.empty(T, Q, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
     v = c.empty(T, K) if emg else None
     crit = c.empty(n_batches, max(iters, 1))[:, :iters].contiguous() if hard else None
     c.launch("tclip_kmeans_visual_run", lambda ws, n, st: (ctypes.c_int32(D), ctypes.c_int32(VISUAL_METHODS[method]), _ptr(x_q),
@@ -424,14 +431,7 @@ def run_paddle_visual(x_q, x_s, y_s, *, n_class, iters, lambd):
     tensor shape here.  No text features: the reference's text-prompt u is dead (paddle.py:183-203)."""
     x_q = _query(x_q)
     x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    T, Q, D = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), "tclip_paddle_visual_workspace_bytes",
-              ctypes.c_int32(D))
-    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
-    c.launch("tclip_paddle_visual_run", lambda ws, n, st: (ctypes.c_int32(D), _ptr(x_q), _ptr(x_s), _ptr(y_s),
-                                                           ctypes.c_float(float(lambd)), _ptr(u), _ptr(v), _ptr(w), _ptr(preds),
-                                                           ws, n, st))
-    return u, v, w, preds
+    return _run_paddle(x_q, x_s, y_s, K, iters, lambd, visual=True)
 
 
 def run_bdcspn_visual(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
@@ -441,14 +441,7 @@ def run_bdcspn_visual(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
         raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
     x_q = _query(x_q)
     x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    T, Q, D = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], 1, 1, 0, 0), "tclip_bdcspn_visual_workspace_bytes",
-              ctypes.c_int32(D))
-    prototypes, u, preds = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
-    c.launch("tclip_bdcspn_visual_run", lambda ws, n, st: (ctypes.c_int32(D), _ptr(x_q), _ptr(x_s), _ptr(y_s),
-                                                           ctypes.c_float(float(temp)), ctypes.c_int32(NORM_TYPES[norm_type]),
-                                                           _ptr(prototypes), _ptr(u), _ptr(preds), ws, n, st))
-    return prototypes, u, preds
+    return _run_bdcspn(x_q, x_s, y_s, K, temp, norm_type, visual=True)
 
 
 def _match(lib, T, Q, K, preds, n_clusters, ids, rows, y_q, graph_matching, cmax, dev):
