@@ -32,7 +32,8 @@ extern "C" {
  *    tclip_debug_set_dead_head added
  *    later, without a new number (additions only; a client that needs them looks the symbols up):
  *    tclip_visual_workspace_bytes, tclip_kmeans_visual_run, tclip_cluster_prototypes_visual, tclip_visual_init;
- *    tclip_paddle_visual_workspace_bytes, tclip_paddle_visual_run, tclip_bdcspn_visual_workspace_bytes, tclip_bdcspn_visual_run
+ *    tclip_paddle_visual_workspace_bytes, tclip_paddle_visual_run, tclip_bdcspn_visual_workspace_bytes, tclip_bdcspn_visual_run;
+ *    tclip_tim_gd_workspace_bytes, tclip_tim_gd_run
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -249,6 +250,27 @@ size_t tclip_alpha_tim_workspace_bytes(const tclip_problem* p);
 int tclip_alpha_tim_run(const tclip_problem* p, const tclip_tim_params* prm, const float* x_q, const float* x_s,
                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* TIM_GD (reference: src/methods/few_shot/tim.py:90-189) on feature rows of `dim` elements, dim independent of n_class:
+ * dim == n_class is the probability-feature case, anything else in 1..1024 the visual one (use_softmax_feature == False; the
+ * class never reads that switch and normalises nothing).  It is ALPHA_TIM with all three entropies Shannon and
+ *   - the marginal entropy -(m * log(m + 1e-12)).sum() of m = mean_q p_q (tim.py:171-172; ALPHA_TIM's has no 1e-12),
+ *   - the criterion per TASK: mean_class ||w_old - w|| (tim.py:181),
+ *   - lr = args.lr_tim, temp and loss_weights [cross-entropy, marginal entropy, conditional entropy] passed directly.
+ * Same Adam step, same closed-form gradient and the same GEMM kernels as ALPHA_TIM; like it, the entry has no bit-level
+ * target (the reference's matmuls and backward pass have no fixed operation order) and is pinned to reference-made fixtures
+ * within bounds derived from the reference's own fp32-against-fp64 gap (tests/test_gpu_tim_gd.py).  Uses n_batches,
+ * tasks_per_batch, n_query, n_class, n_support (>= 1), iters (>= 1); T = n_batches * tasks_per_batch.
+ *   x_q device [T,Q,dim] f32;  x_s device [T,S,dim] f32;  y_s device [T,S] i64 in 0..n_class-1 (a label outside that range is
+ *   never used as an index; callers reject such labels);
+ *   weights device [T,K,dim] out (after the last step);  logits_q device [T,Q,K] out and preds device [T,Q] i32 out: the query
+ *   logits of the LAST iteration's forward pass and their argmax (tim.py:189);  criterions device [iters, T] out.
+ *   workspace: tclip_tim_gd_workspace_bytes(p, dim) bytes, 256-byte aligned (0 on bad input). */
+size_t tclip_tim_gd_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_tim_gd_run(const tclip_problem* p, int32_t dim, double lr, float temp, const float loss_weights[3],
+                     const float* x_q /*[T,Q,dim]*/, const float* x_s /*[T,S,dim]*/, const int64_t* y_s /*[T,S]*/,
+                     float* weights /*[T,K,dim]*/, float* logits_q /*[T,Q,K]*/, int32_t* preds /*[T,Q]*/,
+                     float* criterions /*[iters,T]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* LAPLACIAN_SHOT on probability features (reference: src/methods/few_shot/laplacian_shot.py:66-249; feature
  * dimension = n_class).  Rows L2-normalised (norm_type 1) or left as they are (0), prototypes = support class

@@ -1,7 +1,9 @@
-// ALPHA_TIM (SURVEY.md F4; reference: src/methods/few_shot/tim.py:192-322) on probability features: included
-// at the end of tclip_kernels.hip, uses its helpers (fail, check_problem, align_up, k_support_stats, k_div_rows).
+// ALPHA_TIM (SURVEY.md F4; reference: src/methods/few_shot/tim.py:192-322) on probability features and TIM_GD (tim.py:90-189)
+// on rows of any length: included at the end of tclip_kernels.hip, uses its helpers (fail, check_problem, align_up,
+// k_support_stats, k_div_rows) and launch_vis_support_stats of tclip_visual_fs.inc.
 //
-// Per task the reference keeps one weight matrix W (K classes x D features, D = K here) and runs `iter` Adam
+// Per task the reference keeps one weight matrix W (K classes x D features; D = K for ALPHA_TIM, which this package runs on
+// probability features only, any D in 1..1024 for TIM_GD) and runs `iter` Adam
 // steps on  lw0 * CE(support) - (lw1 * H(marginal of the query predictions) - lw2 * H(query | prediction))
 // with logits T (x.w_k - |w_k|^2/2 - |x|^2/2).  Autograd is replaced by the closed-form gradient:
 //   dL/dlogit[i,k] = p_k (g_k - sum_j g_j p_j),  g = dL/dp  (softmax backward, row by row),
@@ -13,19 +15,23 @@
 
 namespace tclip {
 
-struct TimRows {            // the support rows of a task followed by its query rows
+struct TimRows {            // the support rows of a task followed by its query rows, D elements each
     const float* xs;
     const float* xq;
-    int S, Q, K;
+    int S, Q, D;
     __device__ const float* row(int t, int i) const {
-        return i < S ? xs + ((size_t)t * S + i) * K : xq + ((size_t)t * Q + (i - S)) * K;
+        return i < S ? xs + ((size_t)t * S + i) * D : xq + ((size_t)t * Q + (i - S)) * D;
     }
 };
 
+constexpr int kTimMarginalGd = 2;   // TimLoss::ent1 of TIM_GD: Shannon with the 1e-12 of tim.py:171-172 inside the logarithm
 struct TimLoss {
     float lw0, lw1, lw2, alpha;
-    int ent0, ent1, ent2;   // 0 = Shannon, 1 = Alpha
+    int ent0, ent1, ent2;   // 0 = Shannon, 1 = Alpha; ent1 also kTimMarginalGd
 };
+
+static void launch_vis_support_stats(hipStream_t st, const float* xs, const int64_t* ys, int T, int S, int K, int D, float* sup,
+                                     float* cnt);   // tclip_visual_fs.inc
 
 constexpr int kTimTile = 64;
 
@@ -41,17 +47,17 @@ __global__ void k_tim_row_sqnorm(TimRows X, int n_rows_total, float* __restrict_
     if (row >= n_rows_total) return;
     const float* x = X.row(row / R, row % R);
     float s = 0.0f;
-    for (int d = lane; d < X.K; d += 64) s = fmaf(x[d], x[d], s);
+    for (int d = lane; d < X.D; d += 64) s = fmaf(x[d], x[d], s);
     s = tim_wave_sum(s);
     if (lane == 0) xn[row] = s;
 }
 
-__global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int K, float* __restrict__ wn) {
+__global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int D, float* __restrict__ wn) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows) return;
-    const float* w = W + (size_t)row * K;
+    const float* w = W + (size_t)row * D;
     float s = 0.0f;
-    for (int d = lane; d < K; d += 64) s = fmaf(w[d], w[d], s);
+    for (int d = lane; d < D; d += 64) s = fmaf(w[d], w[d], s);
     s = tim_wave_sum(s);
     if (lane == 0) wn[row] = s;
 }
@@ -67,6 +73,8 @@ __global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int K, f
 // the operand fragments), the next slice's global loads in flight behind the MFMAs; the block's four wavefronts sit 2 x 2.
 //   kTN = false (logits):  C[m][n] = sum_k X_m[k] W_n[k]          rows of X and W contiguous along k (stored transposed)
 //   kTN = true  (dW):      C[m][n] = sum_i G[i][m] X_i[n]         both operands contiguous along the tile dimension
+// K classes and rows of X.D elements (R = S + Q rows per task): the logits are R x K over a depth of D, dW is K x D over a
+// depth of R; W and dW rows have D elements, G and the logits' rows K.  ALPHA_TIM runs it at D = K.
 // Epilogue: the logits' scaling and norms, or (dW) the column sums of G by the blocks of the first column tile.
 // TILE = 128 (2 x 2 MFMA tiles per wavefront) loses to partial tiles and to fewer blocks: K = 397 25.4, K = 1000 48.9 TFLOP/s.
 constexpr int kTimMfmaDepth = 16;    // measured at 64 x 64 tiles: depth 16 52.7, 32 45.9, 64 25.2 TFLOP/s (K = 1000, S = 4000, 4 tasks)
@@ -75,7 +83,7 @@ typedef float tim_f16x __attribute__((ext_vector_type(16)));
 // TILE = 64: one 32 x 32 MFMA tile per wavefront (more, smaller blocks: few tasks, class counts just above a multiple of 64);
 // TILE = 128: 2 x 2 MFMA tiles per wavefront (4 MFMAs per 4 LDS reads)
 template <bool kTN, int TILE>
-__global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, const float* __restrict__ Bmat /* W (logits) or G (dW) */,
+__global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, int K, const float* __restrict__ Bmat /* W (logits) or G (dW) */,
                                                        const float* __restrict__ wn, const float* __restrict__ xn, float temp,
                                                        float* __restrict__ C, float* __restrict__ cs) {
     constexpr int kPad = 1;                                          // odd row stride: the transposed stores of two depth groups hit different banks
@@ -83,8 +91,8 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, const float* _
     constexpr int PER = TILE * kTimMfmaDepth / 256;                      // floats of each operand slice a thread stages (4 or 8)
     __shared__ float As[kTimMfmaDepth][TILE + kPad];
     __shared__ float Bs[kTimMfmaDepth][TILE + kPad];
-    const int K = X.K, R = X.S + X.Q, t = blockIdx.z;
-    const int M = kTN ? K : R, N = K, D = kTN ? R : K;               // C is M x N, the contraction runs over D
+    const int F = X.D, R = X.S + X.Q, t = blockIdx.z;               // F: elements of a feature row
+    const int M = kTN ? K : R, N = kTN ? F : K, D = kTN ? R : F;     // C is M x N, the contraction runs over D
     const int m0 = blockIdx.y * TILE, n0 = blockIdx.x * TILE;
     const int id = threadIdx.x, wave = id >> 6, lane = id & 63, wm = wave >> 1, wnn = wave & 1, half = lane >> 5, li = lane & 31;
     tim_f16x acc[MI][MI];
@@ -101,9 +109,10 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, const float* _
     float a[PER], b[PER];
     // kTN: depth = id / (TILE / PER), PER consecutive tile positions; else: tile row = id / (16 / PER), PER consecutive depths
     constexpr int kThreadsPerDepth = TILE / PER, kThreadsPerRow = kTimMfmaDepth / PER;
-    // interior tiles of a problem whose rows are 16-byte aligned (K a multiple of 4: every base pointer is a 256-byte aligned
-    // workspace offset or a torch allocation) take their PER floats as 128-bit loads: a quarter of the load instructions
-    const bool vec = (K & 3) == 0 && m0 + TILE <= M && n0 + TILE <= N;      // block-uniform
+    // interior tiles of a problem whose rows are 16-byte aligned (row lengths a multiple of 4: every base pointer is a 256-byte
+    // aligned workspace offset or a torch allocation) take their PER floats as 128-bit loads: a quarter of the load instructions.
+    // The logits read rows of F elements only, dW rows of G (K elements) and of X (F elements)
+    const bool vec = (F & 3) == 0 && (!kTN || (K & 3) == 0) && m0 + TILE <= M && n0 + TILE <= N;      // block-uniform
     auto fetch = [&](int d0) {
         if (kTN) {
             const int pp = (id % kThreadsPerDepth) * PER, i = d0 + id / kThreadsPerDepth;
@@ -127,7 +136,7 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, const float* _
         } else {
             const int row = id / kThreadsPerRow, kp = (id % kThreadsPerRow) * PER;
             const float* arow = m0 + row < M ? X.row(t, m0 + row) : nullptr;
-            const float* brow = n0 + row < N ? Bmat + ((size_t)t * K + n0 + row) * K : nullptr;   // W row
+            const float* brow = n0 + row < N ? Bmat + ((size_t)t * K + n0 + row) * F : nullptr;   // W row
             if (vec && d0 + kTimMfmaDepth <= D) {
 #pragma unroll
                 for (int j = 0; j < PER; j += 4) {
@@ -197,7 +206,7 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, const float* _
                 const int m = m0 + wm * (TILE / 2) + i * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
                 if (m >= M) continue;
                 const float v = acc[i][j][r];
-                if (kTN) C[((size_t)t * K + m) * K + n] = v;
+                if (kTN) C[((size_t)t * K + m) * F + n] = v;
                 else C[((size_t)t * R + m) * K + n] = temp * ((v - 0.5f * wnv) - 0.5f * xn[(size_t)t * R + m]);
             }
         }
@@ -285,7 +294,8 @@ __global__ void k_tim_grad(float* __restrict__ P, const int64_t* __restrict__ ys
         if (k < K) {
             const float pk = p[k], mk = m[k];
             // -lw1 * d q_ent / d p   (through the mean over the Q rows)
-            const float gm = c.ent1 == 0 ? (logf(mk) + 1.0f) : a * powf(mk, am1) / am1;
+            const float gm = c.ent1 == 0 ? (logf(mk) + 1.0f)
+                           : c.ent1 == kTimMarginalGd ? (logf(mk + 1e-12f) + mk / (mk + 1e-12f)) : a * powf(mk, am1) / am1;
             // +lw2 * d q_cond_ent / d p
             const float pe = pk + 1e-12f;
             const float gc = c.ent2 == 0 ? -(logf(pe) + pk / pe) : -a * powf(pe, am1) / am1;
@@ -303,14 +313,14 @@ __global__ void k_tim_grad(float* __restrict__ P, const int64_t* __restrict__ ys
 // torch.optim.Adam, single-tensor CPU path (betas 0.9 / 0.999, eps 1e-8, no weight decay): one wavefront per weight
 // row; also |w_k|^2 for the next logits and ||w_old_k - w_k|| for the logged criterion (tim.py:313-314).
 __global__ void k_tim_adam(float* __restrict__ W, float* __restrict__ M, float* __restrict__ V, const float* __restrict__ dW,
-                           const float* __restrict__ cs, int n_rows, int K, float temp, float neg_step, float bc2_sqrt,
+                           const float* __restrict__ cs, int n_rows, int D, float temp, float neg_step, float bc2_sqrt,
                            float* __restrict__ wn, float* __restrict__ moved) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows) return;
-    const size_t base = (size_t)row * K;
+    const size_t base = (size_t)row * D;
     const float c = cs[row];
     float n2 = 0.0f, d2 = 0.0f;
-    for (int d = lane; d < K; d += 64) {
+    for (int d = lane; d < D; d += 64) {
         const float w = W[base + d];
         const float g = temp * (dW[base + d] - c * w);
         const float m = M[base + d] + 0.1f * (g - M[base + d]);                 // exp_avg.lerp_(grad, 1 - beta1)
@@ -332,7 +342,8 @@ __global__ void k_tim_adam(float* __restrict__ W, float* __restrict__ M, float* 
     }
 }
 
-// criterion of one batch: the mean over its tasks and classes of the row displacements (fixed-order tree).
+// criterion of one batch (ALPHA_TIM: n = its tasks x classes) or of one task (TIM_GD: n = its classes): the mean of the
+// block's n row displacements (fixed-order tree).
 __global__ void k_tim_criterion(const float* __restrict__ moved, int n, float* __restrict__ out, int stride) {
     __shared__ float part[256];
     const float* m = moved + (size_t)blockIdx.x * n;
@@ -348,24 +359,90 @@ __global__ void k_tim_criterion(const float* __restrict__ moved, int n, float* _
 }
 
 struct TimWs { size_t sup, cnt, P, xn, wn, marg, cs, dW, M, V, moved, total; };
-static TimWs tim_ws(const tclip_problem& p) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, R = (size_t)p.n_support + p.n_query;
+static TimWs tim_ws(const tclip_problem& p, int dim) {
+    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, R = (size_t)p.n_support + p.n_query, D = dim;
     TimWs w;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    w.sup = take(T * K * K * 4);
+    w.sup = take(T * K * D * 4);
     w.cnt = take(T * K * 4);
     w.P = take(T * R * K * 4);
     w.xn = take(T * R * 4);
     w.wn = take(T * K * 4);
     w.marg = take(T * K * 4);
     w.cs = take(T * K * 4);
-    w.dW = take(T * K * K * 4);
-    w.M = take(T * K * K * 4);
-    w.V = take(T * K * K * 4);
+    w.dW = take(T * K * D * 4);
+    w.M = take(T * K * D * 4);
+    w.V = take(T * K * D * 4);
     w.moved = take(T * K * 4);
     w.total = o;
     return w;
+}
+
+// The Adam loop of both methods on rows of D elements.  per_task = false (ALPHA_TIM): criterions [n_batches, iters], the mean over a
+// batch's tasks and classes; per_task = true (TIM_GD, tim.py:181): criterions [iters, T], the mean over a task's classes.
+static int tim_loop(const tclip_problem& p, int D, double lr, float temp, const TimLoss& loss, bool per_task, const float* x_q,
+                    const float* x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                    char* ws, hipStream_t st) {
+    const TimWs o = tim_ws(p, D);
+    const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
+    const int TR = T * R;
+    float* sup = (float*)(ws + o.sup);
+    float* cnt = (float*)(ws + o.cnt);
+    float* P = (float*)(ws + o.P);
+    float* xn = (float*)(ws + o.xn);
+    float* wn = (float*)(ws + o.wn);
+    float* marg = (float*)(ws + o.marg);
+    float* cs = (float*)(ws + o.cs);
+    float* dW = (float*)(ws + o.dW);
+    float* M = (float*)(ws + o.M);
+    float* V = (float*)(ws + o.V);
+    float* moved = (float*)(ws + o.moved);
+    const TimRows X{x_s, x_q, S, Q, D};
+    const int tiles_k = (K + kTimTile - 1) / kTimTile, tiles_r = (R + kTimTile - 1) / kTimTile, tiles_d = (D + kTimTile - 1) / kTimTile;
+    // init_weights (tim.py:115-134, :218-238): the class means of the support set; Adam state zero
+    if (D == K)
+        hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(x_s), y_s, S, K, 0, sup, cnt);
+    else
+        launch_vis_support_stats(st, x_s, y_s, T, S, K, D, sup, cnt);
+    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
+                       (size_t)TK * D, D, weights);
+    TCLIP_HIP(hipMemsetAsync(M, 0, (size_t)TK * D * 4, st));
+    TCLIP_HIP(hipMemsetAsync(V, 0, (size_t)TK * D * 4, st));
+    hipLaunchKernelGGL(k_tim_row_sqnorm, dim3((TR + 3) / 4), dim3(256), 0, st, X, TR, xn);
+    hipLaunchKernelGGL(k_tim_w_sqnorm, dim3((TK + 3) / 4), dim3(256), 0, st, (const float*)weights, TK, D, wn);
+    for (int it = 0; it < p.iters; it++) {
+        const bool last = it + 1 == p.iters;
+        hipLaunchKernelGGL((k_tim_gemm_mfma<false, kTimTile>), dim3(tiles_k, tiles_r, T), dim3(256), 0, st, X, K, (const float*)weights,
+                           (const float*)wn, (const float*)xn, temp, P, (float*)nullptr);
+        hipLaunchKernelGGL(k_tim_softmax, dim3((TR + 3) / 4), dim3(256), 0, st, P, TR, S, Q, K, last ? logits_q : (float*)nullptr,
+                           preds);
+        hipLaunchKernelGGL(k_tim_marginal, dim3((K + 127) / 128, T), dim3(128), 0, st, (const float*)P, S, Q, K, marg);
+        hipLaunchKernelGGL(k_tim_grad, dim3((TR + 3) / 4), dim3(256), 0, st, P, y_s, (const float*)marg, TR, S, Q, K, loss);
+        hipLaunchKernelGGL((k_tim_gemm_mfma<true, kTimTile>), dim3(tiles_d, tiles_k, T), dim3(256), 0, st, X, K, (const float*)P,
+                           (const float*)nullptr, (const float*)nullptr, 0.0f, dW, cs);
+        // Adam's step scalars, in double as torch computes them (torch/optim/adam.py, _single_tensor_adam)
+        const double step = it + 1, bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
+        hipLaunchKernelGGL(k_tim_adam, dim3((TK + 3) / 4), dim3(256), 0, st, weights, M, V, (const float*)dW, (const float*)cs, TK, D,
+                           temp, (float)(-(lr / bc1)), (float)sqrt(bc2), wn, moved);
+        if (per_task)
+            hipLaunchKernelGGL(k_tim_criterion, dim3(T), dim3(256), 0, st, (const float*)moved, K, criterions + (size_t)it * T, 1);
+        else
+            hipLaunchKernelGGL(k_tim_criterion, dim3(B), dim3(256), 0, st, (const float*)moved, N * K, criterions + it, p.iters);
+    }
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+// what tclip_tim_gd_run and its workspace query check of the problem
+static int check_tim_gd(const tclip_problem* p, int32_t dim) {
+    if (int rc = check_problem(p)) return rc;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
+    if (p->iters < 1) return fail(TCLIP_ERR_ARG, "TIM_GD needs iters >= 1 (the accuracy is read from the last iteration's logits)");
+    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "TIM_GD is a few-shot method: n_support must be positive");
+    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)p->n_support + p->n_query;
+    if (T * R > 0x7fffffffu) return fail(TCLIP_ERR_ARG, "TIM_GD: tasks * (n_support + n_query) must fit in int32");
+    return TCLIP_OK;
 }
 
 }  // namespace tclip
@@ -374,7 +451,7 @@ extern "C" {
 
 size_t tclip_alpha_tim_workspace_bytes(const tclip_problem* p) {
     if (check_problem(p) != TCLIP_OK) return 0;
-    return tim_ws(*p).total;
+    return tim_ws(*p, p->n_class).total;
 }
 
 int tclip_alpha_tim_run(const tclip_problem* pp, const tclip_tim_params* prm, const float* x_q, const float* x_s,
@@ -391,53 +468,30 @@ int tclip_alpha_tim_run(const tclip_problem* pp, const tclip_tim_params* prm, co
             return fail(TCLIP_ERR_ARG, "entropies must be TCLIP_TIM_SHANNON or TCLIP_TIM_ALPHA");
     const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
     if (any_alpha && !(prm->alpha_value != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
-    const TimWs o = tim_ws(p);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_alpha_tim_workspace_bytes")) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
-    const int TR = T * R;
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* P = (float*)(ws + o.P);
-    float* xn = (float*)(ws + o.xn);
-    float* wn = (float*)(ws + o.wn);
-    float* marg = (float*)(ws + o.marg);
-    float* cs = (float*)(ws + o.cs);
-    float* dW = (float*)(ws + o.dW);
-    float* M = (float*)(ws + o.M);
-    float* V = (float*)(ws + o.V);
-    float* moved = (float*)(ws + o.moved);
-    const TimRows X{x_s, x_q, S, Q, K};
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, p.n_class).total, "tclip_alpha_tim_workspace_bytes")) return rc;
     const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], prm->alpha_value,
                        prm->entropies[0], prm->entropies[1], prm->entropies[2]};
-    const int tiles_k = (K + kTimTile - 1) / kTimTile, tiles_r = (R + kTimTile - 1) / kTimTile;
-    // init_weights (tim.py:218-238): the class means of the support set; Adam state zero
-    hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(x_s), y_s, S, K, 0, sup, cnt);
-    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * K)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
-                       (size_t)TK * K, K, weights);
-    TCLIP_HIP(hipMemsetAsync(M, 0, (size_t)TK * K * 4, st));
-    TCLIP_HIP(hipMemsetAsync(V, 0, (size_t)TK * K * 4, st));
-    hipLaunchKernelGGL(k_tim_row_sqnorm, dim3((TR + 3) / 4), dim3(256), 0, st, X, TR, xn);
-    hipLaunchKernelGGL(k_tim_w_sqnorm, dim3((TK + 3) / 4), dim3(256), 0, st, (const float*)weights, TK, K, wn);
-    for (int it = 0; it < p.iters; it++) {
-        const bool last = it + 1 == p.iters;
-        hipLaunchKernelGGL((k_tim_gemm_mfma<false, kTimTile>), dim3(tiles_k, tiles_r, T), dim3(256), 0, st, X, (const float*)weights,
-                           (const float*)wn, (const float*)xn, prm->temp, P, (float*)nullptr);
-        hipLaunchKernelGGL(k_tim_softmax, dim3((TR + 3) / 4), dim3(256), 0, st, P, TR, S, Q, K, last ? logits_q : (float*)nullptr,
-                           preds);
-        hipLaunchKernelGGL(k_tim_marginal, dim3((K + 127) / 128, T), dim3(128), 0, st, (const float*)P, S, Q, K, marg);
-        hipLaunchKernelGGL(k_tim_grad, dim3((TR + 3) / 4), dim3(256), 0, st, P, y_s, (const float*)marg, TR, S, Q, K, loss);
-        hipLaunchKernelGGL((k_tim_gemm_mfma<true, kTimTile>), dim3(tiles_k, tiles_k, T), dim3(256), 0, st, X, (const float*)P,
-                           (const float*)nullptr, (const float*)nullptr, 0.0f, dW, cs);
-        // Adam's step scalars, in double as torch computes them (torch/optim/adam.py, _single_tensor_adam)
-        const double step = it + 1, bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
-        hipLaunchKernelGGL(k_tim_adam, dim3((TK + 3) / 4), dim3(256), 0, st, weights, M, V, (const float*)dW, (const float*)cs, TK, K,
-                           prm->temp, (float)(-(prm->lr / bc1)), (float)sqrt(bc2), wn, moved);
-        hipLaunchKernelGGL(k_tim_criterion, dim3(B), dim3(256), 0, st, (const float*)moved, N * K, criterions + it, p.iters);
-    }
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
+    return tim_loop(p, p.n_class, prm->lr, prm->temp, loss, false, x_q, x_s, y_s, weights, logits_q, preds, criterions,
+                    (char*)workspace, (hipStream_t)stream);
+}
+
+size_t tclip_tim_gd_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_tim_gd(p, dim) != TCLIP_OK) return 0;
+    return tim_ws(*p, dim).total;
+}
+
+int tclip_tim_gd_run(const tclip_problem* pp, int32_t dim, double lr, float temp, const float loss_weights[3], const float* x_q,
+                     const float* x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_tim_gd(pp, dim)) return rc;
+    const tclip_problem p = *pp;
+    if (!loss_weights || !x_q || !x_s || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, dim).total, "tclip_tim_gd_workspace_bytes")) return rc;
+    // tim.py:166-175: all three entropies Shannon, the marginal one with 1e-12 inside its logarithm
+    const TimLoss loss{loss_weights[0], loss_weights[1], loss_weights[2], 0.0f, TCLIP_TIM_SHANNON, kTimMarginalGd, TCLIP_TIM_SHANNON};
+    return tim_loop(p, dim, lr, temp, loss, true, x_q, x_s, y_s, weights, logits_q, preds, criterions, (char*)workspace,
+                    (hipStream_t)stream);
 }
 
 }  // extern "C"

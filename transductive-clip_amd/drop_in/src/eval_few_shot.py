@@ -11,7 +11,7 @@ from src.methods.few_shot.em_dirichlet import EM_DIRICHLET
 from src.methods.few_shot.hard_em_dirichlet import HARD_EM_DIRICHLET
 from src.methods.few_shot.paddle import PADDLE
 from src.methods.few_shot.bdcspn import BDCSPN
-from src.methods.few_shot.tim import ALPHA_TIM
+from src.methods.few_shot.tim import ALPHA_TIM, TIM_GD
 from src.methods.few_shot.laplacian_shot import LAPLACIAN_SHOT
 from src.sampler_few_shot import CategoriesSampler_few_shot, SamplerQuery_few_shot, SamplerSupport_few_shot
 from src.task_generator_few_shot import label_permutation, relabel
@@ -58,7 +58,8 @@ def relabel_indices(y_s, y_q, n_class):
 
 
 _METHODS = {'EM_DIRICHLET': EM_DIRICHLET, 'HARD_EM_DIRICHLET': HARD_EM_DIRICHLET, 'PADDLE': PADDLE, 'BDCSPN': BDCSPN,
-            'ALPHA_TIM': ALPHA_TIM, 'LAPLACIAN_SHOT': LAPLACIAN_SHOT}
+            'ALPHA_TIM': ALPHA_TIM, 'LAPLACIAN_SHOT': LAPLACIAN_SHOT,
+            'TIM-GD': TIM_GD, 'TIM_GD': TIM_GD}      # tim.yaml's name_method is 'TIM-GD'
 
 
 class Evaluator_few_shot:
@@ -105,6 +106,7 @@ class Evaluator_few_shot:
         return cls(model=model, device=device, log_file=log_file, args=args)
 
     # ---- validation-tuned parameter (reference: eval_few_shot.py:130-187)
+    # TIM-GD has no branch in the reference's set_value_opt_param: nothing of it is tuned
     _TUNED = {'LAPLACIAN_SHOT': 'lmd', 'ALPHA_TIM': 'alpha_value', 'PADDLE': 'lambd', 'BDCSPN': 'temp'}
 
     def set_value_opt_param(self, opt_param):
@@ -170,7 +172,7 @@ class Evaluator_few_shot:
         Q = q_idx.shape[2]
         mine = sharding.my_batches(n_batches)
         # the feature width and the class count: one number on softmax features, the embedding length D and args.n_class on
-        # visual features (use_softmax_feature: False; PADDLE and BDCSPN run there, the labels are not re-indexed)
+        # visual features (use_softmax_feature: False; PADDLE, BDCSPN and TIM-GD run there, the labels are not re-indexed)
         W = tab_q.shape[1]
         K = W if a.use_softmax_feature else int(a.n_class)
         # The parameter tuned on the validation split, when the test split is evaluated.  The reference builds the

@@ -1,8 +1,10 @@
-"""Few-shot ALPHA_TIM on probability features, drop-in for the reference's src/methods/few_shot/tim.py:192-322
-(SURVEY.md F4).  Same constructor / run_task / logs contract; the `iter` Adam steps run in libtclip.so
-(tclip_alpha_tim_run) with the gradient in closed form instead of autograd.  The reference's MKL matmuls and autograd
-accumulation order leave no bit-level target, so this class is pinned to the reference within a float tolerance
-(tests/test_alpha_tim.py).  TIM_GD (tim.py:91-189) is not reachable from the reference's evaluator and is not provided."""
+"""Few-shot TIM_GD and ALPHA_TIM, drop-in for the reference's src/methods/few_shot/tim.py: BASE, TIM_GD
+(tim.py:90-189) and ALPHA_TIM (tim.py:192-322).  Same constructor / run_task / logs contract; the `iter` Adam steps run in
+libtclip.so (tclip_tim_gd_run, tclip_alpha_tim_run) with the gradient in closed form instead of autograd.  The reference's
+MKL matmuls and autograd accumulation order leave no bit-level target, so both classes are pinned to the reference within a
+float tolerance (tests/test_alpha_tim.py, tests/test_gpu_tim_gd.py).  TIM_GD never reads use_softmax_feature and normalises
+nothing: it runs on probability features and on D-dim embeddings alike, the class count being args.num_classes_test.
+ALPHA_TIM takes probability features only."""
 import time
 
 import torch
@@ -13,6 +15,42 @@ from tclip_amd import engine
 
 class BASE(FewShotMixin, EMDirichletBase):
     FEW_SHOT = True
+
+
+class TIM_GD(BASE):
+    BANNER = "TIM"
+
+    def __init__(self, model, device, log_file, args):
+        if not hasattr(args, "iter_mm"):
+            args.iter_mm = 0          # tim.yaml has no iter_mm
+        if not hasattr(args, "k_eff"):
+            args.k_eff = 5            # only feeds the unused EM-Dirichlet lambd of the shared base
+        super().__init__(model=model, device=device, log_file=log_file, args=args)
+        self.loss_weights = list(args.loss_weights)      # tim.py:29 (.copy())
+        self.temp = args.temp
+        self.lr = float(args.lr_tim)                     # tim.py:94
+
+    def run_method(self, support, query, y_s, y_q, n_batches=1):
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise RuntimeError("TIM_GD on MI355X needs device='cuda': there is no CPU fallback in this package")
+        self.logger.info(" ==> Executing TIM with T = {}".format(self.args.T))
+        n_task = query.shape[0]
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        # rows of D = query.shape[2] elements, D = n_class on probability features and the embedding length otherwise
+        self.weights, self.logits_q, self.preds, crit = engine.run_tim_gd(
+            query, support, y_s, n_class=self.args.num_classes_test, iters=self.iter, temp=self.temp, lr=self.lr,
+            loss_weights=self.loss_weights, n_batches=n_batches)
+        torch.cuda.synchronize(dev)
+        total = time.time() - t0
+        for i in range(self.iter):
+            # cumulative wall time per iteration over n_task (tim.py:184-186)
+            self.timestamps.append(total * (i + 1) / max(self.iter, 1) / n_task)
+        crit = crit.cpu().numpy()                        # (iter, n_task): mean_class ||w_old - w|| of every task (tim.py:181)
+        self.criterions_per_task = crit
+        self.criterions = list(crit)
+        self.compute_acc(y_q=y_q)                        # argmax of the last iteration's query logits (tim.py:189)
 
 
 class ALPHA_TIM(BASE):

@@ -21,9 +21,9 @@ the command line wins over all three files (values are literal-eval'ed, an overr
 the value it replaces).  Without a config directory the built-in copies of the reference's defaults below are
 used the same way.  Test-split runs of a tunable few-shot method (PADDLE, BDCSPN) need the validation sweep
 file under <results-root>/results_few_shot/val/, exactly as the reference does; runs with `used_test_set val` append to it.
-With `use_softmax_feature False` the zero-shot k-means family and CLIP (with --text-features) and the few-shot PADDLE and
-BDCSPN (no text features needed) run on the raw embeddings of <split>_visual_<backbone>.plk; the class count is read from
-the labels and the sweep and result files carry `_visual` in their names.
+With `use_softmax_feature False` the zero-shot k-means family and CLIP (with --text-features) and the few-shot PADDLE,
+BDCSPN and TIM-GD (`method tim`; no text features needed) run on the raw embeddings of <split>_visual_<backbone>.plk; the
+class count is read from the labels and the sweep and result files carry `_visual` in their names.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse
@@ -59,6 +59,9 @@ METHOD_DEFAULTS = {
     "laplacian_shot": dict(name_method="LAPLACIAN_SHOT", knn=3, lmd=0.7, norm_type="L2N", iter=20, temp=30, tunable=True),
     "alpha_tim": dict(name_method="ALPHA_TIM", temp=15, loss_weights=[1.0, 1.0, 1.0], lr_alpha_tim=1e-4, iter=1000,
                       entropies=["Shannon", "Alpha", "Alpha"], alpha_value=7.0, acc_clustering=False, tunable=True),
+    # tim.yaml says tunable: True, but the reference's set_value_opt_param has no branch for TIM-GD: nothing is tuned
+    "tim": dict(name_method="TIM-GD", temp=15, loss_weights=[1.0, 0.3, 1.0], lr_tim=1e-4, iter=2000, alpha=1.0,
+                acc_clustering=False, tunable=False),
 }
 
 

@@ -270,6 +270,29 @@ def run_alpha_tim(x_q, x_s, y_s, *, iters, temp, lr, alpha_value, loss_weights=(
     return weights, logits_q, preds, crit
 
 
+def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0), n_batches=1):
+    """TIM_GD on either feature kind: x_q (T,Q,D), x_s (T,S,D) f32 cuda with any D in 1..1024 (D = n_class: probability
+    features), y_s (T,S) int64 cuda with labels in 0..n_class-1 -> (weights (T,K,D), logits_q (T,Q,K) of the last iteration's
+    forward pass, preds (T,Q) i32 = their argmax, criterions (iters, T): one value per step and TASK), cuda, not synchronised.
+    K = n_class cannot be read off a tensor shape here.  Tasks never interact, so n_batches only has to divide T."""
+    x_q = _query(x_q)
+    if x_s.dim() != 3 or x_s.shape[1] < 1:
+        raise ValueError("TIM_GD is a few-shot method: x_s must be (T,S,D) with n_support = S positive")
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    T, Q, D = x_q.shape
+    if T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+    dim = ctypes.c_int32(D)
+    lw = (ctypes.c_float * 3)(*[float(w) for w in loss_weights])
+    c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, x_s.shape[1], iters, 1, 0, 0),
+              "tclip_tim_gd_workspace_bytes", dim)
+    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(iters, T)
+    c.launch("tclip_tim_gd_run", lambda ws, n, st: (dim, ctypes.c_double(float(lr)), ctypes.c_float(float(temp)), lw, _ptr(x_q),
+                                                    _ptr(x_s), _ptr(y_s), _ptr(weights), _ptr(logits_q), _ptr(preds), _ptr(crit),
+                                                    ws, n, st))
+    return weights, logits_q, preds, crit
+
+
 def run_laplacian_shot(x_q, x_s, y_s, *, iters, knn, lmd, norm_type="L2N"):
     """LAPLACIAN_SHOT: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda -> (unary (T,Q,K), neighbours (T,Q,knn-1) i32,
     preds_iter (T,iters,Q) i32, energies (T,iters) f64), cuda, not synchronised."""

@@ -26,22 +26,27 @@ def my_batches(n_batches, rank=None, world_size=None):
 # methods whose engine call keeps per-batch records besides predictions and accuracies
 _PER_BATCH_RECORDS = {'EM_DIRICHLET': ('criterions', 'mm_iters'), 'HARD_EM_DIRICHLET': ('criterions', 'mm_iters'),
                       'ALPHA_TIM': ('criterions',)}
+# TIM-GD logs one criterion per step and TASK (tim.py:181): its `criterions` rows are (iter, N) per batch
+_PER_TASK_CRITERIONS = ('TIM-GD', 'TIM_GD')
 
 
 def method_parts(args, method, logs, n_local, N, Q, dev):
     """This rank's results of one method run over `n_local` batches of N tasks, as the parts gather_packed moves
     (SURVEY.md section 8e): `preds` (N*Q) int32 - the class assigned to every query, after the cluster-to-class
     matching for the zero-shot clustering methods, `acc` (N) f32, and for the EM-Dirichlet classes / ALPHA_TIM the
-    per-batch `criterions` (iter) f32 and `mm_iters` (iter) int32.  method=None: a rank without a batch (zero rows of
-    the same widths)."""
+    per-batch `criterions` (iter) f32 and `mm_iters` (iter) int32; for TIM-GD the per-task `criterions` (iter, N) f32.
+    method=None: a rank without a batch (zero rows of the same widths)."""
     records = _PER_BATCH_RECORDS.get(getattr(args, 'name_method', None), ())
     iters = int(getattr(args, 'iter', 0))
+    per_task = getattr(args, 'name_method', None) in _PER_TASK_CRITERIONS
     if method is None:
         parts = {'preds': torch.zeros(0, N * Q, dtype=torch.int32), 'acc': torch.zeros(0, N)}
         if 'criterions' in records:
             parts['criterions'] = torch.zeros(0, iters)
         if 'mm_iters' in records:
             parts['mm_iters'] = torch.zeros(0, iters, dtype=torch.int32)
+        if per_task:
+            parts['criterions'] = torch.zeros(0, iters, N)
     else:
         p = getattr(method, 'matched_preds', None)
         if p is None:
@@ -52,6 +57,9 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
             parts['criterions'] = torch.as_tensor(method.criterions_per_batch, dtype=torch.float32).view(n_local, iters)
         if 'mm_iters' in records:
             parts['mm_iters'] = torch.as_tensor(method.mm_iters, dtype=torch.int32).view(n_local, iters)
+        if per_task:        # (iter, n_local * N) -> one (iter, N) block per batch
+            crit = torch.as_tensor(method.criterions_per_task, dtype=torch.float32)
+            parts['criterions'] = crit.view(iters, n_local, N).permute(1, 0, 2).contiguous()
     return {k: v.to(dev) for k, v in parts.items()}
 
 
