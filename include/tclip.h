@@ -33,7 +33,9 @@ extern "C" {
  *    later, without a new number (additions only; a client that needs them looks the symbols up):
  *    tclip_visual_workspace_bytes, tclip_kmeans_visual_run, tclip_cluster_prototypes_visual, tclip_visual_init;
  *    tclip_paddle_visual_workspace_bytes, tclip_paddle_visual_run, tclip_bdcspn_visual_workspace_bytes, tclip_bdcspn_visual_run;
- *    tclip_tim_gd_workspace_bytes, tclip_tim_gd_run
+ *    tclip_tim_gd_workspace_bytes, tclip_tim_gd_run;
+ *    tclip_alpha_tim_visual_workspace_bytes, tclip_alpha_tim_visual_run, tclip_laplacian_shot_visual_workspace_bytes,
+ *    tclip_laplacian_shot_visual_run
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -251,6 +253,22 @@ int tclip_alpha_tim_run(const tclip_problem* p, const tclip_tim_params* prm, con
                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ALPHA_TIM on feature rows of `dim` elements, dim independent of n_class (visual features, use_softmax_feature == False; the
+ * reference's class never reads that switch and normalises nothing): the loss, the Adam step, the kernels and the per-batch
+ * criterion of tclip_alpha_tim_run with W [K, dim] instead of [K, K].  dim in 1..1024, n_class in 2..1024, n_support >= 1,
+ * iters >= 1; at dim == n_class the results are those of tclip_alpha_tim_run, bit for bit.  Pinned to reference-made fixtures
+ * within bounds derived from the reference's own fp32-against-fp64 gap (tests/test_gpu_visual_alpha_tim.py).
+ *   x_q device [T,Q,dim] f32;  x_s device [T,S,dim] f32;  y_s device [T,S] i64 in 0..n_class-1 (a label outside that range is
+ *   never used as an index and joins no class; callers reject such labels);
+ *   weights device [T,K,dim] out;  logits_q device [T,Q,K] out, preds device [T,Q] i32 out (last iteration's forward pass);
+ *   criterions device [n_batches, iters] out;  workspace: tclip_alpha_tim_visual_workspace_bytes(p, dim) bytes, 256-byte
+ *   aligned (0 on bad input). */
+size_t tclip_alpha_tim_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_alpha_tim_visual_run(const tclip_problem* p, int32_t dim, const tclip_tim_params* prm, const float* x_q /*[T,Q,dim]*/,
+                               const float* x_s /*[T,S,dim]*/, const int64_t* y_s /*[T,S]*/, float* weights /*[T,K,dim]*/,
+                               float* logits_q /*[T,Q,K]*/, int32_t* preds /*[T,Q]*/, float* criterions /*[n_batches,iters]*/,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* TIM_GD (reference: src/methods/few_shot/tim.py:90-189) on feature rows of `dim` elements, dim independent of n_class:
  * dim == n_class is the probability-feature case, anything else in 1..1024 the visual one (use_softmax_feature == False; the
  * class never reads that switch and normalises nothing).  It is ALPHA_TIM with all three entropies Shannon and
@@ -287,6 +305,24 @@ size_t tclip_laplacian_shot_workspace_bytes(const tclip_problem* p);
 int tclip_laplacian_shot_run(const tclip_problem* p, const float* x_q, const float* x_s, const int64_t* y_s, int32_t knn,
                              double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter,
                              double* energies, void* workspace, size_t workspace_bytes, void* stream);
+
+/* LAPLACIAN_SHOT on feature rows of `dim` elements, dim independent of n_class (visual features; the reference's class never
+ * reads use_softmax_feature: it normalises rows, takes class means, squared distances and a kNN graph, all defined for any row
+ * length).  Rows, prototypes [T,K,dim] and the kNN distances live in dim, unary, Y and the bound updates in n_class.  The
+ * queries' pairwise squared distances come from a kernel of their own (k_lshot_pairdist: a [T,Q,Q] fp64 table in the
+ * workspace, many workgroups per task), the selection, the updates and the freeze rule are tclip_laplacian_shot_run's.
+ * dim in 1..1024, n_class in 2..1024, n_support >= 1, n_query <= 1024, knn in 2..n_query, norm_type 0 or 1, iters >= 1; at
+ * dim == n_class the results are those of tclip_laplacian_shot_run, bit for bit.
+ *   x_q device [T,Q,dim] f32;  x_s device [T,S,dim] f32;  y_s device [T,S] i64 in 0..n_class-1 (a label outside that range is
+ *   never used as an index and joins no class; callers reject such labels);
+ *   unary device [T,Q,K] f32 out;  neighbours device [T,Q,knn-1] i32 out;  preds_iter device [T,iters,Q] i32 out;
+ *   energies device [T,iters] f64 out;  workspace: tclip_laplacian_shot_visual_workspace_bytes(p, dim) bytes, 256-byte aligned
+ *   (0 on bad input). */
+size_t tclip_laplacian_shot_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_laplacian_shot_visual_run(const tclip_problem* p, int32_t dim, const float* x_q /*[T,Q,dim]*/, const float* x_s /*[T,S,dim]*/,
+                                    const int64_t* y_s /*[T,S]*/, int32_t knn, double lmd, int32_t norm_type,
+                                    float* unary /*[T,Q,K]*/, int32_t* neighbours /*[T,Q,knn-1]*/, int32_t* preds_iter /*[T,iters,Q]*/,
+                                    double* energies /*[T,iters]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Inductive zero-shot CLIP on probability features (reference: src/methods/zero_shot/inductive_clip.py:45-49,
  * 112-126): the prediction is the arg-max of each query's probability vector, no adaptation.

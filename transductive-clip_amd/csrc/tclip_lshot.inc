@@ -1,5 +1,9 @@
-// LAPLACIAN_SHOT (SURVEY.md F4; reference: src/methods/few_shot/laplacian_shot.py) on probability features: included at
-// the end of tclip_kernels.hip, uses its helpers (fail, check_problem, align_up, k_support_stats, k_div_rows).
+// LAPLACIAN_SHOT (SURVEY.md F4; reference: src/methods/few_shot/laplacian_shot.py) on rows of any length: included at
+// the end of tclip_kernels.hip after tclip_tim.inc, uses its helpers (fail, check_problem, align_up, k_support_stats, k_div_rows)
+// and launch_vis_support_stats of tclip_visual_fs.inc.  A feature row has D elements, D carried separately from the class
+// count K: rows, prototypes and the kNN distances live in D, the unary term, Y and everything after the kNN step in K.
+// tclip_laplacian_shot_run is the probability-feature entry (D = K, distances inside k_lshot_task as before),
+// tclip_laplacian_shot_visual_run the one for D-dim embeddings (any D in 1..1024; distances by k_lshot_pairdist).
 //
 // Per task: L2-normalised features, prototypes = support class means, unary[q][k] = ||proto_k - z_q||^2, a kNN graph
 // over the task's queries (W[i][j] = 1 for the knn-1 nearest other queries j of i), then `iter` bound updates
@@ -22,35 +26,36 @@ __device__ __forceinline__ double lshot_wave_sum(double v) {
 }
 
 // out = x / ||x||_2 row by row (mode 1, laplacian_shot.py:83-85) or a plain copy (mode 0, 'UN').
-__global__ void k_lshot_normalize(const float* __restrict__ x, int n_rows, int K, int mode, float* __restrict__ out) {
+__global__ void k_lshot_normalize(const float* __restrict__ x, int n_rows, int D, int mode, float* __restrict__ out) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows) return;
-    const float* r = x + (size_t)row * K;
+    const float* r = x + (size_t)row * D;
     float nrm = 1.0f;
     if (mode == 1) {
         double s = 0.0;
-        for (int d = lane; d < K; d += 64) s += (double)r[d] * (double)r[d];
+        for (int d = lane; d < D; d += 64) s += (double)r[d] * (double)r[d];
         s = lshot_wave_sum(s);
         nrm = (float)sqrt(s);
     }
-    for (int d = lane; d < K; d += 64) out[(size_t)row * K + d] = mode == 1 ? r[d] / nrm : r[d];
+    for (int d = lane; d < D; d += 64) out[(size_t)row * D + d] = mode == 1 ? r[d] / nrm : r[d];
 }
 
 // unary[t][q][k] = ||proto[t][k] - z[t][q]||^2 (the reference squares LA.norm's fp32 square root, :236-238).
+// proto [T][K][D], zq [T][Q][D] -> unary [T][Q][K].
 // One workgroup per query (its row staged in LDS), one class per wavefront at a time, lanes over the features
 // (coalesced prototype reads, fp64 accumulation, one wavefront reduction per class).
 __global__ __launch_bounds__(256) void k_lshot_unary(const float* __restrict__ proto, const float* __restrict__ zq, int Q, int K,
-                                                     float* __restrict__ unary) {
-    extern __shared__ float zrow[];                                  // the query row, K floats
+                                                     int D, float* __restrict__ unary) {
+    extern __shared__ float zrow[];                                  // the query row, D floats
     const int t = blockIdx.y, q = blockIdx.x;
-    const float* z = zq + ((size_t)t * Q + q) * K;
-    for (int d = threadIdx.x; d < K; d += blockDim.x) zrow[d] = z[d];
+    const float* z = zq + ((size_t)t * Q + q) * D;
+    for (int d = threadIdx.x; d < D; d += blockDim.x) zrow[d] = z[d];
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n_waves = blockDim.x >> 6;
     for (int k = wave; k < K; k += n_waves) {                         // one class per wavefront, lanes over features
-        const float* p = proto + ((size_t)t * K + k) * K;
+        const float* p = proto + ((size_t)t * K + k) * D;
         double s = 0.0;
-        for (int d = lane; d < K; d += 64) {
+        for (int d = lane; d < D; d += 64) {
             const float diff = p[d] - zrow[d];
             s += (double)diff * (double)diff;
         }
@@ -62,44 +67,117 @@ __global__ __launch_bounds__(256) void k_lshot_unary(const float* __restrict__ p
     }
 }
 
+// d2[t][i][j] = sum_d ((double)z[t][i][d] - (double)z[t][j][d])^2 over a task's queries, +inf on the diagonal: the distances the
+// kNN selection of k_lshot_task reads when rows are long (the visual entry; at D = 512..1024 the per-lane serial loop inside
+// the one workgroup that owns a task is the method's hot path, with uncoalesced reads).
+// Grid (row tile, task): a task's Q x Q distances spread over ceil(Q / 32) workgroups.  A block owns 32 rows i and walks the
+// column tiles of 32 rows j; per column tile both 32-row tiles are staged in LDS in chunks of 64 features (row-contiguous,
+// coalesced; one 128-bit load per thread and tile where D is a multiple of 4: every row then starts 16-byte aligned, zq being a
+// 256-byte aligned workspace offset).  The 16 x 16 threads each own a 2 x 2 register tile (i = ty + 16 a, j = tx + 16 b) and
+// accumulate in fp64 in ascending d - the operation order of k_lshot_task's own loop, so both give the same bits.
+// LDS rows are padded to 65 floats: the 16 rows j a wavefront reads at one d fall into 16 different banks, its 4 rows i
+// are broadcasts.  2 x 32 x 65 x 4 = 16640 bytes of LDS, 4 fp64 accumulators, no scratch.
+constexpr int kLshotPdTile = 32, kLshotPdChunk = 64, kLshotPdStride = kLshotPdChunk + 1;
+
+__global__ __launch_bounds__(256) void k_lshot_pairdist(const float* __restrict__ zq, int Q, int D, double* __restrict__ d2) {
+    __shared__ float zi[kLshotPdTile][kLshotPdStride];
+    __shared__ float zj[kLshotPdTile][kLshotPdStride];
+    const int t = blockIdx.y, i0 = blockIdx.x * kLshotPdTile, id = threadIdx.x, tx = id & 15, ty = id >> 4;
+    const float* z = zq + (size_t)t * Q * D;
+    double* out = d2 + (size_t)t * Q * Q;
+    const bool vec = (D & 3) == 0;                                    // block-uniform
+    // a 32 x 64 tile of rows r0.. and features d0..: rows past Q and features past D read as zero (never stored, never summed)
+    auto stage = [&](float (*dst)[kLshotPdStride], int r0, int d0) {
+        if (vec) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int idx = id + 256 * h, r = idx >> 4, c = (idx & 15) * 4;
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (r0 + r < Q && d0 + c < D) v = *reinterpret_cast<const float4*>(z + (size_t)(r0 + r) * D + d0 + c);
+                dst[r][c] = v.x; dst[r][c + 1] = v.y; dst[r][c + 2] = v.z; dst[r][c + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < 8; h++) {
+                const int idx = id + 256 * h, r = idx >> 6, c = idx & 63;
+                dst[r][c] = (r0 + r < Q && d0 + c < D) ? z[(size_t)(r0 + r) * D + d0 + c] : 0.0f;
+            }
+        }
+    };
+    for (int j0 = 0; j0 < Q; j0 += kLshotPdTile) {
+        double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
+        for (int d0 = 0; d0 < D; d0 += kLshotPdChunk) {
+            __syncthreads();                                          // the previous chunk has been read
+            stage(zi, i0, d0);
+            stage(zj, j0, d0);
+            __syncthreads();
+            const int dn = min(kLshotPdChunk, D - d0);
+            for (int d = 0; d < dn; d++) {
+                const double a0 = (double)zi[ty][d], a1 = (double)zi[ty + 16][d];
+                const double b0 = (double)zj[tx][d], b1 = (double)zj[tx + 16][d];
+                double diff = a0 - b0;
+                s00 += diff * diff;
+                diff = a0 - b1;
+                s01 += diff * diff;
+                diff = a1 - b0;
+                s10 += diff * diff;
+                diff = a1 - b1;
+                s11 += diff * diff;
+            }
+        }
+        const int ia = i0 + ty, ib = ia + 16, ja = j0 + tx, jb = ja + 16;
+        if (ia < Q && ja < Q) out[(size_t)ia * Q + ja] = ia == ja ? (double)INFINITY : s00;
+        if (ia < Q && jb < Q) out[(size_t)ia * Q + jb] = ia == jb ? (double)INFINITY : s01;
+        if (ib < Q && ja < Q) out[(size_t)ib * Q + ja] = ib == ja ? (double)INFINITY : s10;
+        if (ib < Q && jb < Q) out[(size_t)ib * Q + jb] = ib == jb ? (double)INFINITY : s11;
+    }
+}
+
 struct LshotArgs {
-    const float* zq;          // [T][Q][K] normalised queries
+    const float* zq;          // [T][Q][D] normalised queries
+    const double* d2;         // [T][Q][Q] from k_lshot_pairdist, or nullptr: the distances are computed in k_lshot_task
     const float* unary;       // [T][Q][K]
     double* ybuf;             // [T][2][Q][K]
     int32_t* neighbours;      // [T][Q][knn-1] out
     int32_t* preds_iter;      // [T][iters][Q] out
     double* energies;         // [T][iters] out
-    int Q, K, knn, iters;
+    int Q, K, D, knn, iters;
     double lmd;
 };
 
 // One workgroup per task: kNN graph, then the bound updates.
 __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
     extern __shared__ char lshot_smem[];
-    const int Q = a.Q, K = a.K, nn = a.knn - 1, t = blockIdx.x;
+    const int Q = a.Q, K = a.K, D = a.D, nn = a.knn - 1, t = blockIdx.x;
     int* nbr = reinterpret_cast<int*>(lshot_smem);                     // [Q][nn]
     double* row_e = reinterpret_cast<double*>(lshot_smem + (((size_t)Q * nn * sizeof(int) + 7) & ~(size_t)7));   // [Q]
     __shared__ int frozen;
     __shared__ double e_old;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const float* zq = a.zq + (size_t)t * Q * K;
+    const float* zq = a.zq + (size_t)t * Q * D;
+    const double* pd = a.d2 ? a.d2 + (size_t)t * Q * Q : nullptr;
     const float* unary = a.unary + (size_t)t * Q * K;
     double* y0 = a.ybuf + (size_t)t * 2 * Q * K;
     double* y1 = y0 + (size_t)Q * K;
 
-    // ---- kNN over the task's queries (create_affinity, :91-101): squared distances in fp64, the nn nearest others,
-    // ties to the lower index (exact ties do not occur between distinct images)
+    // ---- kNN over the task's queries (create_affinity, :91-101): squared distances in fp64 (computed here, or read from
+    // k_lshot_pairdist's table: coalesced, a lane's 64-strided columns of row i), the nn nearest others, ties to the lower
+    // index (exact ties do not occur between distinct images)
     for (int i = wave; i < Q; i += kLshotWaves) {
         double d2[kLshotMaxQ / 64];
-        const float* zi = zq + (size_t)i * K;
+        const float* zi = zq + (size_t)i * D;
 #pragma unroll
         for (int e = 0; e < kLshotMaxQ / 64; e++) {
             const int j = e * 64 + lane;
             d2[e] = INFINITY;
             if (e * 64 < Q && j < Q && j != i) {
-                const float* zj = zq + (size_t)j * K;
+                if (pd) {
+                    d2[e] = pd[(size_t)i * Q + j];
+                    continue;
+                }
+                const float* zj = zq + (size_t)j * D;
                 double s = 0.0;
-                for (int d = 0; d < K; d++) {
+                for (int d = 0; d < D; d++) {
                     const double diff = (double)zi[d] - (double)zj[d];
                     s += diff * diff;
                 }
@@ -213,20 +291,69 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
     }
 }
 
-struct LshotWs { size_t zs, zq, sup, cnt, proto, ybuf, total; };
-static LshotWs lshot_ws(const tclip_problem& p) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support;
+struct LshotWs { size_t zs, zq, sup, cnt, proto, ybuf, d2, total; };
+// rows of `dim` elements; pairdist: room for k_lshot_pairdist's [T][Q][Q] fp64 table (the visual entry)
+static LshotWs lshot_ws(const tclip_problem& p, int dim, bool pairdist) {
+    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, D = dim;
     LshotWs w;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    w.zs = take(T * S * K * 4);
-    w.zq = take(T * Q * K * 4);
-    w.sup = take(T * K * K * 4);
+    w.zs = take(T * S * D * 4);
+    w.zq = take(T * Q * D * 4);
+    w.sup = take(T * K * D * 4);
     w.cnt = take(T * K * 4);
-    w.proto = take(T * K * K * 4);
+    w.proto = take(T * K * D * 4);
     w.ybuf = take(T * 2 * Q * K * 8);
+    w.d2 = pairdist ? take(T * Q * Q * 8) : 0;
     w.total = o;
     return w;
+}
+
+// what both entries check of the problem and of knn / norm_type
+static int check_lshot(const tclip_problem* pp, int32_t knn, int32_t norm_type) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem& p = *pp;
+    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT needs iters >= 1");
+    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive");
+    if (norm_type != 0 && norm_type != 1) return fail(TCLIP_ERR_ARG, "norm_type must be 0 (UN) or 1 (L2N); CL2N needs a train mean the reference never passes");
+    if (knn < 2 || knn > p.n_query) return fail(TCLIP_ERR_ARG, "knn must be in 2..n_query (the nearest neighbour of a query is the query itself)");
+    if (p.n_query > kLshotMaxQ) return fail(TCLIP_ERR_ARG, "n_query must be <= 1024 for LAPLACIAN_SHOT");
+    return TCLIP_OK;
+}
+
+// The launch sequence of both entries on rows of D elements: the support class sums of k_support_stats at D = K and of
+// k_vis_support_stats otherwise; pairdist = false (probability features): the distances inside k_lshot_task, true (visual
+// features): k_lshot_pairdist's table.
+static int lshot_run(const tclip_problem& p, int D, bool pairdist, const float* x_q, const float* x_s, const int64_t* y_s,
+                     int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter,
+                     double* energies, char* ws, hipStream_t st) {
+    const LshotWs o = lshot_ws(p, D, pairdist);
+    const size_t smem = (((size_t)p.n_query * (knn - 1) * sizeof(int) + 7) & ~(size_t)7) + (size_t)p.n_query * sizeof(double);
+    if (smem > 60000) return fail(TCLIP_ERR_ARG, "n_query * knn too large for the neighbour lists in LDS");
+    const int Q = p.n_query, K = p.n_class, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
+    float* zs = (float*)(ws + o.zs);
+    float* zq = (float*)(ws + o.zq);
+    float* sup = (float*)(ws + o.sup);
+    float* cnt = (float*)(ws + o.cnt);
+    float* proto = (float*)(ws + o.proto);
+    double* d2 = pairdist ? (double*)(ws + o.d2) : nullptr;
+    // normalization (:66-89), prototypes = class means of the normalised support (:201-205)
+    hipLaunchKernelGGL(k_lshot_normalize, dim3((T * S + 3) / 4), dim3(256), 0, st, x_s, T * S, D, norm_type, zs);
+    hipLaunchKernelGGL(k_lshot_normalize, dim3((T * Q + 3) / 4), dim3(256), 0, st, x_q, T * Q, D, norm_type, zq);
+    if (D != K)                                                       // as tim_loop: D = K keeps the probability entry's sums
+        launch_vis_support_stats(st, zs, y_s, T, S, K, D, sup, cnt);
+    else
+        hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(zs), y_s, S, K, 0, sup, cnt);
+    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
+                       (size_t)TK * D, D, proto);
+    hipLaunchKernelGGL(k_lshot_unary, dim3(Q, T), dim3(256), (size_t)D * sizeof(float), st, (const float*)proto, (const float*)zq, Q, K, D,
+                       unary);
+    if (pairdist)
+        hipLaunchKernelGGL(k_lshot_pairdist, dim3((Q + kLshotPdTile - 1) / kLshotPdTile, T), dim3(256), 0, st, (const float*)zq, Q, D, d2);
+    const LshotArgs a{zq, d2, unary, (double*)(ws + o.ybuf), neighbours, preds_iter, energies, Q, K, D, knn, p.iters, lmd};
+    hipLaunchKernelGGL(k_lshot_task, dim3(T), dim3(64 * kLshotWaves), smem, st, a);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
 }
 
 }  // namespace tclip
@@ -235,7 +362,7 @@ extern "C" {
 
 size_t tclip_laplacian_shot_workspace_bytes(const tclip_problem* p) {
     if (check_problem(p) != TCLIP_OK) return 0;
-    return lshot_ws(*p).total;
+    return lshot_ws(*p, p->n_class, false).total;
 }
 
 int tclip_laplacian_shot_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, int32_t knn,
@@ -246,33 +373,31 @@ int tclip_laplacian_shot_run(const tclip_problem* pp, const float* x_q, const fl
     if (p.iters < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT needs iters >= 1");
     if (!x_q || !x_s || !y_s || !unary || !neighbours || !preds_iter || !energies || !workspace)
         return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive");
-    if (norm_type != 0 && norm_type != 1) return fail(TCLIP_ERR_ARG, "norm_type must be 0 (UN) or 1 (L2N); CL2N needs a train mean the reference never passes");
-    if (knn < 2 || knn > p.n_query) return fail(TCLIP_ERR_ARG, "knn must be in 2..n_query (the nearest neighbour of a query is the query itself)");
-    if (p.n_query > kLshotMaxQ) return fail(TCLIP_ERR_ARG, "n_query must be <= 1024 for LAPLACIAN_SHOT");
-    const LshotWs o = lshot_ws(p);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_laplacian_shot_workspace_bytes")) return rc;
-    const size_t smem = (((size_t)p.n_query * (knn - 1) * sizeof(int) + 7) & ~(size_t)7) + (size_t)p.n_query * sizeof(double);
-    if (smem > 60000) return fail(TCLIP_ERR_ARG, "n_query * knn too large for the neighbour lists in LDS");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    float* zs = (float*)(ws + o.zs);
-    float* zq = (float*)(ws + o.zq);
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* proto = (float*)(ws + o.proto);
-    // normalization (:66-89), prototypes = class means of the normalised support (:201-205)
-    hipLaunchKernelGGL(k_lshot_normalize, dim3((T * S + 3) / 4), dim3(256), 0, st, x_s, T * S, K, norm_type, zs);
-    hipLaunchKernelGGL(k_lshot_normalize, dim3((T * Q + 3) / 4), dim3(256), 0, st, x_q, T * Q, K, norm_type, zq);
-    hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(zs), y_s, S, K, 0, sup, cnt);
-    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * K)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
-                       (size_t)TK * K, K, proto);
-    hipLaunchKernelGGL(k_lshot_unary, dim3(Q, T), dim3(256), (size_t)K * sizeof(float), st, (const float*)proto, (const float*)zq, Q, K, unary);
-    const LshotArgs a{zq, unary, (double*)(ws + o.ybuf), neighbours, preds_iter, energies, Q, K, knn, p.iters, lmd};
-    hipLaunchKernelGGL(k_lshot_task, dim3(T), dim3(64 * kLshotWaves), smem, st, a);
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
+    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
+    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, p.n_class, false).total, "tclip_laplacian_shot_workspace_bytes")) return rc;
+    return lshot_run(p, p.n_class, false, x_q, x_s, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace,
+                     (hipStream_t)stream);
+}
+
+size_t tclip_laplacian_shot_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024"), 0;
+    return lshot_ws(*p, dim, true).total;
+}
+
+int tclip_laplacian_shot_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s,
+                                    int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours,
+                                    int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
+    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
+    if (!x_q || !x_s || !y_s || !unary || !neighbours || !preds_iter || !energies || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    const tclip_problem p = *pp;
+    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, dim, true).total, "tclip_laplacian_shot_visual_workspace_bytes"))
+        return rc;
+    return lshot_run(p, dim, true, x_q, x_s, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace,
+                     (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,9 +1,9 @@
-// ALPHA_TIM (SURVEY.md F4; reference: src/methods/few_shot/tim.py:192-322) on probability features and TIM_GD (tim.py:90-189)
-// on rows of any length: included at the end of tclip_kernels.hip, uses its helpers (fail, check_problem, align_up,
+// ALPHA_TIM (SURVEY.md F4; reference: src/methods/few_shot/tim.py:192-322) and TIM_GD (tim.py:90-189), both on rows of any
+// length (tclip_alpha_tim_run: probability features, D = K; tclip_alpha_tim_visual_run and tclip_tim_gd_run: any D in 1..1024):
+// included at the end of tclip_kernels.hip, uses its helpers (fail, check_problem, align_up,
 // k_support_stats, k_div_rows) and launch_vis_support_stats of tclip_visual_fs.inc.
 //
-// Per task the reference keeps one weight matrix W (K classes x D features; D = K for ALPHA_TIM, which this package runs on
-// probability features only, any D in 1..1024 for TIM_GD) and runs `iter` Adam
+// Per task the reference keeps one weight matrix W (K classes x D features) and runs `iter` Adam
 // steps on  lw0 * CE(support) - (lw1 * H(marginal of the query predictions) - lw2 * H(query | prediction))
 // with logits T (x.w_k - |w_k|^2/2 - |x|^2/2).  Autograd is replaced by the closed-form gradient:
 //   dL/dlogit[i,k] = p_k (g_k - sum_j g_j p_j),  g = dL/dp  (softmax backward, row by row),
@@ -74,7 +74,7 @@ __global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int D, f
 //   kTN = false (logits):  C[m][n] = sum_k X_m[k] W_n[k]          rows of X and W contiguous along k (stored transposed)
 //   kTN = true  (dW):      C[m][n] = sum_i G[i][m] X_i[n]         both operands contiguous along the tile dimension
 // K classes and rows of X.D elements (R = S + Q rows per task): the logits are R x K over a depth of D, dW is K x D over a
-// depth of R; W and dW rows have D elements, G and the logits' rows K.  ALPHA_TIM runs it at D = K.
+// depth of R; W and dW rows have D elements, G and the logits' rows K.
 // Epilogue: the logits' scaling and norms, or (dW) the column sums of G by the blocks of the first column tile.
 // TILE = 128 (2 x 2 MFMA tiles per wavefront) loses to partial tiles and to fewer blocks: K = 397 25.4, K = 1000 48.9 TFLOP/s.
 constexpr int kTimMfmaDepth = 16;    // measured at 64 x 64 tiles: depth 16 52.7, 32 45.9, 64 25.2 TFLOP/s (K = 1000, S = 4000, 4 tasks)
@@ -343,7 +343,8 @@ __global__ void k_tim_adam(float* __restrict__ W, float* __restrict__ M, float* 
 }
 
 // criterion of one batch (ALPHA_TIM: n = its tasks x classes) or of one task (TIM_GD: n = its classes): the mean of the
-// block's n row displacements (fixed-order tree).
+// block's n row displacements (fixed-order tree).  A displacement is the norm of a weight row of D elements (k_tim_adam);
+// there are K of them per task whatever D is.
 __global__ void k_tim_criterion(const float* __restrict__ moved, int n, float* __restrict__ out, int stride) {
     __shared__ float part[256];
     const float* m = moved + (size_t)blockIdx.x * n;
@@ -445,6 +446,36 @@ static int check_tim_gd(const tclip_problem* p, int32_t dim) {
     return TCLIP_OK;
 }
 
+// ALPHA_TIM on rows of D elements: the checks and the loop of both entries (ws_query: the workspace query to name)
+static int alpha_tim_run(const tclip_problem* pp, int D, const tclip_tim_params* prm, const float* x_q, const float* x_s,
+                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions, void* workspace,
+                         size_t workspace_bytes, void* stream, const char* ws_query) {
+    const tclip_problem p = *pp;
+    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM needs iters >= 1 (the accuracy is read from the last iteration's logits)");
+    if (!prm || !x_q || !x_s || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM is a few-shot method: n_support must be positive");
+    for (int i = 0; i < 3; i++)
+        if (prm->entropies[i] != TCLIP_TIM_SHANNON && prm->entropies[i] != TCLIP_TIM_ALPHA)
+            return fail(TCLIP_ERR_ARG, "entropies must be TCLIP_TIM_SHANNON or TCLIP_TIM_ALPHA");
+    const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
+    if (any_alpha && !(prm->alpha_value != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, D).total, ws_query)) return rc;
+    const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], prm->alpha_value,
+                       prm->entropies[0], prm->entropies[1], prm->entropies[2]};
+    return tim_loop(p, D, prm->lr, prm->temp, loss, false, x_q, x_s, y_s, weights, logits_q, preds, criterions,
+                    (char*)workspace, (hipStream_t)stream);
+}
+
+// what tclip_alpha_tim_visual_run and its workspace query check of the problem
+static int check_alpha_tim_visual(const tclip_problem* p, int32_t dim) {
+    if (int rc = check_problem(p)) return rc;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
+    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)(p->n_support > 0 ? p->n_support : 0) + p->n_query;
+    if (T * R > 0x7fffffffu) return fail(TCLIP_ERR_ARG, "ALPHA_TIM: tasks * (n_support + n_query) must fit in int32");
+    return TCLIP_OK;
+}
+
 }  // namespace tclip
 
 extern "C" {
@@ -458,21 +489,21 @@ int tclip_alpha_tim_run(const tclip_problem* pp, const tclip_tim_params* prm, co
                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM needs iters >= 1 (the accuracy is read from the last iteration's logits)");
-    if (!prm || !x_q || !x_s || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM is a few-shot method: n_support must be positive");
-    for (int i = 0; i < 3; i++)
-        if (prm->entropies[i] != TCLIP_TIM_SHANNON && prm->entropies[i] != TCLIP_TIM_ALPHA)
-            return fail(TCLIP_ERR_ARG, "entropies must be TCLIP_TIM_SHANNON or TCLIP_TIM_ALPHA");
-    const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
-    if (any_alpha && !(prm->alpha_value != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
-    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, p.n_class).total, "tclip_alpha_tim_workspace_bytes")) return rc;
-    const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], prm->alpha_value,
-                       prm->entropies[0], prm->entropies[1], prm->entropies[2]};
-    return tim_loop(p, p.n_class, prm->lr, prm->temp, loss, false, x_q, x_s, y_s, weights, logits_q, preds, criterions,
-                    (char*)workspace, (hipStream_t)stream);
+    return alpha_tim_run(pp, pp->n_class, prm, x_q, x_s, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
+                         "tclip_alpha_tim_workspace_bytes");
+}
+
+size_t tclip_alpha_tim_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_alpha_tim_visual(p, dim) != TCLIP_OK) return 0;
+    return tim_ws(*p, dim).total;
+}
+
+int tclip_alpha_tim_visual_run(const tclip_problem* pp, int32_t dim, const tclip_tim_params* prm, const float* x_q, const float* x_s,
+                               const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
+    return alpha_tim_run(pp, dim, prm, x_q, x_s, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
+                         "tclip_alpha_tim_visual_workspace_bytes");
 }
 
 size_t tclip_tim_gd_workspace_bytes(const tclip_problem* p, int32_t dim) {

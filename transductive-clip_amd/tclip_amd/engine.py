@@ -248,26 +248,50 @@ def run_paddle(x_q, x_s, y_s, *, iters, lambd):
 ENTROPIES = {"Shannon": 0, "Alpha": 1}
 
 
-def run_alpha_tim(x_q, x_s, y_s, *, iters, temp, lr, alpha_value, loss_weights=(1.0, 1.0, 1.0),
-                  entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
-    """ALPHA_TIM: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda -> (weights (T,K,K), logits_q (T,Q,K) of the
-    last iteration's forward pass, preds (T,Q) i32 = their argmax, criterions (n_batches, iters)), cuda, not synchronised."""
-    for e in entropies:
-        if e not in ENTROPIES:
-            raise ValueError("Entropies must be in ['Shannon', 'Alpha']")        # tim.py:286, 295, 305
-    x_q = _query(x_q)
-    x_s, y_s = _support(x_q, x_s, y_s)
-    T, Q, K = x_q.shape
+def _run_alpha_tim(x_q, x_s, y_s, K, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, visual):
+    """ALPHA_TIM on rows of D elements: D = K and tclip_alpha_tim_run for probability features, tclip_alpha_tim_visual_run with D
+    as its first argument for visual ones."""
+    T, Q, D = x_q.shape
     if T % n_batches:
         raise ValueError("the number of tasks must be a multiple of n_batches")
     prm = _capi.TimParams(float(lr), float(temp), float(alpha_value), (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
                           (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
+    stem, dim = ("tclip_alpha_tim_visual", (ctypes.c_int32(D),)) if visual else ("tclip_alpha_tim", ())
     c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, x_s.shape[1], iters, 1, 0, 0),
-              "tclip_alpha_tim_workspace_bytes")
-    weights, logits_q, preds, crit = c.empty(T, K, K), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(n_batches, iters)
-    c.launch("tclip_alpha_tim_run", lambda ws, n, st: (ctypes.byref(prm), _ptr(x_q), _ptr(x_s), _ptr(y_s), _ptr(weights),
-                                                       _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
+              stem + "_workspace_bytes", *dim)
+    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(n_batches, iters)
+    c.launch(stem + "_run", lambda ws, n, st: (*dim, ctypes.byref(prm), _ptr(x_q), _ptr(x_s), _ptr(y_s), _ptr(weights),
+                                               _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
     return weights, logits_q, preds, crit
+
+
+def _check_entropies(entropies):
+    for e in entropies:
+        if e not in ENTROPIES:
+            raise ValueError("Entropies must be in ['Shannon', 'Alpha']")        # tim.py:286, 295, 305
+
+
+def run_alpha_tim(x_q, x_s, y_s, *, iters, temp, lr, alpha_value, loss_weights=(1.0, 1.0, 1.0),
+                  entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
+    """ALPHA_TIM: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda -> (weights (T,K,K), logits_q (T,Q,K) of the
+    last iteration's forward pass, preds (T,Q) i32 = their argmax, criterions (n_batches, iters)), cuda, not synchronised."""
+    _check_entropies(entropies)
+    x_q = _query(x_q)
+    x_s, y_s = _support(x_q, x_s, y_s)
+    return _run_alpha_tim(x_q, x_s, y_s, x_q.shape[2], iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, visual=False)
+
+
+def run_alpha_tim_visual(x_q, x_s, y_s, *, n_class, iters, temp, lr, alpha_value, loss_weights=(1.0, 1.0, 1.0),
+                         entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
+    """ALPHA_TIM on visual features: x_q (T,Q,D), x_s (T,S,D) raw embeddings f32 cuda with any D in 1..1024, y_s (T,S) int64 cuda
+    with labels in 0..n_class-1 -> (weights (T,K,D), logits_q (T,Q,K) of the last iteration's forward pass, preds (T,Q) i32 =
+    their argmax, criterions (n_batches, iters)), cuda, not synchronised.  K = n_class cannot be read off a tensor shape here."""
+    _check_entropies(entropies)
+    x_q = _query(x_q)
+    if x_s.dim() != 3 or x_s.shape[1] < 1:
+        raise ValueError("ALPHA_TIM is a few-shot method: x_s must be (T,S,D) with n_support = S positive")
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    return _run_alpha_tim(x_q, x_s, y_s, K, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, visual=True)
 
 
 def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0), n_batches=1):
@@ -293,21 +317,42 @@ def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.
     return weights, logits_q, preds, crit
 
 
+def _run_laplacian_shot(x_q, x_s, y_s, K, iters, knn, lmd, norm_type, visual):
+    """LAPLACIAN_SHOT on rows of D elements: D = K and tclip_laplacian_shot_run for probability features,
+    tclip_laplacian_shot_visual_run with D as its first argument for visual ones."""
+    T, Q, D = x_q.shape
+    stem, dim = ("tclip_laplacian_shot_visual", (ctypes.c_int32(D),)) if visual else ("tclip_laplacian_shot", ())
+    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), stem + "_workspace_bytes", *dim)
+    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
+    preds_iter, energies = c.empty(T, max(iters, 1), Q, dtype=torch.int32), c.empty(T, max(iters, 1), dtype=torch.float64)
+    c.launch(stem + "_run", lambda ws, n, st: (*dim, _ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_int32(int(knn)),
+                                               ctypes.c_double(float(lmd)), ctypes.c_int32(NORM_TYPES[norm_type]),
+                                               _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies), ws, n, st))
+    return unary, nbr, preds_iter, energies
+
+
+def _check_lshot_norm(norm_type):
+    if norm_type not in ("UN", "L2N"):
+        raise ValueError("norm_type must be 'UN' or 'L2N' (the reference's CL2N needs a train mean it never passes)")
+
+
 def run_laplacian_shot(x_q, x_s, y_s, *, iters, knn, lmd, norm_type="L2N"):
     """LAPLACIAN_SHOT: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda -> (unary (T,Q,K), neighbours (T,Q,knn-1) i32,
     preds_iter (T,iters,Q) i32, energies (T,iters) f64), cuda, not synchronised."""
-    if norm_type not in ("UN", "L2N"):
-        raise ValueError("norm_type must be 'UN' or 'L2N' (the reference's CL2N needs a train mean it never passes)")
+    _check_lshot_norm(norm_type)
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
-    T, Q, K = x_q.shape
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), "tclip_laplacian_shot_workspace_bytes")
-    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
-    preds_iter, energies = c.empty(T, max(iters, 1), Q, dtype=torch.int32), c.empty(T, max(iters, 1), dtype=torch.float64)
-    c.launch("tclip_laplacian_shot_run", lambda ws, n, st: (_ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_int32(int(knn)),
-                                                            ctypes.c_double(float(lmd)), ctypes.c_int32(NORM_TYPES[norm_type]),
-                                                            _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies), ws, n, st))
-    return unary, nbr, preds_iter, energies
+    return _run_laplacian_shot(x_q, x_s, y_s, x_q.shape[2], iters, knn, lmd, norm_type, visual=False)
+
+
+def run_laplacian_shot_visual(x_q, x_s, y_s, *, n_class, iters, knn, lmd, norm_type="L2N"):
+    """LAPLACIAN_SHOT on visual features: x_q (T,Q,D), x_s (T,S,D) raw embeddings f32 cuda with any D in 1..1024, y_s (T,S)
+    int64 cuda with labels in 0..n_class-1 -> (unary (T,Q,K), neighbours (T,Q,knn-1) i32, preds_iter (T,iters,Q) i32, energies
+    (T,iters) f64), cuda, not synchronised.  K = n_class cannot be read off a tensor shape here."""
+    _check_lshot_norm(norm_type)
+    x_q = _query(x_q)
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    return _run_laplacian_shot(x_q, x_s, y_s, K, iters, knn, lmd, norm_type, visual=True)
 
 
 def argmax_rows(x):
