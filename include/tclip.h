@@ -35,7 +35,8 @@ extern "C" {
  *    tclip_paddle_visual_workspace_bytes, tclip_paddle_visual_run, tclip_bdcspn_visual_workspace_bytes, tclip_bdcspn_visual_run;
  *    tclip_tim_gd_workspace_bytes, tclip_tim_gd_run;
  *    tclip_alpha_tim_visual_workspace_bytes, tclip_alpha_tim_visual_run, tclip_laplacian_shot_visual_workspace_bytes,
- *    tclip_laplacian_shot_visual_run
+ *    tclip_laplacian_shot_visual_run;
+ *    tclip_match_clusters_workspace_bytes, tclip_match_clusters
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -145,6 +146,26 @@ int tclip_match_clusters_host_strided(int32_t n_task, int32_t n_query, int32_t n
                                       const int32_t* n_clusters, const int32_t* cluster_ids, const float* prototypes,
                                       const int64_t* y_q, int32_t graph_matching, int32_t c_stride, int32_t* new_preds,
                                       float* acc);
+
+/* Accuracy tail, the matching ON THE DEVICE (all pointers DEVICE memory, asynchronous on `stream`): what
+ * tclip_match_clusters_host_strided computes, bit for bit - same new_preds, same acc - from what tclip_cluster_prototypes[_visual]
+ * (+ tclip_probability_features) leave on the device; no copy to the host, no host threads, no synchronisation.  One
+ * wavefront per task runs the host's shortest-augmenting-path solver in fp64 with its scanning order and tie rule
+ * (k_match_clusters, csrc/tclip_match.inc); graph_matching == 0 takes the first maximum of each prototype row.
+ *   preds [T,Q] i32, n_clusters [T] i32, cluster_ids [T, c_stride] i32, prototypes [T, c_stride, K] f32, y_q [T,Q] i64;
+ *   c_stride in 1..min(Q, K) - the full min(Q, K) of the prototype entries: nothing is read back to choose a smaller one;
+ *   new_preds [T,Q] i32 out, acc [T] f32 out, status [T] i32 out.
+ * Argument checks (T >= 1, Q >= 1, K in 2..1024, c_stride, null pointers) return TCLIP_ERR_ARG before any launch.  What the
+ * host entry checks in the DATA is checked per task on the device, and no label is used as an index before it: a task with
+ * n_clusters outside 1..c_stride (status 1), a cluster id (2) or a prediction (3) outside 0..K-1, or an infeasible assignment
+ * (4: e.g. a NaN prototype row) gets status != 0, acc = NaN and new_preds = -1; the other tasks of the call are unaffected.
+ * The kernel keeps a task in LDS (29 K + 13 c_stride bytes) and needs no global workspace: the query returns 0 and
+ * `workspace` may be NULL. */
+size_t tclip_match_clusters_workspace_bytes(int32_t n_task, int32_t n_query, int32_t n_class, int32_t c_stride);
+int tclip_match_clusters(int32_t n_task, int32_t n_query, int32_t n_class, const int32_t* preds, const int32_t* n_clusters,
+                         const int32_t* cluster_ids, const float* prototypes, const int64_t* y_q, int32_t graph_matching,
+                         int32_t c_stride, int32_t* new_preds, float* acc, int32_t* status,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* Host threads tclip_match_clusters_host* may start: TCLIP_HOST_THREADS if set, else min(16, cores this process may run
  * on / LOCAL_WORLD_SIZE) - one process per GPU must not oversubscribe the node's cores. */

@@ -4061,3 +4061,4 @@ int tclip_gather_rows(const float* table, int64_t n_rows, int32_t K, const int64
 #include "tclip_visual.inc"
 #include "tclip_visual_fs.inc"
 #include "tclip_methods.inc"
+#include "tclip_match.inc"

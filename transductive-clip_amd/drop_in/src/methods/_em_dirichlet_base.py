@@ -50,7 +50,11 @@ class EMDirichletBase(object):
 
     def get_logs(self):
         self.criterions = np.asarray(self.criterions, dtype=np.float32)
-        self.test_acc = torch.cat(self.test_acc, dim=1).cpu().numpy()
+        on_device = any(a.is_cuda for a in self.test_acc)
+        self.test_acc = torch.cat(self.test_acc, dim=1).cpu()
+        if on_device:            # args.device_matching: a task the host matching raises for has a NaN accuracy there
+            engine.match_status_ok(self.test_acc)
+        self.test_acc = self.test_acc.numpy()
         return {'timestamps': np.array(self.timestamps).mean(), 'criterions': self.criterions,
                 'acc': self.test_acc}
 
@@ -61,16 +65,27 @@ class EMDirichletBase(object):
         accuracy = (preds_q == y_q.cpu()).float().mean(1, keepdim=True)
         self.test_acc.append(accuracy)
 
+    def _matching(self):
+        """args.device_matching (main_features.py --opts device_matching True): the cluster-to-class matching runs on the
+        device too; accuracies and matched predictions stay there until get_logs.  The option is optional, and args may be
+        a namespace (a missing attribute is an AttributeError) or a dict with attribute access (a KeyError)."""
+        try:
+            on = getattr(self.args, "device_matching", False)
+        except KeyError:
+            on = False
+        return "device" if on else "host"
+
     def compute_acc_clustering(self, query, y_q):
         acc, new_preds = engine.clustering_accuracy(query, self.preds, y_q,
-                                                    graph_matching=bool(self.args.graph_matching))
+                                                    graph_matching=bool(self.args.graph_matching), matching=self._matching())
         self.matched_preds = new_preds
         self.test_acc.append(acc.view(-1, 1))
 
     def compute_acc_clustering_visual(self, query, y_q, text):
         """the accuracy tail on visual features (soft_kmeans.py:36-66): D-dim prototypes, scored against the text features"""
         acc, new_preds = engine.clustering_accuracy_visual(query, self.preds, y_q, text, self.args.T,
-                                                           graph_matching=bool(self.args.graph_matching))
+                                                           graph_matching=bool(self.args.graph_matching),
+                                                           matching=self._matching())
         self.matched_preds = new_preds
         self.test_acc.append(acc.view(-1, 1))
 

@@ -24,6 +24,8 @@ file under <results-root>/results_few_shot/val/, exactly as the reference does; 
 With `use_softmax_feature False` the zero-shot k-means family and CLIP (with --text-features) and the few-shot PADDLE,
 BDCSPN and TIM-GD (`method tim`; no text features needed) run on the raw embeddings of <split>_visual_<backbone>.plk; the
 class count is read from the labels and the sweep and result files carry `_visual` in their names.
+`device_matching True` (zero-shot clustering methods; not a default: absent unless given) matches clusters to classes on the
+device instead of on host threads - same accuracies, no copy of the prototypes to the host.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse

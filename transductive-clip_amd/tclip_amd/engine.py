@@ -394,11 +394,24 @@ def run_bdcspn(x_q, x_s, y_s, *, temp, norm_type="L2N"):
     return _run_bdcspn(x_q, x_s, y_s, x_q.shape[2], temp, norm_type, visual=False)
 
 
-def clustering_accuracy(x_q, preds, y_q, graph_matching=True):
-    """Zero-shot accuracy tail: device prototypes of the predicted clusters, host assignment.
+MATCHING = ("host", "device")
+
+
+def _check_matching(matching):
+    if matching not in MATCHING:
+        raise ValueError(f"matching must be one of {MATCHING}, got {matching!r}")
+    return _match_device if matching == "device" else _match
+
+
+def clustering_accuracy(x_q, preds, y_q, graph_matching=True, *, matching="host"):
+    """Zero-shot accuracy tail: device prototypes of the predicted clusters, then the assignment of clusters to classes.
 
     x_q (T,Q,K) cuda f32, preds (T,Q) cuda i32, y_q (T,Q) int64 (any device).
-    Returns (acc (T,) f32 cpu, new_preds (T,Q) i32 cpu)."""
+    matching="host" (the default): the assignment runs on host threads; the call synchronises the stream and returns
+    (acc (T,) f32 cpu, new_preds (T,Q) i32 cpu).
+    matching="device": tclip_match_clusters on the current stream, the same bits; returns (acc, new_preds) on the device,
+    not synchronised.  A task the host path would raise RuntimeError for has acc = NaN there (match_status_ok)."""
+    match = _check_matching(matching)
     _require_cuda(x_q, "x_q")
     x_q = x_q.contiguous().float()
     T, Q, K = x_q.shape
@@ -416,7 +429,7 @@ def clustering_accuracy(x_q, preds, y_q, graph_matching=True):
         rc = lib.tclip_cluster_prototypes(T, Q, K, _ptr(x_q), _ptr(preds), _ptr(n_clusters), _ptr(ids), _ptr(protos),
                                           ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, _stream())
         _capi.check(rc, "tclip_cluster_prototypes")
-    return _match(lib, T, Q, K, preds, n_clusters, ids, protos, y_q, graph_matching, cmax, dev)
+    return match(lib, T, Q, K, preds, n_clusters, ids, protos, y_q, graph_matching, cmax, dev)
 
 
 VISUAL_METHODS = {"soft_kmeans": 0, "hard_kmeans": 1, "em_gaussian": 2}     # TCLIP_VISUAL_* of include/tclip.h
@@ -531,11 +544,44 @@ def _match(lib, T, Q, K, preds, n_clusters, ids, rows, y_q, graph_matching, cmax
     return acc, new_preds
 
 
-def clustering_accuracy_visual(x_q, preds, y_q, text, T, graph_matching=True):
+def _match_device(lib, T, Q, K, preds, n_clusters, ids, rows, y_q, graph_matching, cmax, dev):
+    """the matching on the device (tclip_match_clusters) from the full (T, cmax, K) rows: nothing is copied to the host or
+    read back and the stream is not synchronised; a failed task has acc = NaN and new_preds = -1"""
+    with torch.cuda.device(dev):
+        y_d = y_q.reshape(T, Q).to(dev).long().contiguous()
+        new_preds = torch.empty(T, Q, dtype=torch.int32, device=dev)
+        acc = torch.empty(T, dtype=torch.float32, device=dev)
+        status = torch.empty(T, dtype=torch.int32, device=dev)
+        ws_bytes = lib.tclip_match_clusters_workspace_bytes(T, Q, K, cmax)
+        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev) if ws_bytes else None
+        ws_ptr = ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256) if ws_bytes else None
+        rc = lib.tclip_match_clusters(T, Q, K, _ptr(preds), _ptr(n_clusters), _ptr(ids), _ptr(rows), _ptr(y_d),
+                                      int(bool(graph_matching)), cmax, _ptr(new_preds), _ptr(acc), _ptr(status), ws_ptr, ws_bytes,
+                                      _stream())
+        _capi.check(rc, "tclip_match_clusters")
+    return acc, new_preds
+
+
+def match_status_ok(acc):
+    """For callers of matching="device" once they bring the accuracies to the host: raises the RuntimeError the host path
+    raises when a task could not be matched (a label outside 0..K-1, an infeasible assignment, e.g. a NaN prototype row) -
+    such a task's accuracy is NaN - and names the tasks.  Returns `acc` on the CPU.  Copying from the device waits for it."""
+    acc = acc.detach().cpu()
+    failed = torch.nonzero(torch.isnan(acc.reshape(acc.shape[0], -1)).any(1)).flatten().tolist() if acc.numel() else []
+    if failed:
+        raise RuntimeError(f"tclip_match_clusters failed for task(s) {failed}: a cluster id or prediction outside 0..K-1, "
+                           "or no feasible assignment (NaN prototypes)")
+    return acc
+
+
+def clustering_accuracy_visual(x_q, preds, y_q, text, T, graph_matching=True, *, matching="host"):
     """Accuracy tail of the visual k-means methods (soft_kmeans.py:36-66): D-dim prototypes of the predicted clusters
     (tclip_cluster_prototypes_visual), probs = softmax_k(T * (p/||p||) . text_k) of each (tclip_probability_features: the
     scale before the dot product, as the reference's tail has it), host matching of clusters to classes on those rows.
-    x_q (T,Q,D) cuda f32, preds (T,Q) cuda i32, y_q (T,Q) int64, text (K,D).  Returns (acc (T,) f32 cpu, new_preds (T,Q) i32 cpu)."""
+    x_q (T,Q,D) cuda f32, preds (T,Q) cuda i32, y_q (T,Q) int64, text (K,D).  Returns (acc (T,) f32 cpu, new_preds (T,Q) i32 cpu);
+    with matching="device" the matching runs on the device too (tclip_match_clusters) and both come back on the device, not
+    synchronised (see clustering_accuracy)."""
+    match = _check_matching(matching)
     _require_cuda(x_q, "x_q")
     x_q = x_q.contiguous().float()
     n_task, Q, D = x_q.shape
@@ -558,7 +604,7 @@ def clustering_accuracy_visual(x_q, preds, y_q, text, T, graph_matching=True):
         rc = lib.tclip_probability_features(_ptr(protos), _ptr(text), ctypes.c_int64(n_task * cmax), ctypes.c_int32(D),
                                             ctypes.c_int32(K), ctypes.c_float(float(T)), _ptr(probs), _stream())
         _capi.check(rc, "tclip_probability_features")
-    return _match(lib, n_task, Q, K, preds, n_clusters, ids, probs, y_q, graph_matching, cmax, dev)
+    return match(lib, n_task, Q, K, preds, n_clusters, ids, probs, y_q, graph_matching, cmax, dev)
 
 
 def gather_rows(table, idx):
