@@ -36,7 +36,8 @@ extern "C" {
  *    tclip_tim_gd_workspace_bytes, tclip_tim_gd_run;
  *    tclip_alpha_tim_visual_workspace_bytes, tclip_alpha_tim_visual_run, tclip_laplacian_shot_visual_workspace_bytes,
  *    tclip_laplacian_shot_visual_run;
- *    tclip_match_clusters_workspace_bytes, tclip_match_clusters
+ *    tclip_match_clusters_workspace_bytes, tclip_match_clusters;
+ *    tclip_em_gaussian_cov_visual_workspace_bytes, tclip_em_gaussian_cov_visual_run
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -384,6 +385,23 @@ size_t tclip_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
 int tclip_kmeans_visual_run(const tclip_problem* p, int32_t dim, int32_t method, const float* x_q, const float* u0,
                             float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* EM_GAUSSIAN_COV on VISUAL features (use_softmax_feature == False; reference src/methods/zero_shot/em_gaussian_cov.py:106-257,
+ * the text-prompt initialisation of :215-227 given as u0, see tclip_visual_init): tclip_em_gaussian_cov_run's op sequence in the
+ * D-dimensional embedding space, dim = D independent of K = p->n_class.  Centroids w and inverse variances s are [T, K, D]:
+ *   s[t,k,d] = sum_q u / max(sum_q (w[t,k,d] - z[t,q,d])^2 u[t,q,k], eps)      (the sum over q in torch's outer-sum order of K*D columns),
+ *   logit[t,q,k] = -1/2 sum_d (w - z)^2 s + 1/2 sum_d log(s + eps)             (both sums in torch's last-dim order, any D in 1..1024),
+ *   u = softmax_k(logit + lambd v / Q), v = log(mean_q u + eps) + 1; clusters with sum_q u <= eps keep their w and s.
+ * A run from the reference's own u0 gives its bits.  Uses n_batches, tasks_per_batch, n_query, n_class (2..1024), iters, lambd
+ * (int(K/5) * n_query); n_support must be 0 and dim in 1..1024, anything else is TCLIP_ERR_ARG before any launch.
+ *   x_q device [T,Q,D] f32 raw embeddings;  u0 device [T,Q,K] f32;  u device [T,Q,K] out;  v device [T,K] out;
+ *   w, s device [T,K,D] out;  preds device [T,Q] i32 out (first maximum of u);
+ *   workspace: tclip_em_gaussian_cov_visual_workspace_bytes(p, dim) bytes, 256-byte aligned (0 on bad input; a short or
+ *   misaligned one is TCLIP_ERR_WORKSPACE).  Accuracy tail: tclip_cluster_prototypes_visual and what follows it. */
+size_t tclip_em_gaussian_cov_visual_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_em_gaussian_cov_visual_run(const tclip_problem* p, int32_t dim, const float* x_q /*[T,Q,dim]*/, const float* u0 /*[T,Q,K]*/,
+                                     float* u /*[T,Q,K]*/, float* v /*[T,K]*/, float* w /*[T,K,dim]*/, float* s /*[T,K,dim]*/,
+                                     int32_t* preds /*[T,Q]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Accuracy tail of the visual k-means methods, device half: tclip_cluster_prototypes for D-dim features
  * (soft_kmeans.py:36-44): the clusters present in `preds` in first-appearance order and the mean raw embedding of each.

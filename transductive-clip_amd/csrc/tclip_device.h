@@ -291,22 +291,26 @@ __device__ __forceinline__ float dsum_outer(int n, long col, long ncols, F get) 
 }
 
 // torch's contiguous last-dim sum evaluated serially by one thread (small n only).
+// Vector lane jj (0..7) of that sum for n >= 8: the 4 interleaved cascades over the elements 8 i + jj, the whole vectors
+// beyond the 4-way part joining partial 0.
+template <typename F>
+__device__ __forceinline__ float dsum_inner_lane(int n, int jj, F get) {
+    const int vec_size = n >> 3, size_ilp = vec_size >> 2;
+    float p[4];
+    for (int r = 0; r < 4; r++) p[r] = dsum_cascade(size_ilp, [&](int m) { return get(8 * (4 * m + r) + jj); });
+    for (int vv = size_ilp * 4; vv < vec_size; vv++) p[0] += get(8 * vv + jj);
+    p[0] += p[1];
+    p[0] += p[2];
+    p[0] += p[3];
+    return p[0];
+}
 template <typename F>
 __device__ float dsum_inner_serial(int n, F get) {
     if (n < 8) return dsum_ilp4(n, get);
-    const int vec_size = n >> 3, size_ilp = vec_size >> 2;
     float p0[8];
-    for (int jj = 0; jj < 8; jj++) {
-        float p[4];
-        for (int r = 0; r < 4; r++) p[r] = dsum_cascade(size_ilp, [&](int m) { return get(8 * (4 * m + r) + jj); });
-        for (int vv = size_ilp * 4; vv < vec_size; vv++) p[0] += get(8 * vv + jj);
-        p[0] += p[1];
-        p[0] += p[2];
-        p[0] += p[3];
-        p0[jj] = p[0];
-    }
+    for (int jj = 0; jj < 8; jj++) p0[jj] = dsum_inner_lane(n, jj, get);
     float fin = 0.0f;
-    for (int k = vec_size * 8; k < n; k++) fin += get(k);
+    for (int k = (n >> 3) * 8; k < n; k++) fin += get(k);
     for (int jj = 0; jj < 8; jj++) fin += p0[jj];
     return fin;
 }

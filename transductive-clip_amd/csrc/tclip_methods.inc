@@ -2,10 +2,10 @@
 // last by tclip_kernels.hip, after the kernels and launchers of tclip_visual.inc / tclip_visual_fs.inc.
 //
 // Probability features (the reference's use_softmax_feature == True) have rows of K = n_class elements; visual features (raw
-// CLIP embeddings) rows of D elements, D independent of K.  The op sequences are the same; a FeatureSpace picks the three
-// launchers whose work depends on the row length, everything else ([T, Q, K] / [T, K] tensors: the softmax, the cluster sizes,
-// v, the first-minimum one-hot, the criterion) is shared as it stands.  EM_GAUSSIAN_COV and KL_KMEANS exist on probability
-// features only and keep their own loops below.  EM-Dirichlet does not come through here.
+// CLIP embeddings) rows of D elements, D independent of K.  The op sequences are the same; a FeatureSpace picks the
+// launchers whose work depends on the row length (three, and EM_GAUSSIAN_COV's two), everything else ([T, Q, K] / [T, K]
+// tensors: the softmax, the cluster sizes, v, the first-minimum one-hot, the criterion) is shared as it stands.  KL_KMEANS
+// exists on probability features only and keeps its own loop below.  EM-Dirichlet does not come through here.
 
 namespace tclip {
 
@@ -44,6 +44,22 @@ struct FeatureSpace {
         }
     }
 
+    // EM_GAUSSIAN_COV: s[t,k,:] = cs[t,k] / max(sum_q (w[t,k,:] - z[t,q,:])^2 u[t,q,k], eps) for the rows `live` marks
+    void cov_stats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, const float* w, int T, int Q,
+                   int K, float* s) const {
+        if (visual) launch_vis_cov_stats(st, u, z, cs, live, w, T, Q, K, D, s);
+        else launch_cov_stats(st, u, z, cs, live, w, T, Q, K, s);
+    }
+
+    // EM_GAUSSIAN_COV: out[t,q,k] = -1/2 sum_d (w - z)^2 s + 1/2 sum_d log(s + eps) for the classes `need` marks; det [T, K] is
+    // room for the half log-determinants (visual features only: the probability kernel keeps them in registers)
+    int cov_logits(int T, hipStream_t st, const float* w, const float* s, const float* z, const uint8_t* need, int Q, int K, float* det,
+                   float* out) const {
+        if (visual) return launch_vis_cov_logits(T, st, w, s, z, need, Q, K, D, det, out);
+        dispatch_E<LaunchCovLogitsRows>(K, T, st, w, s, z, need, Q, K, out);
+        return TCLIP_OK;
+    }
+
     // sup[t,k,:] = sum of the support rows of class k, cnt[t,k] = their number
     void support_stats(hipStream_t st, const float* x_s, const int64_t* y_s, int T, int S, int K, float* sup, float* cnt) const {
         if (visual) launch_vis_support_stats(st, x_s, y_s, T, S, K, D, sup, cnt);
@@ -66,6 +82,18 @@ struct KmeansWs {
         w.logit = take(T * Q * K * 4);
         w.change = take(T * 4);
         w.total = o;
+        return w;
+    }
+};
+
+// EM_GAUSSIAN_COV on visual features: the k-means regions and the half log-determinants [T, K] f32
+struct CovVisualWs {
+    size_t det, total;
+    static CovVisualWs layout(const tclip_problem& p) {
+        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class;
+        CovVisualWs w;
+        w.det = KmeansWs::layout(p).total;
+        w.total = w.det + align_up(T * K * 4);
         return w;
     }
 };
@@ -165,6 +193,42 @@ static int kmeans_loop(const FeatureSpace& sp, Kmeans kind, const tclip_problem&
     if (emg)      // the last v_update
         hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
                            (int32_t*)nullptr);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+// ---- EM_GAUSSIAN_COV (SURVEY.md F1): EM_GAUSSIAN with a diagonal inverse covariance per cluster; no temperature -----------
+// `det`: room for [T, K] floats on visual features, unused on probability features.
+static int em_gaussian_cov_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const float* u_init, float* u, float* v,
+                                float* w, float* s, int32_t* preds, float* det, char* ws, hipStream_t st) {
+    const KmeansWs o = KmeansWs::layout(p);
+    const int Q = p.n_query, K = p.n_class, T = p.n_batches * p.tasks_per_batch, TK = T * K;
+    const size_t TQK = (size_t)T * Q * K;
+    float* cs = (float*)(ws + o.cs);
+    uint8_t* live = (uint8_t*)(ws + o.live);
+    uint8_t* ones = (uint8_t*)(ws + o.ones);
+    float* logit0 = (float*)(ws + o.logit);
+    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, u_init, u, TQK);       // u = z / u = u0
+    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
+    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
+    // w_init, s_init: every cluster                                                (em_gaussian_cov.py:146-180)
+    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
+                       (float*)nullptr, (int32_t*)nullptr);
+    sp.mstats(st, u, x_q, cs, ones, T, Q, K, Mstats::LiveOnly, w, nullptr, nullptr, false);
+    sp.cov_stats(st, u, x_q, cs, ones, w, T, Q, K, s);
+    for (int it = 0; it < p.iters; it++) {
+        // w_update, s_update: non-empty clusters move, empty ones keep w and s        (:160-193); v of the previous v_update
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
+                           live, it > 0 ? v : (float*)nullptr, (int32_t*)nullptr);
+        sp.mstats(st, u, x_q, cs, live, T, Q, K, Mstats::LiveOnly, w, nullptr, nullptr, false);
+        sp.cov_stats(st, u, x_q, cs, live, w, T, Q, K, s);
+        // u_update: Mahalanobis distances + log-determinants of the clusters that moved, softmax with lambd v / Q   (:106-129)
+        if (int rc = sp.cov_logits(T, st, w, s, x_q, it == 0 ? ones : live, Q, K, det, logit0)) return rc;
+        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
+                           (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
+    }
+    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
+                       (int32_t*)nullptr);                                              // the last v_update
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
 }
@@ -317,47 +381,15 @@ int tclip_hard_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, f
                        (char*)workspace, (hipStream_t)stream);
 }
 
-// ---- EM_GAUSSIAN_COV (SURVEY.md F1): EM_GAUSSIAN with a diagonal inverse covariance per cluster; no temperature
 int tclip_em_gaussian_cov_run(const tclip_problem* pp, const float* x_q, float* u, float* v, float* w, float* s,
                               int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_problem(pp)) return rc;
     const tclip_problem p = *pp;
     if (!x_q || !u || !v || !w || !s || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
     if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV");
-    const KmeansWs o = KmeansWs::layout(p);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_soft_kmeans_workspace_bytes")) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const int Q = p.n_query, K = p.n_class, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    uint8_t* ones = (uint8_t*)(ws + o.ones);
-    float* logit0 = (float*)(ws + o.logit);
-    hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
-    TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    // w_init, s_init: every cluster                                                (em_gaussian_cov.py:146-180)
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live,
-                       (float*)nullptr, (int32_t*)nullptr);
-    launch_mstats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)ones, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
-    launch_cov_stats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)ones, (const float*)w, T, Q, K, s);
-    for (int it = 0; it < p.iters; it++) {
-        // w_update, s_update: non-empty clusters move, empty ones keep w and s        (:160-193); v of the previous v_update
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
-                           live, it > 0 ? v : (float*)nullptr, (int32_t*)nullptr);
-        launch_mstats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)live, (const float*)nullptr, (const float*)nullptr, T, Q, K, w, 0);
-        launch_cov_stats(st, (const float*)u, x_q, (const float*)cs, (const uint8_t*)live, (const float*)w, T, Q, K, s);
-        // u_update: Mahalanobis distances + log-determinants of the clusters that moved, softmax with lambd v / Q   (:106-129)
-        dispatch_E<LaunchCovLogitsRows>(K, T, st, (const float*)w, (const float*)s, x_q, (const uint8_t*)(it == 0 ? ones : live), Q, K,
-                                        logit0);
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0,
-                           (const float*)v, T * Q, Q, K, (float)p.lambd, 0, 0, u, preds);
-    }
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs, live, v,
-                       (int32_t*)nullptr);                                              // the last v_update
-    TCLIP_HIP(hipGetLastError());
-    return TCLIP_OK;
+    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_soft_kmeans_workspace_bytes")) return rc;
+    return em_gaussian_cov_loop(FeatureSpace{p.n_class, false}, p, x_q, x_q, u, v, w, s, preds, nullptr, (char*)workspace,
+                                (hipStream_t)stream);
 }
 
 // ---- KL_KMEANS: HARD_KMEANS's outputs with KL centroids and divergences
@@ -431,6 +463,26 @@ int tclip_kmeans_visual_run(const tclip_problem* pp, int32_t dim, int32_t method
     if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_visual_workspace_bytes")) return rc;
     return kmeans_loop(FeatureSpace{dim, true}, kind, p, x_q, u0, temperature, u, v, w, preds, criterions, (char*)workspace,
                        (hipStream_t)stream);
+}
+
+size_t tclip_em_gaussian_cov_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (dim < 1 || dim > 1024) { fail(TCLIP_ERR_ARG, kDimRange); return 0; }
+    if (p->n_support != 0) { fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV"); return 0; }
+    return CovVisualWs::layout(*p).total;
+}
+
+int tclip_em_gaussian_cov_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* u0, float* u, float* v,
+                                     float* w, float* s, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const tclip_problem p = *pp;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, kDimRange);
+    if (!x_q || !u0 || !u || !v || !w || !s || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV");
+    const CovVisualWs o = CovVisualWs::layout(p);
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_em_gaussian_cov_visual_workspace_bytes")) return rc;
+    return em_gaussian_cov_loop(FeatureSpace{dim, true}, p, x_q, u0, u, v, w, s, preds, (float*)((char*)workspace + o.det),
+                                (char*)workspace, (hipStream_t)stream);
 }
 
 // ---- few-shot, both feature kinds -------------------------------------------------------------------------------------

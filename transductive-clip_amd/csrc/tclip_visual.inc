@@ -11,6 +11,9 @@
 //     in 1..1024, including the cascade dumps after 16 and 32 eight-float steps per accumulator (D >= 512, D = 1024).
 //   * k_vis_mstats: the centroid statistics sum_q u[t,q,k] z[t,q,d] in the order of torch's
 //     (z.unsqueeze(2) * u.unsqueeze(3)).sum(1): an outer sum over K*D contiguous columns (k_mstats for D = K).
+//   * EM_GAUSSIAN_COV (em_gaussian_cov.py; driver em_gaussian_cov_loop): k_vis_mstats<true> gives the inverse variances s in the
+//     same outer-sum order, k_vis_dist<true> the Mahalanobis sums in the same last-dim order with s in a second LDS tile,
+//     k_vis_logdet the half log-determinants once per class and iteration.
 //   * k_vis_prototypes: the accuracy tail's cluster prototypes (one-hot statistics of the predictions) of D-dim rows.
 
 namespace tclip {
@@ -23,13 +26,23 @@ namespace tclip {
 // chunks of 512 elements, which is where torch's 16-step cascade block ends: the chunks are restaged for every group of
 // n_waves queries, so that each wavefront carries one query's 64 accumulators across the chunk boundary and no more.
 // Rows of fewer than 8 elements take torch's 4-way scalar row sum instead (cascade_sum: no vector is complete).
-constexpr int kVisTile = 64, kVisChunk = 512, kVisThreads = 1024;
+//
+// kCov, EM_GAUSSIAN_COV's E-step (em_gaussian_cov.py:106-129): every squared difference is multiplied by the cluster's inverse
+// variance s[t,k,d] before it is added (square and product rounded one after the other, as diff.square_().mul_(s) does), and
+// logit[t,q,k] = -1/2 sum + det[t,k], det the half log-determinant k_vis_logdet left.  The same sums in the same order; a second
+// LDS tile holds s, so a chunk is 256 elements (8 of the cascade's 16 steps: the dumps fall on chunk ends all the same) and
+// rows of more than 256 elements are restaged for every group of queries.
+constexpr int kVisTile = 64, kVisChunk = 512, kVisCovChunk = 256, kVisThreads = 1024;
 constexpr int kVisLds = kVisTile * (kVisChunk + 1) * (int)sizeof(float);
+constexpr int kVisCovLds = 2 * kVisTile * (kVisCovChunk + 1) * (int)sizeof(float);
 
+template <bool kCov>
 __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restrict__ w, const float* __restrict__ z,
                                                           const uint8_t* __restrict__ need, int Q, int K, int D, float pre,
-                                                          float temperature, float* __restrict__ logit0) {
-    extern __shared__ float wt[];                                   // [kVisTile][stride]
+                                                          float temperature, float* __restrict__ logit0,
+                                                          const float* __restrict__ s, const float* __restrict__ det) {
+    extern __shared__ float wt[];                                   // [kVisTile][stride]; kCov: s's tile behind it
+    constexpr int kChunk = kCov ? kVisCovChunk : kVisChunk, kChunkSteps = kChunk / 32;
     const int t = blockIdx.y, k0 = blockIdx.x * kVisTile;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = blockDim.x >> 6;
@@ -37,24 +50,35 @@ __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restric
     const bool ok = k < K && need[(size_t)t * K + k];
     if (!__syncthreads_or(ok)) return;                              // no class of the tile moved
     const int rows = K - k0 < kVisTile ? K - k0 : kVisTile;
-    const int n_chunks = D > kVisChunk ? 2 : 1;
-    const int stride = (D < kVisChunk ? D : kVisChunk) | 1;
+    const int n_chunks = (D + kChunk - 1) / kChunk;
+    const int stride = (D < kChunk ? D : kChunk) | 1;
+    const int s_off = kVisTile * stride;                            // kCov: s's element lies s_off words behind w's
     const float* wsrc = w + ((size_t)t * K + k0) * D;
-    auto stage = [&](int c0, int clen) {                            // rows x clen words, eight loads in flight per thread
+    const float* ssrc = kCov ? s + ((size_t)t * K + k0) * D : nullptr;
+    auto stage_one = [&](const float* src, float* dst, int c0, int clen) {     // rows x clen words, eight loads in flight per thread
         const int n = rows * clen, step = blockDim.x;
         for (int i0 = threadIdx.x; i0 < n; i0 += 8 * step) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int i = i0 + j * step;
-                v[j] = i < n ? wsrc[(size_t)(i / clen) * D + c0 + i % clen] : 0.0f;
+                v[j] = i < n ? src[(size_t)(i / clen) * D + c0 + i % clen] : 0.0f;
             }
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int i = i0 + j * step;
-                if (i < n) wt[(i / clen) * stride + i % clen] = v[j];
+                if (i < n) dst[(i / clen) * stride + i % clen] = v[j];
             }
         }
+    };
+    auto stage = [&](int c0, int clen) {
+        stage_one(wsrc, wt, c0, clen);
+        if (kCov) stage_one(ssrc, wt + s_off, c0, clen);
+    };
+    // one term of the row sum: element d of the lane's row at p[d]
+    auto term = [&](const float* p, int d, float zv) {
+        const float df = p[d] - zv;
+        return kCov ? (df * df) * p[s_off + d] : df * df;
     };
     const float* wl = wt + (lane < rows ? lane : rows - 1) * stride;    // lanes beyond the last class recompute it; nothing is stored
     const int vec_size = D >> 3, size_ilp = vec_size >> 2, nleft = vec_size - 4 * size_ilp, ntail = D - 8 * vec_size;
@@ -69,23 +93,20 @@ __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restric
 #pragma unroll
         for (int sl = 0; sl < 32; sl++) a0[sl] = a1[sl] = 0.0f;
         for (int c = 0; c < n_chunks; c++) {
-            const int c0 = c * kVisChunk;
+            const int c0 = c * kChunk;
             if (n_chunks > 1) {
                 __syncthreads();                                    // every wavefront is done with the previous chunk
-                stage(c0, c == 0 ? kVisChunk : D - kVisChunk);
+                stage(c0, D - c0 < kChunk ? D - c0 : kChunk);
                 __syncthreads();
             }
             const float* wc = wl - c0;                              // element d of the row at wc[d]
-            const int m_end = size_ilp < (c + 1) * 16 ? size_ilp : (c + 1) * 16;
-            for (int m = c * 16; m < m_end; m++) {
+            const int m_end = size_ilp < (c + 1) * kChunkSteps ? size_ilp : (c + 1) * kChunkSteps;
+            for (int m = c * kChunkSteps; m < m_end; m++) {
                 float zc[32];
 #pragma unroll
                 for (int sl = 0; sl < 32; sl++) zc[sl] = zq[32 * m + sl];
 #pragma unroll
-                for (int sl = 0; sl < 32; sl++) {
-                    const float df = wc[32 * m + sl] - zc[sl];
-                    a0[sl] += df * df;
-                }
+                for (int sl = 0; sl < 32; sl++) a0[sl] += term(wc, 32 * m + sl, zc[sl]);
                 if ((m & 15) == 15) {                               // end of a 16-step cascade block: level 0 into level 1
 #pragma unroll
                     for (int sl = 0; sl < 32; sl++) { a1[sl] += a0[sl]; a0[sl] = 0.0f; }
@@ -93,7 +114,7 @@ __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restric
             }
         }
         if (q >= Q) continue;                                       // wave-uniform; after the last barrier of this query group
-        const float* wc = wl - (n_chunks - 1) * kVisChunk;          // the leftovers and the tail lie in the last chunk
+        const float* wc = wl - (n_chunks - 1) * kChunk;             // the leftovers and the tail lie in the last chunk
         float fin = 0.0f;
         if (vec_size == 0) {                                        // D < 8: row_sum of 4 interleaved scalar partials
             const int ilp = D >> 2;
@@ -101,10 +122,10 @@ __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restric
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 float x = 0.0f;
-                if (r < 4 * ilp) { const float df = wc[r] - zq[r]; x += df * df; }
+                if (r < 4 * ilp) x += term(wc, r, zq[r]);
                 p[r] = x;
             }
-            for (int i = 4 * ilp; i < D; i++) { const float df = wc[i] - zq[i]; p[0] += df * df; }
+            for (int i = 4 * ilp; i < D; i++) p[0] += term(wc, i, zq[i]);
             fin = p[0];
             fin += p[1];
             fin += p[2];
@@ -115,15 +136,9 @@ __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restric
             int d = 32 * size_ilp;
             for (int i = 0; i < nleft; i++, d += 8) {               // whole vectors beyond the 4-way part join accumulator 0
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float df = wc[d + j] - zq[d + j];
-                    a0[j] += df * df;
-                }
+                for (int j = 0; j < 8; j++) a0[j] += term(wc, d + j, zq[d + j]);
             }
-            for (int i = 0; i < ntail; i++) {                       // the D mod 8 tail first
-                const float df = wc[d + i] - zq[d + i];
-                fin += df * df;
-            }
+            for (int i = 0; i < ntail; i++) fin += term(wc, d + i, zq[d + i]);     // the D mod 8 tail first
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 float p0 = a0[j];
@@ -133,10 +148,11 @@ __global__ __launch_bounds__(kVisThreads) void k_vis_dist(const float* __restric
                 fin += p0;
             }
         }
-        if (ok) logit0[((size_t)t * Q + q) * K + k] = temperature * (pre * fin);
+        if (ok) logit0[((size_t)t * Q + q) * K + k] = kCov ? -0.5f * fin + det[(size_t)t * K + k] : temperature * (pre * fin);
     }
 }
 
+template <bool kCov>
 static bool vis_dist_lds_raised() {
     struct Seen { int device; bool ok; };
     static std::mutex mu;
@@ -146,7 +162,8 @@ static bool vis_dist_lds_raised() {
     std::lock_guard<std::mutex> lock(mu);
     for (auto& e : seen)
         if (e.device == dev) return e.ok;
-    const bool ok = hipFuncSetAttribute((const void*)k_vis_dist, hipFuncAttributeMaxDynamicSharedMemorySize, kVisLds) == hipSuccess;
+    const bool ok = hipFuncSetAttribute((const void*)k_vis_dist<kCov>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        kCov ? kVisCovLds : kVisLds) == hipSuccess;
     seen.push_back(Seen{dev, ok});
     return ok;
 }
@@ -155,9 +172,55 @@ static int launch_vis_dist(int T, hipStream_t st, const float* w, const float* z
                            float pre, float temperature, float* logit0) {
     const int stride = (D < kVisChunk ? D : kVisChunk) | 1;
     const size_t lds = (size_t)kVisTile * stride * sizeof(float);
-    if (lds > 65536 && !vis_dist_lds_raised()) return fail(TCLIP_ERR_HIP, "k_vis_dist: cannot raise the LDS limit to %s bytes", "131328");
-    hipLaunchKernelGGL(k_vis_dist, dim3((K + kVisTile - 1) / kVisTile, T), dim3(kVisThreads), lds, st, w, z, need, Q, K, D, pre,
-                       temperature, logit0);
+    if (lds > 65536 && !vis_dist_lds_raised<false>()) return fail(TCLIP_ERR_HIP, "k_vis_dist: cannot raise the LDS limit to %s bytes", "131328");
+    hipLaunchKernelGGL(k_vis_dist<false>, dim3((K + kVisTile - 1) / kVisTile, T), dim3(kVisThreads), lds, st, w, z, need, Q, K, D, pre,
+                       temperature, logit0, (const float*)nullptr, (const float*)nullptr);
+    return TCLIP_OK;
+}
+
+// ---- EM_GAUSSIAN_COV's half log-determinants ------------------------------------------------------------------------------
+// det[t,k] = 1/2 sum_d log(s[t,k,d] + eps) for the classes `need` marks, once per class and iteration: the sum in torch's
+// last-dim order (dsum_inner_serial's, its eight vector lanes on eight threads), the logarithm MKL's vsLn as in k_cov_logits_rows.
+// One wavefront per class row: the logarithms are taken 64 elements at a time and parked in LDS.
+constexpr int kVisDetWaves = 4, kVisDetMaxD = 1024;
+
+__global__ __launch_bounds__(64 * kVisDetWaves) void k_vis_logdet(const float* __restrict__ s, const uint8_t* __restrict__ need, int TK,
+                                                                  int D, float* __restrict__ det) {
+    __shared__ float lg[kVisDetWaves][kVisDetMaxD];
+    __shared__ float part[kVisDetWaves][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x * kVisDetWaves + wave;
+    const bool on = row < TK && need[row < TK ? row : 0];
+    float* l = lg[wave];
+    if (on) {
+        const float* sr = s + (size_t)row * D;
+        for (int d = lane; d < D; d += 64) l[d] = log_f32(sr[d] + kEpsF);
+    }
+    __syncthreads();
+    auto get = [&](int d) { return l[d]; };
+    if (on && D >= 8 && lane < 8) part[wave][lane] = dsum_inner_lane(D, lane, get);
+    __syncthreads();
+    if (!on || lane != 0) return;
+    float fin = 0.0f;
+    if (D < 8) {
+        fin = dsum_ilp4(D, get);
+    } else {
+        for (int d = (D >> 3) * 8; d < D; d++) fin += l[d];
+        for (int jj = 0; jj < 8; jj++) fin += part[wave][jj];
+    }
+    det[row] = 0.5f * fin;
+}
+
+// logit[t,q,k] = -1/2 sum_d (w[t,k,d] - z[t,q,d])^2 s[t,k,d] + 1/2 sum_d log(s[t,k,d] + eps) for the classes `need` marks
+static int launch_vis_cov_logits(int T, hipStream_t st, const float* w, const float* s, const float* z, const uint8_t* need, int Q,
+                                 int K, int D, float* det, float* logit0) {
+    const int TK = T * K;
+    hipLaunchKernelGGL(k_vis_logdet, dim3((TK + kVisDetWaves - 1) / kVisDetWaves), dim3(64 * kVisDetWaves), 0, st, s, need, TK, D, det);
+    const int stride = (D < kVisCovChunk ? D : kVisCovChunk) | 1;
+    const size_t lds = (size_t)2 * kVisTile * stride * sizeof(float);
+    if (lds > 65536 && !vis_dist_lds_raised<true>()) return fail(TCLIP_ERR_HIP, "k_vis_dist: cannot raise the LDS limit to %s bytes", "131584");
+    hipLaunchKernelGGL(k_vis_dist<true>, dim3((K + kVisTile - 1) / kVisTile, T), dim3(kVisThreads), lds, st, w, z, need, Q, K, D, 0.0f,
+                       0.0f, logit0, s, (const float*)det);
     return TCLIP_OK;
 }
 
@@ -171,6 +234,10 @@ static int launch_vis_dist(int T, hipStream_t st, const float* w, const float* z
 // (few_shot/bdcspn.py:139-141), is the plain quotient.  Q is then any row count (BD-CSPN: S + n_query augmented rows).
 // The rows kernel: one thread per column d, kVisRows classes per thread (u wave-uniform, each z value read once per
 // kVisRows classes), for the classes whose columns all take the cascade order; k_vis_mstats_one the last few.
+// kCov: the inverse diagonal covariances of EM_GAUSSIAN_COV (em_gaussian_cov.py:172-193) for the rows `live` marks,
+//   y[t,k,d] = cs[t,k] / max(sum_q (wc[t,k,d] - z[t,q,d])^2 * u[t,q,k], eps),
+// the same outer sum over the same K*D columns with the square and the product by u rounded one after the other
+// (k_mstats*<true> for D = K); `mode` is 0.
 constexpr int kVisRows = 16;
 
 __device__ __forceinline__ void vis_mstats_put(float* y, size_t idx, float s, float c, bool alive, int mode,
@@ -182,10 +249,11 @@ __device__ __forceinline__ void vis_mstats_put(float* y, size_t idx, float s, fl
     else if (mode == 1) y[idx] = r * 0.0f;
 }
 
+template <bool kCov>
 __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, const float* __restrict__ z,
                                                    const float* __restrict__ cs, const uint8_t* __restrict__ live, int Q, int K,
                                                    int D, int mode, float* __restrict__ y, const float* __restrict__ sup,
-                                                   const float* __restrict__ cnt) {
+                                                   const float* __restrict__ cnt, const float* __restrict__ wc) {
     const int t = blockIdx.z, k0 = blockIdx.y * kVisRows;
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
@@ -198,6 +266,16 @@ __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, 
     const float* ut = u + (size_t)t * Q * K + k0;
     const float* zt = z + (size_t)t * Q * D + d;
     const int nj = K - k0 < kVisRows ? K - k0 : kVisRows;
+    float wcv[kVisRows];
+#pragma unroll
+    for (int j = 0; j < kVisRows; j++) wcv[j] = kCov && j < nj ? wc[((size_t)t * K + k0 + j) * D + d] : 0.0f;
+    auto term = [&](int j, float uv, float fv) {
+        if (kCov) {
+            const float df = wcv[j] - fv;
+            return (df * df) * uv;
+        }
+        return uv * fv;
+    };
     const int cl = dev_ceil_log2(Q) / 4;
     const int level_power = cl > 4 ? cl : 4;
     const int step = 1 << level_power, mask = step - 1;
@@ -209,7 +287,7 @@ __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, 
         for (int jj = 0; jj < step; ++jj, ++i) {
             const float fv = zt[(size_t)i * D];
 #pragma unroll
-            for (int j = 0; j < kVisRows; j++) a0[j] += (j < nj ? ut[(size_t)i * K + j] : 0.0f) * fv;
+            for (int j = 0; j < kVisRows; j++) a0[j] += term(j, j < nj ? ut[(size_t)i * K + j] : 0.0f, fv);
         }
         const bool l2 = (i & (mask << level_power)) == 0, l3 = l2 && (i & (mask << (2 * level_power))) == 0;
 #pragma unroll
@@ -222,7 +300,7 @@ __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, 
     for (; i < Q; ++i) {
         const float fv = zt[(size_t)i * D];
 #pragma unroll
-        for (int j = 0; j < kVisRows; j++) a0[j] += (j < nj ? ut[(size_t)i * K + j] : 0.0f) * fv;
+        for (int j = 0; j < kVisRows; j++) a0[j] += term(j, j < nj ? ut[(size_t)i * K + j] : 0.0f, fv);
     }
 #pragma unroll
     for (int j = 0; j < kVisRows; j++) {
@@ -232,14 +310,19 @@ __global__ __launch_bounds__(64) void k_vis_mstats(const float* __restrict__ u, 
         s += a1[j];
         s += a2[j];
         s += a3[j];
+        if (kCov) {
+            if (live[row]) y[row * D + d] = cs[row] / (s < kEpsF ? kEpsF : s);
+            continue;
+        }
         vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode, sup, cnt, row);
     }
 }
 
 // One output per thread, any column (the rows of the 4-way row-sum columns: at most the last 31 of K*D).
+template <bool kCov>
 __global__ void k_vis_mstats_one(const float* __restrict__ u, const float* __restrict__ z, const float* __restrict__ cs,
                                  const uint8_t* __restrict__ live, int Q, int K, int D, int k_first, int mode, float* __restrict__ y,
-                                 const float* __restrict__ sup, const float* __restrict__ cnt) {
+                                 const float* __restrict__ sup, const float* __restrict__ cnt, const float* __restrict__ wc) {
     const int t = blockIdx.z, k = blockIdx.y + k_first;
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
@@ -247,22 +330,43 @@ __global__ void k_vis_mstats_one(const float* __restrict__ u, const float* __res
     if (mode == 0 && !live[row]) return;
     const float* ut = u + (size_t)t * Q * K + k;
     const float* zt = z + (size_t)t * Q * D + d;
-    const float s = dsum_outer(Q, (long)k * D + d, (long)K * D, [&](int q) { return ut[(size_t)q * K] * zt[(size_t)q * D]; });
+    const float wcv = kCov ? wc[row * D + d] : 0.0f;
+    const float s = dsum_outer(Q, (long)k * D + d, (long)K * D, [&](int q) {
+        if (kCov) {
+            const float df = wcv - zt[(size_t)q * D];
+            return (df * df) * ut[(size_t)q * K];
+        }
+        return ut[(size_t)q * K] * zt[(size_t)q * D];
+    });
+    if (kCov) {
+        y[row * D + d] = cs[row] / (s < kEpsF ? kEpsF : s);      // mode 0: the row is live
+        return;
+    }
     vis_mstats_put(y, row * D + d, s, cs[row], live[row] != 0, mode, sup, cnt, row);
 }
 
-static void launch_vis_mstats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, int T, int Q,
-                              int K, int D, int mode, float* y, const float* sup = nullptr, const float* cnt = nullptr) {
+template <bool kCov>
+static void launch_vis_mstats_mode(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, int T, int Q,
+                                   int K, int D, int mode, float* y, const float* sup, const float* cnt, const float* wc) {
     const long ncols = (long)K * D;
     const int full_rows = ncols >= 8 ? (int)(((ncols / 32) * 32) / D) : 0;     // rows 0 .. full_rows-1 are all-cascade
     const int groups = full_rows / kVisRows;
     if (groups > 0)
-        hipLaunchKernelGGL(k_vis_mstats, dim3((D + 63) / 64, groups, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, mode, y, sup,
-                           cnt);
+        hipLaunchKernelGGL(k_vis_mstats<kCov>, dim3((D + 63) / 64, groups, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, mode, y, sup,
+                           cnt, wc);
     const int k_first = groups * kVisRows;
     if (k_first < K)
-        hipLaunchKernelGGL(k_vis_mstats_one, dim3((D + 63) / 64, K - k_first, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, k_first,
-                           mode, y, sup, cnt);
+        hipLaunchKernelGGL(k_vis_mstats_one<kCov>, dim3((D + 63) / 64, K - k_first, T), dim3(64), 0, st, u, z, cs, live, Q, K, D, k_first,
+                           mode, y, sup, cnt, wc);
+}
+static void launch_vis_mstats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, int T, int Q,
+                              int K, int D, int mode, float* y, const float* sup = nullptr, const float* cnt = nullptr) {
+    launch_vis_mstats_mode<false>(st, u, z, cs, live, T, Q, K, D, mode, y, sup, cnt, nullptr);
+}
+// EM_GAUSSIAN_COV: s = cs / max(sum_q (w - z_q)^2 u, eps) for the rows `live` marks
+static void launch_vis_cov_stats(hipStream_t st, const float* u, const float* z, const float* cs, const uint8_t* live, const float* w,
+                                 int T, int Q, int K, int D, float* s) {
+    launch_vis_mstats_mode<true>(st, u, z, cs, live, T, Q, K, D, 0, s, nullptr, nullptr, w);
 }
 
 // ---- accuracy-tail prototypes -----------------------------------------------------------------------------------------

@@ -68,6 +68,8 @@ _SIGNATURES = {
     "tclip_visual_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
     "tclip_kmeans_visual_run": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_float,
                                                _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_em_gaussian_cov_visual_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_em_gaussian_cov_visual_run": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32] + [_P] * 8 + [ctypes.c_size_t, _P]),
     "tclip_cluster_prototypes_visual": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P] * 6),
     "tclip_visual_init": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P]),
     "tclip_paddle_visual_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),

@@ -494,6 +494,30 @@ def run_em_gaussian_visual(x_q, u0, *, iters, temperature, lambd):
     return u, v, w, preds
 
 
+def run_em_gaussian_cov_visual(x_q, u0, *, iters, lambd):
+    """EM_GAUSSIAN_COV on visual features: x_q (T,Q,D) raw embeddings, D <= 1024, u0 (T,Q,K) the initial responsibilities
+    (visual_init) -> (u (T,Q,K), v (T,K), w (T,K,D), s (T,K,D), preds (T,Q) i32), cuda, not synchronised.  Accuracy:
+    clustering_accuracy_visual."""
+    if x_q.dim() != 3:
+        raise ValueError("x_q must be (T,Q,D)")
+    T, Q, D = x_q.shape
+    if u0.dim() != 3 or u0.shape[0] != T or u0.shape[1] != Q:
+        raise ValueError("u0 must be (T,Q,K) with the T and Q of x_q")
+    if D > 1024:
+        raise ValueError(f"embeddings of at most 1024 elements, got {D}")
+    for t, name in ((x_q, "x_q"), (u0, "u0")):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a cuda tensor: the engine has no CPU path")
+    x_q = _query(x_q)
+    u0 = u0.to(x_q.device).contiguous().float()
+    K = u0.shape[2]
+    c, u, w, preds = _kmeans_call(x_q, K, "tclip_em_gaussian_cov_visual_workspace_bytes", ctypes.c_int32(D), iters=iters, lambd=lambd)
+    v, s = c.empty(T, K), c.empty(T, K, D)
+    c.launch("tclip_em_gaussian_cov_visual_run", lambda ws, n, st: (ctypes.c_int32(D), _ptr(x_q), _ptr(u0), _ptr(u), _ptr(v), _ptr(w),
+                                                                    _ptr(s), _ptr(preds), ws, n, st))
+    return u, v, w, s, preds
+
+
 def _support_visual(x_q, x_s, y_s, n_class):
     """_support for D-wide rows: the width of x_s is checked against D, the labels against n_class (on the device: one
     reduction, its result read back, so that no kernel ever sees a label outside 0..n_class-1)."""
