@@ -37,7 +37,9 @@ extern "C" {
  *    tclip_alpha_tim_visual_workspace_bytes, tclip_alpha_tim_visual_run, tclip_laplacian_shot_visual_workspace_bytes,
  *    tclip_laplacian_shot_visual_run;
  *    tclip_match_clusters_workspace_bytes, tclip_match_clusters;
- *    tclip_em_gaussian_cov_visual_workspace_bytes, tclip_em_gaussian_cov_visual_run
+ *    tclip_em_gaussian_cov_visual_workspace_bytes, tclip_em_gaussian_cov_visual_run;
+ *    tclip_gather_task_rows, tclip_paddle_tasks_workspace_bytes, tclip_paddle_run_tasks,
+ *    tclip_paddle_visual_tasks_workspace_bytes, tclip_paddle_visual_run_tasks
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -178,6 +180,22 @@ int tclip_host_threads(void);
 int tclip_gather_rows(const float* table, int64_t n_rows, int32_t n_class, const int64_t* idx,
                       int64_t n_out, float* out, void* stream);
 
+/* The fused task builder of the few-shot task-batch loop: the reference's `all_features[indices, :]`
+ * (src/eval_few_shot.py:233-241) followed by get_task's `data[:, unique_labels]` (src/task_generator_few_shot.py:41-52) in one
+ * pass over the table rows,
+ *     out[r, d] = table[idx[r], cols ? cols[(r / rows_per_task) * width + d] : d].
+ *   table device [n_rows, width] f32;  idx device [n_out] i64;  cols device [n_out / rows_per_task, width] i32 (one column
+ *   permutation per task of rows_per_task rows) or NULL for the identity;  out device [n_out, width] f32.
+ * A pure copy: every bit of every float is preserved, NaN payloads included.  An idx value outside [0, n_rows) is never
+ * dereferenced and leaves its row of `out` unwritten, as tclip_gather_rows does; the values of cols are the caller's to check
+ * (tclip_check_task_indices).  A null table, idx or out, n_rows < 1, width < 1, rows_per_task < 1, n_out < 0, and n_out not a
+ * multiple of rows_per_task when cols is given are TCLIP_ERR_ARG before any launch.  Without cols, rows of a multiple of 4
+ * floats in 16-byte aligned arrays move in 16-byte words; with cols the stores stay coalesced and the permuted loads hit the
+ * row just fetched. */
+int tclip_gather_task_rows(const float* table, int64_t n_rows, int32_t width, const int64_t* idx /*[n_out]*/, int32_t rows_per_task,
+                           const int32_t* cols /*[n_out/rows_per_task, width] or NULL*/, int64_t n_out, float* out /*[n_out, width]*/,
+                           void* stream);
+
 /* SOFT_KMEANS on probability features (reference: src/methods/zero_shot/soft_kmeans.py:105-220;
  * BASELINE config 3's second method).  Uses p->n_batches * p->tasks_per_batch tasks, n_query,
  * n_class and iters; n_support must be 0; the other fields are ignored.  temperature = args.T.
@@ -247,6 +265,29 @@ size_t tclip_paddle_workspace_bytes(const tclip_problem* p);
 int tclip_paddle_run(const tclip_problem* p, const float* x_q, const float* x_s, const int64_t* y_s, float lambd,
                      float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
                      void* stream);
+
+/* PADDLE fed from the feature TABLES of the task-batch loop (see tclip_em_dirichlet_run_tasks for `src` and `y_s`): row r of
+ * task t is table[idx[t,r]], on probability features with its columns permuted by src->cols[t].  The support rows are read in
+ * place by the kernel that sums them per class - PADDLE reads them exactly once - and x_s [T,S,D] is never built; the query
+ * rows, read in every iteration, are gathered once into the workspace (k_gather_task_rows), so the workspace is that of the
+ * dense entry plus [T,Q,D] floats and does not depend on n_support.  Results are those of tclip_paddle_run /
+ * tclip_paddle_visual_run on the materialised tensors, bit for bit.
+ *   src->table_q device [rows_q, D] f32, src->q_idx device [T, Q] i64;  src->table_s device [rows_s, D] f32, src->s_idx device
+ *   [T, S] i64;  D = n_class and src->cols device [T, K] i32 or NULL (probability features), D = dim and src->cols == NULL
+ *   (visual features: the reference permutes no columns there, a non-NULL cols is TCLIP_ERR_ARG);
+ *   y_s device [T, S] i64: the support labels after get_task's re-indexing (visual features: as they are), in 0..n_class-1;
+ *   u, v, w, preds, lambd as for the dense entries (w device [T, K, D]).
+ * Limits and checks are the dense entries': n_support >= 1, n_class in 2..1024, dim in 1..1024, null pointers
+ * (TCLIP_ERR_ARG), workspace of tclip_paddle[_visual]_tasks_workspace_bytes bytes, 256-byte aligned (TCLIP_ERR_WORKSPACE; the
+ * query returns 0 on bad input).  The entries do not know the tables' row counts: call tclip_check_task_indices on the index
+ * tensors and cols first (the Python binding does). */
+size_t tclip_paddle_tasks_workspace_bytes(const tclip_problem* p);
+int tclip_paddle_run_tasks(const tclip_problem* p, const tclip_task_source* src, const int64_t* y_s, float lambd,
+                           float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream);
+size_t tclip_paddle_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_paddle_visual_run_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s,
+                                  float lambd, float* u, float* v, float* w, int32_t* preds,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ALPHA_TIM on probability features (reference: src/methods/few_shot/tim.py:192-322; feature dimension =
  * n_class).  Weights start as the class means of the support set; each of `iters` iterations takes one

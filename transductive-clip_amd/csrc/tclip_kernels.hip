@@ -28,6 +28,7 @@
 //   k_kl_centroids, k_kl_divergences, k_argmin_rows, k_hard_assign   KL_KMEANS / HARD_KMEANS assignment
 //   k_support_stats, k_div_rows   support class means (few-shot EM-Dirichlet, PADDLE, BDCSPN)
 //   k_gather_log_features   u = z and log z read from a feature table through index tensors (tclip_em_dirichlet_run_tasks)
+//   k_gather_rows, k_gather_task_rows   task construction from a feature table: rows, and rows with a column permutation per task
 //   k_col_mean, k_bdcspn_normalize, k_bdcspn_eta   BD-CSPN normalisation (torch's norm order) and query shift
 //   k_argmax_rows   inductive CLIP baseline
 #include <hip/hip_runtime.h>
@@ -2560,6 +2561,56 @@ __global__ void k_gather_rows(const float* __restrict__ table, int64_t n_rows, i
     for (int d = threadIdx.x; d < K; d += blockDim.x) out[r * K + d] = table[src * K + d];
 }
 
+// The fused task builder (tclip_gather_task_rows): out[r, d] = table[idx[r], cols ? cols[r / rows_per_task, d] : d], the
+// task-batch loop's `all_features[indices, :]` and get_task's `data[:, unique_labels]` in one pass.  A pure copy of 32-bit
+// words (NaN payloads survive).  `lanes` threads (a power of two, 1..256) share a row, 256 / lanes rows a block; consecutive
+// lanes write consecutive words of the output row, so the stores are coalesced whatever `cols` does to the loads (a table row
+// is at most 4 KB and stays in cache while its permutation is read).  kVec: no cols, width a multiple of 4 and both arrays
+// 16-byte aligned - 16-byte loads and stores, `width4` = width / 4.  A row whose index lies outside [0, n_rows) is not read
+// and not written.
+template <bool kVec>
+__global__ __launch_bounds__(256) void k_gather_task_rows(const uint32_t* __restrict__ table, int64_t n_rows, int width,
+                                                          const int64_t* __restrict__ idx, int rows_per_task,
+                                                          const int32_t* __restrict__ cols, int64_t n_out, int lanes,
+                                                          uint32_t* __restrict__ out) {
+    const int rows_per_block = blockDim.x / lanes;
+    const int lane = threadIdx.x % lanes;
+    for (int64_t r = (int64_t)blockIdx.x * rows_per_block + threadIdx.x / lanes; r < n_out; r += (int64_t)gridDim.x * rows_per_block) {
+        const int64_t src = idx[r];
+        if (src < 0 || src >= n_rows) continue;
+        if (kVec) {
+            const int width4 = width >> 2;
+            const uint4* in4 = reinterpret_cast<const uint4*>(table + src * width);
+            uint4* out4 = reinterpret_cast<uint4*>(out + r * width);
+            for (int d = lane; d < width4; d += lanes) out4[d] = in4[d];
+        } else if (cols) {
+            const int32_t* c = cols + (r / rows_per_task) * width;
+            for (int d = lane; d < width; d += lanes) out[r * width + d] = table[src * width + c[d]];
+        } else {
+            for (int d = lane; d < width; d += lanes) out[r * width + d] = table[src * width + d];
+        }
+    }
+}
+
+// launches k_gather_task_rows; the arguments have been checked
+static void launch_gather_task_rows(hipStream_t st, const float* table, int64_t n_rows, int width, const int64_t* idx, int rows_per_task,
+                                    const int32_t* cols, int64_t n_out, float* out) {
+    if (n_out == 0) return;
+    const bool vec = !cols && (width & 3) == 0 && (((uintptr_t)table | (uintptr_t)out) & 15) == 0;
+    const int per_lane = vec ? width >> 2 : width;
+    int lanes = 1;
+    while (lanes < 256 && lanes < per_lane) lanes <<= 1;
+    const int rows_per_block = 256 / lanes;
+    int64_t blocks = (n_out + rows_per_block - 1) / rows_per_block;
+    if (blocks > (1 << 20)) blocks = 1 << 20;
+    if (vec)
+        hipLaunchKernelGGL(k_gather_task_rows<true>, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)table, n_rows, width, idx,
+                           rows_per_task, cols, n_out, lanes, (uint32_t*)out);
+    else
+        hipLaunchKernelGGL(k_gather_task_rows<false>, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)table, n_rows, width, idx,
+                           rows_per_task, cols, n_out, lanes, (uint32_t*)out);
+}
+
 // ------------------------------------------------------------------------------------------
 // Probability-feature front-end (reference: src/utils.py:287-290): for every image embedding f,
 //   z = softmax_k( (T * f/||f||) . text_k ),  text_k unit-norm class text embeddings.
@@ -4050,6 +4101,19 @@ int tclip_gather_rows(const float* table, int64_t n_rows, int32_t K, const int64
     if (!table || !idx || !out || n_rows < 1 || K < 1 || n_out < 0) return fail(TCLIP_ERR_ARG, "bad argument to tclip_gather_rows");
     if (n_out == 0) return TCLIP_OK;
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n_out), dim3(128), 0, (hipStream_t)stream, table, n_rows, K, idx, n_out, out);
+    TCLIP_HIP(hipGetLastError());
+    return TCLIP_OK;
+}
+
+int tclip_gather_task_rows(const float* table, int64_t n_rows, int32_t width, const int64_t* idx, int32_t rows_per_task,
+                           const int32_t* cols, int64_t n_out, float* out, void* stream) {
+    if (!table || !idx || !out) return fail(TCLIP_ERR_ARG, "tclip_gather_task_rows: null pointer argument");
+    if (n_rows < 1 || width < 1 || rows_per_task < 1 || n_out < 0)
+        return fail(TCLIP_ERR_ARG, "tclip_gather_task_rows: n_rows, width and rows_per_task must be positive, n_out non-negative");
+    if (cols && n_out % rows_per_task != 0)
+        return fail(TCLIP_ERR_ARG, "tclip_gather_task_rows: n_out must be a multiple of rows_per_task when cols is given");
+    if (n_out == 0) return TCLIP_OK;
+    launch_gather_task_rows((hipStream_t)stream, table, n_rows, width, idx, rows_per_task, cols, n_out, out);
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
 }

@@ -60,10 +60,11 @@ struct FeatureSpace {
         return TCLIP_OK;
     }
 
-    // sup[t,k,:] = sum of the support rows of class k, cnt[t,k] = their number
-    void support_stats(hipStream_t st, const float* x_s, const int64_t* y_s, int T, int S, int K, float* sup, float* cnt) const {
+    // sup[t,k,:] = sum of the support rows of class k, cnt[t,k] = their number; the rows a dense [T, S, D] tensor or table
+    // rows read in place (visual features: x_s.cols is not read)
+    void support_stats(hipStream_t st, const RowSrc& x_s, const int64_t* y_s, int T, int S, int K, float* sup, float* cnt) const {
         if (visual) launch_vis_support_stats(st, x_s, y_s, T, S, K, D, sup, cnt);
-        else hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(x_s), y_s, S, K, 0, sup, cnt);
+        else hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, x_s, y_s, S, K, 0, sup, cnt);
     }
 };
 
@@ -111,6 +112,18 @@ struct PaddleWs {
         w.live = take(T * K);
         w.logit = take(T * Q * K * 4);
         w.total = o;
+        return w;
+    }
+};
+
+// PADDLE fed from the feature tables: PaddleWs and the query rows [T, Q, D], gathered once; nothing depends on n_support
+struct PaddleTasksWs {
+    size_t xq, total;
+    static PaddleTasksWs layout(const tclip_problem& p, int dim) {
+        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, Q = p.n_query, D = dim;
+        PaddleTasksWs w;
+        w.xq = PaddleWs::layout(p, dim).total;
+        w.total = w.xq + align_up(T * Q * D * 4);
         return w;
     }
 };
@@ -234,7 +247,8 @@ static int em_gaussian_cov_loop(const FeatureSpace& sp, const tclip_problem& p, 
 }
 
 // ---- PADDLE (SURVEY.md section 8f, F4): few-shot soft k-means with the class-proportion penalty -------------------------
-static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const float* x_s, const int64_t* y_s,
+// The support set is read exactly once, for the class sums: `x_s` is a dense tensor or table rows read in place.
+static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const RowSrc& x_s, const int64_t* y_s,
                        float lambd, float* u, float* v, float* w, int32_t* preds, char* ws, hipStream_t st) {
     const PaddleWs o = PaddleWs::layout(p, sp.D);
     const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
@@ -293,7 +307,7 @@ static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const flo
     normalize(x_s, x_s, S, S, norm_type, (const float*)mean, (const float*)nullptr, zs);
     normalize(x_q, x_q, Q, Q, norm_type, (const float*)mean, (const float*)nullptr, zq);
     // initial prototypes: support class means (:117-120), L2-normalised for get_logits (:50)
-    sp.support_stats(st, zs, y_s, T, S, K, sup, cnt);
+    sp.support_stats(st, dense_rows(zs), y_s, T, S, K, sup, cnt);
     hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
                        (size_t)TK * D, D, prototypes);
     normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
@@ -499,7 +513,39 @@ int tclip_paddle_run(const tclip_problem* pp, const float* x_q, const float* x_s
     if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
     if (p.n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE");
     if (int rc = check_workspace(workspace, workspace_bytes, PaddleWs::layout(p, p.n_class).total, "tclip_paddle_workspace_bytes")) return rc;
-    return paddle_loop(FeatureSpace{p.n_class, false}, p, x_q, x_s, y_s, lambd, u, v, w, preds, (char*)workspace, (hipStream_t)stream);
+    return paddle_loop(FeatureSpace{p.n_class, false}, p, x_q, dense_rows(x_s), y_s, lambd, u, v, w, preds, (char*)workspace,
+                       (hipStream_t)stream);
+}
+
+// PADDLE from the feature tables on rows of `dim` elements: the queries are gathered (and, probability features, permuted)
+// once into the workspace, the support rows are read in place by the support statistics; then paddle_loop as it stands
+static int paddle_run_tasks(const FeatureSpace& sp, const tclip_problem& p, const tclip_task_source* src, const int64_t* y_s, float lambd,
+                            float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes, const char* query_name,
+                            hipStream_t st) {
+    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !u || !v || !w || !preds || !workspace)
+        return fail(TCLIP_ERR_ARG, kNullArg);
+    if (sp.visual && src->cols) return fail(TCLIP_ERR_ARG, "PADDLE on visual features permutes no columns: cols must be NULL");
+    const PaddleTasksWs o = PaddleTasksWs::layout(p, sp.D);
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, query_name)) return rc;
+    const int64_t T = (int64_t)p.n_batches * p.tasks_per_batch;
+    float* x_q = (float*)((char*)workspace + o.xq);
+    // every q_idx value has been checked by the caller (tclip_check_task_indices): no row of x_q stays unwritten
+    launch_gather_task_rows(st, src->table_q, INT64_MAX, sp.D, src->q_idx, p.n_query, src->cols, T * p.n_query, x_q);
+    return paddle_loop(sp, p, x_q, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, lambd, u, v, w, preds, (char*)workspace, st);
+}
+
+size_t tclip_paddle_tasks_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (p->n_support < 1) { fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE"); return 0; }
+    return PaddleTasksWs::layout(*p, p->n_class).total;
+}
+
+int tclip_paddle_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, float lambd, float* u, float* v,
+                           float* w, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    if (pp->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE");
+    return paddle_run_tasks(FeatureSpace{pp->n_class, false}, *pp, src, y_s, lambd, u, v, w, preds, workspace, workspace_bytes,
+                            "tclip_paddle_tasks_workspace_bytes", (hipStream_t)stream);
 }
 
 size_t tclip_paddle_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
@@ -514,7 +560,19 @@ int tclip_paddle_visual_run(const tclip_problem* pp, int32_t dim, const float* x
     const tclip_problem p = *pp;
     if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
     if (int rc = check_workspace(workspace, workspace_bytes, PaddleWs::layout(p, dim).total, "tclip_paddle_visual_workspace_bytes")) return rc;
-    return paddle_loop(FeatureSpace{dim, true}, p, x_q, x_s, y_s, lambd, u, v, w, preds, (char*)workspace, (hipStream_t)stream);
+    return paddle_loop(FeatureSpace{dim, true}, p, x_q, dense_rows(x_s), y_s, lambd, u, v, w, preds, (char*)workspace, (hipStream_t)stream);
+}
+
+size_t tclip_paddle_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_visual_fs(p, dim, "PADDLE") != TCLIP_OK) return 0;
+    return PaddleTasksWs::layout(*p, dim).total;
+}
+
+int tclip_paddle_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, float lambd,
+                                  float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_visual_fs(pp, dim, "PADDLE")) return rc;
+    return paddle_run_tasks(FeatureSpace{dim, true}, *pp, src, y_s, lambd, u, v, w, preds, workspace, workspace_bytes,
+                            "tclip_paddle_visual_tasks_workspace_bytes", (hipStream_t)stream);
 }
 
 size_t tclip_bdcspn_workspace_bytes(const tclip_problem* p) {

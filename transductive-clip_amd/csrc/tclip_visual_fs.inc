@@ -16,7 +16,10 @@ namespace tclip {
 // One block per (class, task): the members of the class are compacted in order into LDS and only they are visited; the dumps
 // that fall between two members are replayed (SparseCascade), since the zero products of the other rows only matter through
 // the positions of the dumps.  A label outside 0..K-1 matches no block and is never used as an index.
-__global__ __launch_bounds__(256) void k_vis_support_stats(const float* __restrict__ xs, const int64_t* __restrict__ ys, int S, int K,
+// The rows come from a RowSrc without a column permutation (the reference permutes no columns on visual features): row s of
+// task t is xs.base[t, s, :] of a dense [T, S, D] tensor, or xs.base[xs.idx[t S + s], :] of a feature table read in place
+// (tclip_paddle_visual_run_tasks); the order of the additions is the same.
+__global__ __launch_bounds__(256) void k_vis_support_stats(RowSrc xs, const int64_t* __restrict__ ys, int S, int K,
                                                            int D, float* __restrict__ sup, float* __restrict__ cnt) {
     extern __shared__ int vis_members[];           // indices s with ys == k, ascending
     __shared__ int n_members;
@@ -44,7 +47,9 @@ __global__ __launch_bounds__(256) void k_vis_support_stats(const float* __restri
         __syncthreads();
     }
     const int nm = n_members;
-    const float* xt = xs + (size_t)t * S * D;
+    const float* xt = xs.base + (xs.idx ? 0 : (size_t)t * S * D);
+    const int64_t* it = xs.idx ? xs.idx + (size_t)t * S : nullptr;
+    auto row = [&](int s_) { return xt + (size_t)(it ? it[s_] : (int64_t)s_) * D; };
     const long ncols = (long)K * D;
     const int size_ilp = S >> 2;
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
@@ -52,7 +57,7 @@ __global__ __launch_bounds__(256) void k_vis_support_stats(const float* __restri
         float r;
         if (outer_column_is_cascade(col, ncols)) {
             SparseCascade c(S);
-            for (int i = 0; i < nm; i++) c.add(vis_members[i], xt[(size_t)vis_members[i] * D + d]);
+            for (int i = 0; i < nm; i++) c.add(vis_members[i], row(vis_members[i])[d]);
             r = c.finish();
         } else {   // 4 interleaved cascades over s/4; the leftovers (s >= 4*(S/4)) join partial 0 after its cascade is complete
             SparseCascade c0(size_ilp), c1(size_ilp), c2(size_ilp), c3(size_ilp);
@@ -60,7 +65,7 @@ __global__ __launch_bounds__(256) void k_vis_support_stats(const float* __restri
             float p0 = 0.f;
             for (int i = 0; i < nm; i++) {
                 const int s = vis_members[i];
-                const float v = xt[(size_t)s * D + d];
+                const float v = row(s)[d];
                 if (s >= size_ilp * 4) {
                     if (!has_extra) { p0 = c0.finish(); has_extra = true; }
                     p0 += v;
@@ -85,9 +90,15 @@ __global__ __launch_bounds__(256) void k_vis_support_stats(const float* __restri
     if (threadIdx.x == 0) cnt[(size_t)t * K + k] = (float)nm;
 }
 
-static void launch_vis_support_stats(hipStream_t st, const float* xs, const int64_t* ys, int T, int S, int K, int D, float* sup,
+static void launch_vis_support_stats(hipStream_t st, const RowSrc& xs, const int64_t* ys, int T, int S, int K, int D, float* sup,
                                      float* cnt) {
     hipLaunchKernelGGL(k_vis_support_stats, dim3(K, T), dim3(256), (size_t)S * sizeof(int), st, xs, ys, S, K, D, sup, cnt);
+}
+
+// a dense [T, S, D] tensor (ALPHA_TIM, TIM_GD, LaplacianShot, BD-CSPN)
+static void launch_vis_support_stats(hipStream_t st, const float* xs, const int64_t* ys, int T, int S, int K, int D, float* sup,
+                                     float* cnt) {
+    launch_vis_support_stats(st, dense_rows(xs), ys, T, S, K, D, sup, cnt);
 }
 
 }  // namespace tclip

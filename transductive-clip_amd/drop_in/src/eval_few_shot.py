@@ -190,33 +190,52 @@ class Evaluator_few_shot:
         method = self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file)
         timestamps, parts = [], None
         runs = [(first_method, mine[:1]), (method, mine[1:])] if first_method is not None else [(method, mine)]
-        ran = None                        # the last method object that actually executed on this rank
+        # batches_per_call (absent or 0: all batches of a run in one engine call): consecutive groups of at most that many
+        # batches, each with a method object of its own, as the reference builds one per batch - what bounds the (T,S,W)
+        # tensors of the methods that cannot read their rows in place.  The first group keeps the run's object (batch 0 of a
+        # tuned run was built before the sweep file was read); the others are built from args as they now stand.
+        per_call = int(getattr(a, 'batches_per_call', 0) or 0)
+        if per_call < 0:
+            raise ValueError("batches_per_call must be a non-negative number of batches")
+        groups = []
         for m, ids in runs:
-            if not ids:
-                continue
+            step = per_call if per_call > 0 else max(len(ids), 1)
+            for g0 in range(0, len(ids), step):
+                groups.append((m if g0 == 0 else None, ids[g0:g0 + step]))
+        materialise = bool(getattr(a, 'materialise_tasks', False))
+        ran = None                        # the last method object that actually executed on this rank
+        for m, ids in groups:
+            if m is None:
+                m = self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file)
             ran = m
-            si, qi = s_idx[ids].reshape(-1), q_idx[ids].reshape(-1)
-            # The EM-Dirichlet classes read the task rows from the tables through the index tensors (label flip and column
-            # permutation inside the kernels): x_s (T,S,K) - 1.6 GB per 100 tasks at K = 1000, 4 shots - is never built
-            if a.name_method in ('EM_DIRICHLET', 'HARD_EM_DIRICHLET') and a.use_softmax_feature \
-                    and not getattr(a, 'materialise_tasks', False):
-                rel = relabel_indices(lab_s[si].view(-1, S), lab_q[qi].view(-1, Q), K)
+            si, qi = s_idx[ids].reshape(-1, S), q_idx[ids].reshape(-1, Q)
+            y_s, y_q = lab_s[si.reshape(-1)].view(-1, S), lab_q[qi.reshape(-1)].view(-1, Q)
+            # label re-indexing / column permutation of Tasks_Generator_few_shot.get_task WITHOUT touching the features: softmax
+            # features only (visual features keep labels and columns); None when a support set misses a class, and the tensors
+            # are then materialised as the reference does
+            cols, rel = None, None
+            if not materialise:
+                rel = relabel_indices(y_s, y_q, K) if a.use_softmax_feature else (None, y_s, y_q)
+            # The EM-Dirichlet classes and PADDLE read the task rows from the tables through the index tensors (label flip and
+            # column permutation inside the kernels): x_s (T,S,K) - 1.6 GB per 100 tasks at K = 1000, 4 shots - is never built
+            in_place = a.name_method == 'PADDLE' or (a.name_method in ('EM_DIRICHLET', 'HARD_EM_DIRICHLET') and a.use_softmax_feature)
+            if rel is not None:
+                cols, y_s, y_q = rel
+            if rel is not None and in_place:
+                m.run_tables(table_s=tab_s, s_idx=si, table_q=tab_q, q_idx=qi, cols=cols, y_s=y_s.to(dev), y_q=y_q.to(dev),
+                             n_batches=len(ids))
+            else:
                 if rel is not None:
-                    cols, y_s, y_q = rel
-                    m.run_tables(table_s=tab_s, s_idx=si.view(-1, S), table_q=tab_q, q_idx=qi.view(-1, Q), cols=cols,
-                                 y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
-                    logs = m.get_logs()
-                    parts = sharding.concat_parts(parts, sharding.method_parts(a, m, logs, len(ids), N, Q, dev))
-                    timestamps += [float(logs['timestamps'])] * len(ids)
-                    continue
-            x_s = engine.gather_rows(tab_s, si).view(len(ids) * N, S, W)
-            x_q = engine.gather_rows(tab_q, qi).view(len(ids) * N, Q, W)
-            y_s, y_q = lab_s[si].view(-1, S), lab_q[qi].view(-1, Q)
-            # label re-indexing / column permutation of Tasks_Generator_few_shot.get_task, per task
-            x_s, x_q, y_s, y_q = relabel_batch(x_s, x_q, y_s, y_q, a.use_softmax_feature)
-            # BDCSPN normalises the features in run_task, before run_method (few_shot/bdcspn.py:165-166): run_batch does both
-            run = getattr(m, "run_batch", m.run_method)
-            run(support=x_s, query=x_q, y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
+                    # the fused task builder: `table[idx][..., cols]` in one device pass, the re-indexed labels from the same call
+                    x_s = engine.gather_task_rows(tab_s, si, cols)
+                    x_q = engine.gather_task_rows(tab_q, qi, cols)
+                else:
+                    x_s = engine.gather_rows(tab_s, si.reshape(-1)).view(len(ids) * N, S, W)
+                    x_q = engine.gather_rows(tab_q, qi.reshape(-1)).view(len(ids) * N, Q, W)
+                    x_s, x_q, y_s, y_q = relabel_batch(x_s, x_q, y_s, y_q, a.use_softmax_feature)
+                # BDCSPN normalises the features in run_task, before run_method (few_shot/bdcspn.py:165-166): run_batch does both
+                run = getattr(m, "run_batch", m.run_method)
+                run(support=x_s, query=x_q, y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
             logs = m.get_logs()
             parts = sharding.concat_parts(parts, sharding.method_parts(a, m, logs, len(ids), N, Q, dev))
             timestamps += [float(logs['timestamps'])] * len(ids)

@@ -26,6 +26,11 @@ BDCSPN and TIM-GD (`method tim`; no text features needed) run on the raw embeddi
 class count is read from the labels and the sweep and result files carry `_visual` in their names.
 `device_matching True` (zero-shot clustering methods; not a default: absent unless given) matches clusters to classes on the
 device instead of on host threads - same accuracies, no copy of the prototypes to the host.
+Few-shot task tensors are built on the device; EM-Dirichlet and PADDLE read their rows from the feature tables in place.
+`batches_per_call N` (few-shot; not a default: absent or 0 runs all batches of a rank in one engine call) runs at most N
+batches per call, each call with a method object of its own - what bounds the (tasks, support, width) tensors of BDCSPN, TIM
+and LaplacianShot at ImageNet scale; `materialise_tasks True` takes the reference's route instead (gather, then a per-task
+relabelling on the host) - same results either way.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse

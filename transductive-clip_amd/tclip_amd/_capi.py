@@ -38,12 +38,19 @@ _SIGNATURES = {
     "tclip_match_clusters": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 5 + [ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P,
                                             ctypes.c_size_t, _P]),
     "tclip_gather_rows": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int64, _P, _P]),
+    "tclip_gather_task_rows": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, ctypes.c_int64, _P, _P]),
     "tclip_soft_kmeans_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_soft_kmeans_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, ctypes.c_float, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_em_gaussian_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_em_gaussian_cov_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_paddle_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_paddle_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_paddle_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
+    "tclip_paddle_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_float, _P, _P, _P, _P, _P,
+                                              ctypes.c_size_t, _P]),
+    "tclip_paddle_visual_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_paddle_visual_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P, ctypes.c_float,
+                                                     _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_alpha_tim_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_alpha_tim_run": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TimParams)] + [_P] * 8 + [ctypes.c_size_t, _P]),
     "tclip_alpha_tim_visual_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),

@@ -163,6 +163,43 @@ def run_em_dirichlet_tasks(table_q, q_idx, table_s=None, s_idx=None, y_s=None, c
     return EMDirichletResult(u=u, v=v, alpha=alpha, preds=preds, criterions=crit, mm_iters=mm)
 
 
+def _cols_tensor(cols, T, W, dev):
+    """int32 (T,W) column permutations on the device, every value checked against the row width: on the host when that is
+    where the tensor is, by tclip_check_task_indices otherwise (IndexError, as `_index_tensor`)"""
+    cols = cols.to(torch.int32)
+    if tuple(cols.shape) != (T, W) or (not cols.is_cuda and cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= W)):
+        raise IndexError(f"cols must be (T,{W}) with values in [0, {W})")
+    on_device = cols.is_cuda
+    cols = cols.to(dev).contiguous()
+    if on_device and cols.numel():
+        _check_on_device(None, 1, cols, W, "cols")
+    return cols
+
+
+def gather_task_rows(table, idx, cols=None):
+    """The fused task builder (tclip_gather_task_rows): table (n,W) f32 cuda, idx (T,R) int64 rows of it, cols (T,W) the per-task
+    column permutation of Tasks_Generator_few_shot.get_task or None -> (T,R,W) f32 cuda with out[t,r,d] =
+    table[idx[t,r], cols[t,d]]: `table[idx][..., cols]` in one pass, a bit-exact copy.  An index or column outside its range
+    raises IndexError before anything is launched.  Not synchronised (device-resident idx / cols: one host sync each for the
+    range check)."""
+    _require_cuda(table, "table")
+    if table.dim() != 2 or idx.dim() != 2:
+        raise ValueError("table must be (n,W) and idx (T,R)")
+    table = table.contiguous().float()
+    dev, W = table.device, table.shape[1]
+    idx = _index_tensor(idx, table.shape[0], dev, "idx")
+    T, R = idx.shape
+    if cols is not None:
+        cols = _cols_tensor(cols, T, W, dev)
+    out = torch.empty(T, R, W, device=dev)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _capi.lib().tclip_gather_task_rows(_ptr(table), table.shape[0], W, _ptr(idx), R, _ptr(cols), T * R, _ptr(out), _stream())
+    _capi.check(rc, "tclip_gather_task_rows")
+    return out
+
+
 def _kmeans_call(x_q, K, ws_query, *ws_args, iters, lambd=0, n_batches=1):
     """What the zero-shot k-means calls share on either feature kind: the problem, the workspace query and the outputs every
     method has.  x_q (T,Q,D), D = K for probability features -> (call, u (T,Q,K), w (T,K,D), preds (T,Q) i32)."""
@@ -243,6 +280,59 @@ def run_paddle(x_q, x_s, y_s, *, iters, lambd):
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
     return _run_paddle(x_q, x_s, y_s, x_q.shape[2], iters, lambd, visual=False)
+
+
+def _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, lambd, visual):
+    """PADDLE from the feature tables on rows of D elements (tclip_paddle_run_tasks / tclip_paddle_visual_run_tasks)"""
+    _require_cuda(table_q, "table_q")
+    _require_cuda(table_s, "table_s")
+    if table_q.dim() != 2 or table_s.dim() != 2 or q_idx.dim() != 2 or s_idx.dim() != 2:
+        raise ValueError("table_q and table_s must be (rows,D), q_idx (T,Q) and s_idx (T,S)")
+    table_q, table_s = table_q.contiguous().float(), table_s.contiguous().float()
+    dev, D = table_q.device, table_q.shape[1]
+    if table_s.shape[1] != D or table_s.device != dev:
+        raise ValueError("table_q and table_s must be (rows,D) tensors of one width on one device")
+    q_idx = _index_tensor(q_idx, table_q.shape[0], dev, "q_idx")
+    s_idx = _index_tensor(s_idx, table_s.shape[0], dev, "s_idx")
+    T, Q = q_idx.shape
+    S = s_idx.shape[1]
+    if S < 1:
+        raise ValueError("PADDLE is a few-shot method: s_idx must be (T,S) with n_support = S positive")
+    y_s = y_s.reshape(y_s.shape[0], -1).long().to(dev).contiguous()
+    if s_idx.shape[0] != T or tuple(y_s.shape) != (T, S):
+        raise ValueError("s_idx and y_s must be (T,S) with the T of q_idx")
+    if y_s.numel() and not bool(((y_s >= 0) & (y_s < K)).all()):
+        raise ValueError(f"y_s holds a label outside 0..{K - 1}")
+    if cols is not None:
+        cols = _cols_tensor(cols, T, D, dev)
+    stem, dim = ("tclip_paddle_visual", (ctypes.c_int32(D),)) if visual else ("tclip_paddle", ())
+    c = _Call(dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
+    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
+    src = _capi.TaskSource(table_q.data_ptr(), q_idx.data_ptr(), table_s.data_ptr(), s_idx.data_ptr(),
+                           cols.data_ptr() if cols is not None else None)
+    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_float(float(lambd)), _ptr(u),
+                                                     _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
+    return u, v, w, preds
+
+
+def run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, lambd):
+    """PADDLE fed from the task-batch loop's feature tables (tclip_paddle_run_tasks): table_q, table_s (rows,K) f32 cuda,
+    q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column permutation
+    of Tasks_Generator_few_shot.get_task or None -> (u (T,Q,K), v (T,K), w (T,K,K), preds (T,Q) i32), cuda, not synchronised.
+    The support rows are read in place: no (T,S,K) tensor is built; the results are those of run_paddle on the materialised
+    tensors, bit for bit."""
+    return _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], iters, lambd, visual=False)
+
+
+def run_paddle_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, lambd):
+    """PADDLE on visual features fed from the feature tables (tclip_paddle_visual_run_tasks): table_q, table_s (rows,D) raw
+    embeddings f32 cuda with any D in 1..1024, q_idx (T,Q), s_idx (T,S), y_s (T,S) int64 labels in 0..n_class-1 as they are (no
+    re-indexing and no column permutation on visual features) -> (u (T,Q,K), v (T,K), w (T,K,D), preds (T,Q) i32), cuda, not
+    synchronised; the bits of run_paddle_visual on the materialised tensors."""
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    return _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, iters, lambd, visual=True)
 
 
 ENTROPIES = {"Shannon": 0, "Alpha": 1}
