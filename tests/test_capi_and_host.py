@@ -179,6 +179,21 @@ def test_widened_method_classes_have_no_cpu_path():
         m = cls(model=None, device=torch.device("cpu"), log_file=None, args=a)
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             m.run_task(dict(fs_task), shot=1)
+    # feature width = num_classes_test: the refusals of other feature kinds do not fire first
+    from src.methods.few_shot.em_dirichlet import EM_DIRICHLET as FS
+    from src.methods.few_shot.hard_em_dirichlet import HARD_EM_DIRICHLET as FSH
+    from src.methods.few_shot.laplacian_shot import LAPLACIAN_SHOT
+    from src.methods.few_shot.tim import ALPHA_TIM, TIM_GD
+    from src.methods.zero_shot.em_dirichlet import EM_DIRICHLET as ZS
+    from src.methods.zero_shot.hard_em_dirichlet import HARD_EM_DIRICHLET as ZSH
+    for cls in (ZS, ZSH, FS, FSH, TIM_GD, ALPHA_TIM, LAPLACIAN_SHOT):
+        a = CfgNode(iter=2, iter_mm=100, num_classes_test=20, n_class=20, n_query=75, k_eff=4, T=30, use_softmax_feature=True,
+                    graph_matching=True, temp=15.0, loss_weights=[1.0, 1.0, 1.0], lr_tim=1e-4, lr_alpha_tim=1e-4,
+                    entropies=["Shannon", "Alpha", "Alpha"], alpha_value=7.0, knn=3, lmd=0.7, norm_type="L2N", batch_size=2,
+                    shots=1)
+        m = cls(model=None, device=torch.device("cpu"), log_file=None, args=a)
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            m.run_task(dict(zs_task)) if cls in (ZS, ZSH) else m.run_task(dict(fs_task), shot=1)
 
 
 def test_source_digest_ignores_comments_not_code(tmp_path, monkeypatch):

@@ -218,7 +218,7 @@ class Evaluator_few_shot:
                 rel = relabel_indices(y_s, y_q, K) if a.use_softmax_feature else (None, y_s, y_q)
             # The EM-Dirichlet classes and PADDLE read the task rows from the tables through the index tensors (label flip and
             # column permutation inside the kernels): x_s (T,S,K) - 1.6 GB per 100 tasks at K = 1000, 4 shots - is never built
-            in_place = a.name_method == 'PADDLE' or (a.name_method in ('EM_DIRICHLET', 'HARD_EM_DIRICHLET') and a.use_softmax_feature)
+            in_place = m.reads_rows_in_place(a.use_softmax_feature)
             if rel is not None:
                 cols, y_s, y_q = rel
             if rel is not None and in_place:
@@ -234,8 +234,7 @@ class Evaluator_few_shot:
                     x_q = engine.gather_rows(tab_q, qi.reshape(-1)).view(len(ids) * N, Q, W)
                     x_s, x_q, y_s, y_q = relabel_batch(x_s, x_q, y_s, y_q, a.use_softmax_feature)
                 # BDCSPN normalises the features in run_task, before run_method (few_shot/bdcspn.py:165-166): run_batch does both
-                run = getattr(m, "run_batch", m.run_method)
-                run(support=x_s, query=x_q, y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
+                m.run_batch(support=x_s, query=x_q, y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
             logs = m.get_logs()
             parts = sharding.concat_parts(parts, sharding.method_parts(a, m, logs, len(ids), N, Q, dev))
             timestamps += [float(logs['timestamps'])] * len(ids)

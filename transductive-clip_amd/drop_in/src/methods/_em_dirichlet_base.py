@@ -1,9 +1,11 @@
-"""Shared host logic of the four EM-Dirichlet method classes.
+"""Shared host logic of the reference-named method classes.
 
-Mirrors the reference's BASE/EM_DIRICHLET interface (constructor keywords, run_task, the logs
-dict, the post-call attributes u / v / alpha) while the loop itself runs in libtclip.so on the
-GPU (tclip_amd.engine).  Reference: src/methods/zero_shot/em_dirichlet.py:9-246,
-src/methods/few_shot/em_dirichlet.py:9-220 and their hard_ twins."""
+MethodBase holds what every class repeats around its engine call: constructor state and logger, the device check, the timed
+call, the rules that spread one wall time over the reference's per-iteration records, the accuracy helpers and get_logs.
+EMDirichletBase adds the EM-Dirichlet loop; ZeroShotMixin / FewShotMixin add run_task.  Together they mirror the
+reference's BASE/EM_DIRICHLET interface (constructor keywords, run_task, the logs dict, the post-call attributes
+u / v / alpha) while the loop itself runs in libtclip.so on the GPU (tclip_amd.engine).  Reference:
+src/methods/zero_shot/em_dirichlet.py:9-246, src/methods/few_shot/em_dirichlet.py:9-220 and their hard_ twins."""
 import time
 
 import numpy as np
@@ -15,27 +17,20 @@ from tclip_amd import engine
 _SIMPLEX_ERROR = "The selected method is unable to handle query features that are not in the unit simplex"
 
 
-class EMDirichletBase(object):
-    HARD = False
-    FEW_SHOT = False
-    BANNER = "EM-DIRICHLET"
+class MethodBase(object):
+    LOGGER_NAME = __name__      # a class outside the EM-Dirichlet family logs under its own module's name, as the reference's does
+    ARG_DEFAULTS = {}           # written into args where the method's YAML has no such key
 
     def __init__(self, model, device, log_file, args):
+        for key, value in self.ARG_DEFAULTS.items():
+            if not hasattr(args, key):
+                setattr(args, key, value)
         self.device = device
-        self.iter = args.iter
-        # `lambd` from the YAML is ignored by the reference too (em_dirichlet.py:14)
-        if self.FEW_SHOT:
-            self.lambd = int(args.num_classes_test / args.k_eff) * args.n_query
-        else:
-            self.lambd = int(args.num_classes_test / 5) * args.n_query
         self.model = model
         self.log_file = log_file
-        self.logger = Logger(__name__, self.log_file)
+        self.logger = Logger(self.LOGGER_NAME, self.log_file)
         self.init_info_lists()
         self.args = args
-        self.eps = 1e-15
-        self.iter_mm = args.iter_mm
-        self.mm_iters = None
 
     def __del__(self):
         try:
@@ -48,6 +43,10 @@ class EMDirichletBase(object):
         self.criterions = []
         self.test_acc = []
 
+    def record_convergence(self, new_time, criterions):
+        self.criterions.append(criterions)
+        self.timestamps.append(new_time)
+
     def get_logs(self):
         self.criterions = np.asarray(self.criterions, dtype=np.float32)
         on_device = any(a.is_cuda for a in self.test_acc)
@@ -58,10 +57,58 @@ class EMDirichletBase(object):
         return {'timestamps': np.array(self.timestamps).mean(), 'criterions': self.criterions,
                 'acc': self.test_acc}
 
+    # -- the engine call --------------------------------------------------------------------
+    def _cuda_device(self, name=None):
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise RuntimeError("{} on MI355X needs device='cuda': there is no CPU fallback in this package".format(
+                name or type(self).__name__))
+        return dev
+
+    def _timed(self, call):
+        """call() between two device synchronisations: its result and the wall time of the interval"""
+        dev = torch.device(self.device)
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        out = call()
+        torch.cuda.synchronize(dev)
+        return out, time.time() - t0
+
+    def _execute(self, banner, call, name=None):
+        """device check, banner log line, timed engine call"""
+        self._cuda_device(name)
+        self.logger.info(banner)
+        return self._timed(call)
+
+    @staticmethod
+    def spread_time(rule, total, iters, n_task):
+        """The reference appends one host-clock reading per outer iteration (or task); the fused loops have no such clock,
+        so the total of one call is spread by the rule of the reference file the class mirrors:
+          cumulative  the clock keeps running, every reading divided by n_task (em_dirichlet.py:242-244, paddle.py:214-216,
+                      tim.py:184-186 and :317-319); reproduces the reference's "mean of cumulative times" statistic
+          share       the clock restarts every iteration (soft_kmeans.py:203-216, em_gaussian.py:204-224)
+          twice       every iteration is recorded twice, once undivided (hard_kmeans.py:198-204, kl_kmeans.py:178-187)
+          per_task    one cumulative reading after every task (laplacian_shot.py:243-245)"""
+        per_iter = total / max(iters, 1)
+        if rule == "cumulative":
+            return [total * (i + 1) / max(iters, 1) / n_task for i in range(iters)]
+        if rule == "share":
+            return [per_iter / n_task] * iters
+        if rule == "twice":
+            return [per_iter, per_iter / n_task] * iters
+        if rule == "per_task":
+            return [total * (t + 1) / n_task for t in range(n_task)]
+        raise ValueError(f"unknown timestamp rule {rule!r}")
+
+    def _text_features(self, dev):
+        # imported here: a Level-1 overlay that copies only the modules of the probability-feature path keeps working
+        from src.methods._visual import text_features
+        return text_features(self.model, self.args, dev)
+
     # -- accuracy ---------------------------------------------------------------------------
-    def compute_acc(self, y_q):
+    def compute_acc(self, y_q, preds_q=None):
         # on the host: the mean of 75 zeros and ones is rounded as the reference's CPU op rounds it
-        preds_q = self.preds.long().cpu()
+        preds_q = (self.preds if preds_q is None else preds_q).long().cpu()
         accuracy = (preds_q == y_q.cpu()).float().mean(1, keepdim=True)
         self.test_acc.append(accuracy)
 
@@ -75,19 +122,34 @@ class EMDirichletBase(object):
             on = False
         return "device" if on else "host"
 
-    def compute_acc_clustering(self, query, y_q):
-        acc, new_preds = engine.clustering_accuracy(query, self.preds, y_q,
-                                                    graph_matching=bool(self.args.graph_matching), matching=self._matching())
+    def compute_acc_clustering(self, query, y_q, text=None):
+        """`text` given: the accuracy tail on visual features (soft_kmeans.py:36-66): D-dim prototypes, scored against the
+        text features"""
+        kw = dict(graph_matching=bool(self.args.graph_matching), matching=self._matching())
+        if text is None:
+            acc, new_preds = engine.clustering_accuracy(query, self.preds, y_q, **kw)
+        else:
+            acc, new_preds = engine.clustering_accuracy_visual(query, self.preds, y_q, text, self.args.T, **kw)
         self.matched_preds = new_preds
         self.test_acc.append(acc.view(-1, 1))
 
-    def compute_acc_clustering_visual(self, query, y_q, text):
-        """the accuracy tail on visual features (soft_kmeans.py:36-66): D-dim prototypes, scored against the text features"""
-        acc, new_preds = engine.clustering_accuracy_visual(query, self.preds, y_q, text, self.args.T,
-                                                           graph_matching=bool(self.args.graph_matching),
-                                                           matching=self._matching())
-        self.matched_preds = new_preds
-        self.test_acc.append(acc.view(-1, 1))
+
+class EMDirichletBase(MethodBase):
+    HARD = False
+    FEW_SHOT = False
+    BANNER = "EM-DIRICHLET"
+
+    def __init__(self, model, device, log_file, args):
+        super().__init__(model=model, device=device, log_file=log_file, args=args)
+        self.iter = args.iter
+        # `lambd` from the YAML is ignored by the reference too (em_dirichlet.py:14)
+        if self.FEW_SHOT:
+            self.lambd = int(args.num_classes_test / args.k_eff) * args.n_query
+        else:
+            self.lambd = int(args.num_classes_test / 5) * args.n_query
+        self.eps = 1e-15
+        self.iter_mm = args.iter_mm
+        self.mm_iters = None
 
     # -- the loop ---------------------------------------------------------------------------
     def _run_engine(self, query, support=None, y_s=None, n_batches=1, tables=None):
@@ -95,29 +157,19 @@ class EMDirichletBase(object):
         task-batch loop's index tensors (engine.run_em_dirichlet_tasks) and `query` / `support` are not used"""
         if not self.args.use_softmax_feature:
             raise ValueError(_SIMPLEX_ERROR)
-        dev = torch.device(self.device)
-        if dev.type != "cuda":
-            raise RuntimeError("EM-Dirichlet on MI355X needs device='cuda': there is no CPU fallback in this package")
-        self.logger.info(" ==> Executing {} with LAMBDA = {} and T = {}".format(self.BANNER, self.lambd, self.args.T))
         n_task = tables["q_idx"].shape[0] if tables is not None else query.shape[0]
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
         kw = dict(n_batches=n_batches, iters=self.iter, iter_mm=self.iter_mm, lambd=self.lambd, hard=self.HARD)
         if tables is not None:
-            res = engine.run_em_dirichlet_tasks(tables["table_q"], tables["q_idx"], tables.get("table_s"), tables.get("s_idx"),
-                                                y_s, tables.get("cols"), **kw)
+            call = lambda: engine.run_em_dirichlet_tasks(tables["table_q"], tables["q_idx"], tables.get("table_s"),      # noqa: E731
+                                                         tables.get("s_idx"), y_s, tables.get("cols"), **kw)
         else:
-            res = engine.run_em_dirichlet(query, support, y_s, **kw)
-        torch.cuda.synchronize(dev)
-        total = time.time() - t0
+            call = lambda: engine.run_em_dirichlet(query, support, y_s, **kw)      # noqa: E731
+        res, total = self._execute(" ==> Executing {} with LAMBDA = {} and T = {}".format(self.BANNER, self.lambd, self.args.T),
+                                   call, name="EM-Dirichlet")
         self.u, self.v, self.alpha, self.preds = res.u, res.v, res.alpha, res.preds
         self.mm_iters = res.mm_iters.cpu().numpy()
         crit = res.criterions.cpu().numpy()            # (n_batches, iters)
-        # the reference appends one cumulative wall time per outer iteration, divided by n_task
-        # (em_dirichlet.py:242-244); the fused loop has no per-iteration host clock, so the total
-        # is spread evenly, which reproduces the reference's "mean of cumulative times" statistic
-        for i in range(self.iter):
-            self.timestamps.append(total * (i + 1) / max(self.iter, 1) / n_task)
+        self.timestamps += self.spread_time("cumulative", total, self.iter, n_task)
         self.criterions = list(crit.mean(0)) if n_batches > 1 else list(crit[0])
         self.criterions_per_batch = crit
         return res
@@ -137,8 +189,27 @@ class ZeroShotMixin:
         self._run_engine(query, n_batches=n_batches)
         self.compute_acc_clustering(query, y_q)
 
+    def _run_clustering(self, query, run, run_visual):
+        """The head SOFT_KMEANS, HARD_KMEANS and EM_GAUSSIAN share: run() on probability features; on visual features
+        (use_softmax_feature: False) run_visual(u0) with the initial assignment u0 from the text features.  Returns the
+        engine's result, the wall time and the text features (None on probability features) for compute_acc_clustering."""
+        dev = self._cuda_device()
+        text = None if self.args.use_softmax_feature else self._text_features(dev)
+        self.logger.info(" ==> Executing {} with T = {}".format(self.BANNER, self.args.T))
+        if text is None:
+            out, total = self._timed(run)
+        else:
+            out, total = self._timed(lambda: run_visual(engine.visual_init(query, text, self.args.T)))
+        return out, total, text
+
 
 class FewShotMixin:
+    IN_PLACE_FEATURES = ()      # of "softmax" / "visual": the feature kinds on which run_tables reads the task rows in place
+
+    @classmethod
+    def reads_rows_in_place(cls, use_softmax_feature):
+        return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_FEATURES
+
     def run_task(self, task_dic, shot=10):
         y_s, y_q = task_dic['y_s'], task_dic['y_q']
         support, query = task_dic['x_s'], task_dic['x_q']
@@ -147,8 +218,12 @@ class FewShotMixin:
         y_s = y_s.long().squeeze(2).to(self.device)
         y_q = y_q.long().squeeze(2).to(self.device)
         del task_dic
-        self.run_method(support=support, query=query, y_s=y_s, y_q=y_q)
+        self.run_batch(support=support, query=query, y_s=y_s, y_q=y_q)
         return self.get_logs()
+
+    def run_batch(self, support, query, y_s, y_q, n_batches=1):
+        """what run_task runs on the tensors of its tasks: run_method, unless a class prepares its inputs first (BDCSPN)"""
+        self.run_method(support=support, query=query, y_s=y_s, y_q=y_q, n_batches=n_batches)
 
     def run_method(self, support, query, y_s, y_q, n_batches=1):
         # unlike the reference (few_shot/em_dirichlet.py:186-190) the inputs are left untouched:

@@ -6,11 +6,9 @@ from src.methods._em_dirichlet_base import EMDirichletBase, FewShotMixin
 
 class BASE(FewShotMixin, EMDirichletBase):
     FEW_SHOT = True
+    IN_PLACE_FEATURES = ("softmax",)
 
 
 class HARD_EM_DIRICHLET(BASE):
     HARD = True
     BANNER = "HARD EM-DIRICHLET"
-
-    def __init__(self, model, device, log_file, args):
-        super().__init__(model=model, device=device, log_file=log_file, args=args)

@@ -6,10 +6,6 @@ place through tclip_paddle_run_tasks / tclip_paddle_visual_run_tasks).  `args.la
 EM-Dirichlet.  On visual features the rows are D-dim embeddings and the class count is
 args.num_classes_test, as in the reference; the reference's text-prompt u (:186-196) is overwritten by
 the first u_update before anything reads it, so no text features are asked for."""
-import time
-
-import torch
-
 from src.methods._em_dirichlet_base import EMDirichletBase, FewShotMixin
 from tclip_amd import engine
 
@@ -20,10 +16,10 @@ class BASE(FewShotMixin, EMDirichletBase):
 
 class PADDLE(BASE):
     BANNER = "PADDLE"
+    ARG_DEFAULTS = {"iter_mm": 0}          # paddle.yaml has no iter_mm
+    IN_PLACE_FEATURES = ("softmax", "visual")
 
     def __init__(self, model, device, log_file, args):
-        if not hasattr(args, "iter_mm"):
-            args.iter_mm = 0          # paddle.yaml has no iter_mm
         super().__init__(model=model, device=device, log_file=log_file, args=args)
         self.lambd = args.lambd       # paddle.py:26
 
@@ -33,7 +29,7 @@ class PADDLE(BASE):
         else:
             call = lambda: engine.run_paddle_visual(query, support, y_s, n_class=self.args.num_classes_test,      # noqa: E731
                                                     iters=self.iter, lambd=self.lambd)
-        self._timed(call, query.shape[0], y_q)
+        self._run(call, query.shape[0], y_q)
 
     def run_tables(self, table_s, s_idx, table_q, q_idx, cols, y_s, y_q, n_batches=1):
         """run_method for the task-batch loop (Evaluator_few_shot.evaluate_tasks) on either feature kind: the support / query
@@ -48,21 +44,13 @@ class PADDLE(BASE):
                 raise ValueError("PADDLE on visual features permutes no columns: cols must be None")
             call = lambda: engine.run_paddle_visual_tasks(table_q, q_idx, table_s, s_idx, y_s,      # noqa: E731
                                                           n_class=self.args.num_classes_test, iters=self.iter, lambd=self.lambd)
-        self._timed(call, q_idx.shape[0], y_q)
+        self._run(call, q_idx.shape[0], y_q)
 
-    def _timed(self, call, n_task, y_q):
-        """the engine call between two device synchronisations, then the reference's bookkeeping"""
-        dev = torch.device(self.device)
-        if dev.type != "cuda":
-            raise RuntimeError("PADDLE on MI355X needs device='cuda': there is no CPU fallback in this package")
-        self.logger.info(" ==> Executing PADDLE with LAMBDA = {} and T = {}".format(self.lambd, self.args.T))
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        self.u, self.v, self.w, self.preds = call()
-        torch.cuda.synchronize(dev)
-        total = time.time() - t0
-        for i in range(self.iter):
-            # cumulative wall time per iteration over n_task (paddle.py:214-216)
-            self.timestamps.append(total * (i + 1) / max(self.iter, 1) / n_task)
+    def _run(self, call, n_task, y_q):
+        """the engine call, then the reference's bookkeeping"""
+        (self.u, self.v, self.w, self.preds), total = self._execute(
+            " ==> Executing PADDLE with LAMBDA = {} and T = {}".format(self.lambd, self.args.T), call)
+        # cumulative wall time per iteration over n_task (paddle.py:214-216)
+        self.timestamps += self.spread_time("cumulative", total, self.iter, n_task)
         self.criterions = [0.0] * self.iter       # the reference compares u with a copy of itself (:211-212)
         self.compute_acc(y_q=y_q)

@@ -5,12 +5,12 @@ MKL matmuls and autograd accumulation order leave no bit-level target, so both c
 float tolerance (tests/test_alpha_tim.py, tests/test_gpu_tim_gd.py).  TIM_GD never reads use_softmax_feature and normalises
 nothing: it runs on probability features and on D-dim embeddings alike, the class count being args.num_classes_test.
 ALPHA_TIM takes probability features only."""
-import time
-
-import torch
-
 from src.methods._em_dirichlet_base import EMDirichletBase, FewShotMixin
 from tclip_amd import engine
+
+
+# tim.yaml and alpha_tim.yaml have no iter_mm; k_eff only feeds the unused EM-Dirichlet lambd of the shared base
+_ARG_DEFAULTS = {"iter_mm": 0, "k_eff": 5}
 
 
 class BASE(FewShotMixin, EMDirichletBase):
@@ -19,34 +19,22 @@ class BASE(FewShotMixin, EMDirichletBase):
 
 class TIM_GD(BASE):
     BANNER = "TIM"
+    ARG_DEFAULTS = _ARG_DEFAULTS
 
     def __init__(self, model, device, log_file, args):
-        if not hasattr(args, "iter_mm"):
-            args.iter_mm = 0          # tim.yaml has no iter_mm
-        if not hasattr(args, "k_eff"):
-            args.k_eff = 5            # only feeds the unused EM-Dirichlet lambd of the shared base
         super().__init__(model=model, device=device, log_file=log_file, args=args)
         self.loss_weights = list(args.loss_weights)      # tim.py:29 (.copy())
         self.temp = args.temp
         self.lr = float(args.lr_tim)                     # tim.py:94
 
     def run_method(self, support, query, y_s, y_q, n_batches=1):
-        dev = torch.device(self.device)
-        if dev.type != "cuda":
-            raise RuntimeError("TIM_GD on MI355X needs device='cuda': there is no CPU fallback in this package")
-        self.logger.info(" ==> Executing TIM with T = {}".format(self.args.T))
-        n_task = query.shape[0]
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
         # rows of D = query.shape[2] elements, D = n_class on probability features and the embedding length otherwise
-        self.weights, self.logits_q, self.preds, crit = engine.run_tim_gd(
-            query, support, y_s, n_class=self.args.num_classes_test, iters=self.iter, temp=self.temp, lr=self.lr,
-            loss_weights=self.loss_weights, n_batches=n_batches)
-        torch.cuda.synchronize(dev)
-        total = time.time() - t0
-        for i in range(self.iter):
-            # cumulative wall time per iteration over n_task (tim.py:184-186)
-            self.timestamps.append(total * (i + 1) / max(self.iter, 1) / n_task)
+        (self.weights, self.logits_q, self.preds, crit), total = self._execute(
+            " ==> Executing TIM with T = {}".format(self.args.T),
+            lambda: engine.run_tim_gd(query, support, y_s, n_class=self.args.num_classes_test, iters=self.iter, temp=self.temp,
+                                      lr=self.lr, loss_weights=self.loss_weights, n_batches=n_batches))
+        # cumulative wall time per iteration over n_task (tim.py:184-186)
+        self.timestamps += self.spread_time("cumulative", total, self.iter, query.shape[0])
         crit = crit.cpu().numpy()                        # (iter, n_task): mean_class ||w_old - w|| of every task (tim.py:181)
         self.criterions_per_task = crit
         self.criterions = list(crit)
@@ -55,12 +43,9 @@ class TIM_GD(BASE):
 
 class ALPHA_TIM(BASE):
     BANNER = "ALPHA_TIM"
+    ARG_DEFAULTS = _ARG_DEFAULTS
 
     def __init__(self, model, device, log_file, args):
-        if not hasattr(args, "iter_mm"):
-            args.iter_mm = 0          # alpha_tim.yaml has no iter_mm
-        if not hasattr(args, "k_eff"):
-            args.k_eff = 5            # only feeds the unused EM-Dirichlet lambd of the shared base
         super().__init__(model=model, device=device, log_file=log_file, args=args)
         self.loss_weights = list(args.loss_weights)      # tim.py:29 (.copy())
         self.temp = args.temp
@@ -71,21 +56,13 @@ class ALPHA_TIM(BASE):
     def run_method(self, support, query, y_s, y_q, n_batches=1):
         if query.shape[2] != self.args.num_classes_test:
             raise NotImplementedError("ALPHA_TIM here takes probability features (use_softmax_feature: True, feature dimension = n_class)")
-        dev = torch.device(self.device)
-        if dev.type != "cuda":
-            raise RuntimeError("ALPHA_TIM on MI355X needs device='cuda': there is no CPU fallback in this package")
-        self.logger.info(" ==> Executing ALPHA_TIM with ALPHA = {} and T = {}".format(self.alpha_value, self.args.T))
-        n_task = query.shape[0]
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        self.weights, self.logits_q, self.preds, crit = engine.run_alpha_tim(
-            query, support, y_s, iters=self.iter, temp=self.temp, lr=self.lr, alpha_value=self.alpha_value,
-            loss_weights=self.loss_weights, entropies=self.entropies, n_batches=n_batches)
-        torch.cuda.synchronize(dev)
-        total = time.time() - t0
-        for i in range(self.iter):
-            # cumulative wall time per iteration over n_task (tim.py:317-319)
-            self.timestamps.append(total * (i + 1) / max(self.iter, 1) / n_task)
+        (self.weights, self.logits_q, self.preds, crit), total = self._execute(
+            " ==> Executing ALPHA_TIM with ALPHA = {} and T = {}".format(self.alpha_value, self.args.T),
+            lambda: engine.run_alpha_tim(query, support, y_s, iters=self.iter, temp=self.temp, lr=self.lr,
+                                         alpha_value=self.alpha_value, loss_weights=self.loss_weights,
+                                         entropies=self.entropies, n_batches=n_batches))
+        # cumulative wall time per iteration over n_task (tim.py:317-319)
+        self.timestamps += self.spread_time("cumulative", total, self.iter, query.shape[0])
         crit = crit.cpu().numpy()                        # (n_batches, iter): mean_{task,class} ||w_old - w||
         self.criterions_per_batch = crit
         self.criterions = list(crit.mean(0)) if n_batches > 1 else list(crit[0])

@@ -10,6 +10,3 @@ class BASE(ZeroShotMixin, EMDirichletBase):
 class HARD_EM_DIRICHLET(BASE):
     HARD = True
     BANNER = "HARD EM-DIRICHLET"
-
-    def __init__(self, model, device, log_file, args):
-        super().__init__(model=model, device=device, log_file=log_file, args=args)

@@ -4,18 +4,8 @@ Same constructor / run_task / logs contract as the EM-Dirichlet classes; the loo
 libtclip.so (tclip_soft_kmeans_run).  On visual features (use_softmax_feature: False) the initial assignment comes from the
 text features (reference :185-197; src/methods/_visual.py) and the loop runs in the embedding space
 (tclip_kmeans_visual_run)."""
-import time
-
-import torch
-
 from src.methods._em_dirichlet_base import EMDirichletBase, ZeroShotMixin
 from tclip_amd import engine
-
-
-def _text_features(model, args, device):
-    # imported here: a Level-1 overlay that copies only the modules of the probability-feature path keeps working
-    from src.methods._visual import text_features
-    return text_features(model, args, device)
 
 
 class BASE(ZeroShotMixin, EMDirichletBase):
@@ -24,34 +14,13 @@ class BASE(ZeroShotMixin, EMDirichletBase):
 
 class SOFT_KMEANS(BASE):
     BANNER = "SOFT K-MEANS"
-
-    def __init__(self, model, device, log_file, args):
-        if not hasattr(args, "iter_mm"):
-            args.iter_mm = 0          # soft_kmeans.yaml has no iter_mm
-        super().__init__(model=model, device=device, log_file=log_file, args=args)
+    ARG_DEFAULTS = {"iter_mm": 0}          # soft_kmeans.yaml has no iter_mm
 
     def run_method(self, query, y_q, n_batches=1):
-        dev = torch.device(self.device)
-        if dev.type != "cuda":
-            raise RuntimeError("SOFT_KMEANS on MI355X needs device='cuda': there is no CPU fallback in this package")
-        visual = not self.args.use_softmax_feature
-        text = _text_features(self.model, self.args, dev) if visual else None
-        self.logger.info(" ==> Executing SOFT K-MEANS with T = {}".format(self.args.T))
-        n_task = query.shape[0]
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        if visual:
-            u0 = engine.visual_init(query, text, self.args.T)
-            self.u, self.w, self.preds = engine.run_soft_kmeans_visual(query, u0, iters=self.iter, temperature=self.args.T)
-        else:
-            self.u, self.w, self.preds = engine.run_soft_kmeans(query, iters=self.iter, temperature=self.args.T)
-        torch.cuda.synchronize(dev)
-        total = time.time() - t0
-        for i in range(self.iter):
-            # the reference restarts its clock every iteration (soft_kmeans.py:203-216)
-            self.timestamps.append(total / max(self.iter, 1) / n_task)
+        (self.u, self.w, self.preds), total, text = self._run_clustering(
+            query, lambda: engine.run_soft_kmeans(query, iters=self.iter, temperature=self.args.T),
+            lambda u0: engine.run_soft_kmeans_visual(query, u0, iters=self.iter, temperature=self.args.T))
+        # the reference restarts its clock every iteration (soft_kmeans.py:203-216)
+        self.timestamps += self.spread_time("share", total, self.iter, query.shape[0])
         self.criterions = [0.0] * self.iter       # the reference compares u with a copy of itself
-        if visual:
-            self.compute_acc_clustering_visual(query, y_q, text)
-        else:
-            self.compute_acc_clustering(query, y_q)
+        self.compute_acc_clustering(query, y_q, text)
