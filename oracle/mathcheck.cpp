@@ -162,3 +162,22 @@ extern "C" float mc_norm8(const float* x, long n) {
     for (; d < n; d++) b = __builtin_fmaf(x[d], x[d], b);
     return sqrtf(b);
 }
+
+// torch's bmm a^T b of KL_KMEANS's centroids (kl_kmeans.py: u.transpose(1, 2) @ query) as the fixture host evaluates it (see
+// k_kl_centroids in tclip_kernels.hip): MKL's sgemm accumulates every output as one chain of fused multiply-adds over the
+// rows in ascending order; below 400 multiply-adds per matrix ATen runs its own triple loop, a rounded product plus an add.
+// MKL picks its kernel by the host's CPU, so torch's own bmm has other bits on some hosts (rows of 7 elements, 15 or more of
+// them); this is the same on every host.  a (T, R, M), b (T, R, N) -> out (T, M, N).
+extern "C" void mc_bmm_tn(const float* a, const float* b, long T, long R, long M, long N, float* out) {
+    const bool fused = R * M * N >= 400;
+    for (long t = 0; t < T; t++) {
+        float* o = out + t * M * N;
+        for (long i = 0; i < M * N; i++) o[i] = 0.0f;
+        for (long r = 0; r < R; r++)                     // every output's chain advances by one row
+            for (long m = 0; m < M; m++) {
+                const float av = a[(t * R + r) * M + m];
+                const float* bv = b + (t * R + r) * N;
+                for (long n = 0; n < N; n++) o[m * N + n] = fused ? __builtin_fmaf(av, bv[n], o[m * N + n]) : o[m * N + n] + av * bv[n];
+            }
+    }
+}

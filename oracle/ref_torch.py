@@ -31,9 +31,9 @@ MM_CHECK_EVERY = 50
 MM_TOL = 1e-11
 
 
-def one_hot_rows(labels, n_class):
+def one_hot_rows(labels, n_class, dtype=torch.float32):
     """(N,S) int64 -> (N,S,K) f32, as src/utils.py:18-24 builds it (rows of an identity)."""
-    eye = torch.eye(n_class)
+    eye = torch.eye(n_class, dtype=dtype)
     return torch.stack([eye[row] for row in labels], 0)
 
 
@@ -176,12 +176,13 @@ def clustering_accuracy(u, x_q, y_q, n_class, graph_matching=True):
     return acc, new_preds
 
 
-def run_soft_kmeans(x_q, *, n_class, iters, temperature):
+def run_soft_kmeans(x_q, *, n_class, iters, temperature, dtype=torch.float32):
     """SOFT_KMEANS on probability features, the reference's torch op sequence
     (src/methods/zero_shot/soft_kmeans.py:105-220): w = u^T z / sum u (empty clusters keep their
     centroid), u = softmax_k(-T/2 ||w_k - z_q||^2).  Returns dict(u, w, criterions, seconds);
-    the logged criterion is identically 0 (the reference compares u with a copy of itself)."""
-    query = x_q.clone().float()
+    the logged criterion is identically 0 (the reference compares u with a copy of itself).
+    dtype=torch.float64 (here and in the restatements below) runs the inputs and the whole op sequence in double."""
+    query = x_q.clone().to(dtype)
     t0 = time.time()
     u = query.clone()
     num = (query.unsqueeze(2) * u.unsqueeze(3)).sum(1)
@@ -200,13 +201,13 @@ def run_soft_kmeans(x_q, *, n_class, iters, temperature):
     return {"u": u, "w": w, "criterions": torch.stack(criterions), "seconds": time.time() - t0}
 
 
-def run_hard_kmeans(x_q, *, n_class, iters):
+def run_hard_kmeans(x_q, *, n_class, iters, dtype=torch.float32):
     """HARD_KMEANS on probability features, the reference's torch op sequence
     (src/methods/zero_shot/hard_kmeans.py:26-35, 128-152, 186-204): w = u^T z / sum u with empty
     clusters set to ZERO, u = one_hot(argmin_k softmax_k(||w_k - z_q||^2)) - the softmax is kept
     because ties after its rounding decide the argmin.  Returns dict(u, w, criterions (iters,),
     labels (iters,N,Q), seconds); the reference logs every criterion twice."""
-    query = x_q.clone().float()
+    query = x_q.clone().to(dtype)
     t0 = time.time()
     u = query.clone()
     u_old = u.clone()
@@ -229,17 +230,18 @@ def run_hard_kmeans(x_q, *, n_class, iters):
             "seconds": time.time() - t0}
 
 
-def run_paddle(x_q, x_s, y_s, *, n_class, iters, lambd):
+def run_paddle(x_q, x_s, y_s, *, n_class, iters, lambd, log=torch.log, dtype=torch.float32):
     """PADDLE on probability features, the reference's torch op sequence
     (src/methods/few_shot/paddle.py:94-219): prototypes from the support class means, then
     u = softmax_k(-1/2 ||w_k - z_q||^2 + lambd v_k / Q), v = log(mean_q u + eps) + 1,
     w = (sum_q u z + support sums) / (sum_q u + support counts).  Returns dict(u, v, w, criterions,
-    argmax (iters,N,Q), seconds); the logged criterion is identically 0."""
-    query, support = x_q.clone().float(), x_s.clone().float()
+    argmax (iters,N,Q), seconds); the logged criterion is identically 0.  `log` (here and below): the float32 logarithm, torch's
+    own unless the caller brings the host-independent one (tests/helpers/restated.py)."""
+    query, support = x_q.clone().to(dtype), x_s.clone().to(dtype)
     n_task, n_query = query.shape[0], query.shape[1]
     t0 = time.time()
-    v = torch.zeros(n_task, n_class)
-    ys_hot = one_hot_rows(y_s.long().view(n_task, -1), n_class)
+    v = torch.zeros(n_task, n_class, dtype=dtype)
+    ys_hot = one_hot_rows(y_s.long().view(n_task, -1), n_class, dtype)
     counts = ys_hot.sum(1).unsqueeze(-1)
     w = (ys_hot.unsqueeze(-1) * support.unsqueeze(2)).sum(1).div_(counts)
     criterions, argmax = [], []
@@ -249,7 +251,7 @@ def run_paddle(x_q, x_s, y_s, *, n_class, iters, lambd):
         logits = -1 / 2 * (diff.square_()).sum(dim=-1)
         u = (logits + lambd * v.unsqueeze(1) / n_query).softmax(2)
         argmax.append(u.argmax(2).clone())
-        v = torch.log(u.sum(1) / u.size(1) + EPS) + 1
+        v = log(u.sum(1) / u.size(1) + EPS) + 1
         num = (query.unsqueeze(2) * u.unsqueeze(3)).sum(1)
         den = u.sum(1)
         num.add_((support.unsqueeze(2) * ys_hot.unsqueeze(3)).sum(1))
@@ -260,15 +262,15 @@ def run_paddle(x_q, x_s, y_s, *, n_class, iters, lambd):
             "seconds": time.time() - t0}
 
 
-def run_em_gaussian(x_q, *, n_class, iters, temperature, lambd):
+def run_em_gaussian(x_q, *, n_class, iters, temperature, lambd, log=torch.log, dtype=torch.float32):
     """EM_GAUSSIAN on probability features, the reference's torch op sequence
     (src/methods/zero_shot/em_gaussian.py:107-229): SOFT_KMEANS plus the class-proportion term,
     u = softmax_k(T * (-1/2 ||w_k - z_q||^2) + lambd v_k / Q), v = log(mean_q u + eps) + 1.
     Returns dict(u, v, w, criterions, argmax (iters,N,Q), seconds); the logged criterion is 0."""
-    query = x_q.clone().float()
+    query = x_q.clone().to(dtype)
     n_task, n_query = query.shape[0], query.shape[1]
     t0 = time.time()
-    v = torch.zeros(n_task, n_class)
+    v = torch.zeros(n_task, n_class, dtype=dtype)
     u = query.clone()
     num = (query.unsqueeze(2) * u.unsqueeze(3)).sum(1)
     den = u.sum(1).clamp(min=EPS)
@@ -283,7 +285,7 @@ def run_em_gaussian(x_q, *, n_class, iters, temperature, lambd):
         logits = -1 / 2 * (diff.square_()).sum(dim=-1)
         u = (temperature * logits + lambd * v.unsqueeze(1) / n_query).softmax(2)
         argmax.append(u.argmax(2).clone())
-        v = torch.log(u.sum(1) / u.size(1) + EPS) + 1
+        v = log(u.sum(1) / u.size(1) + EPS) + 1
         criterions.append((u.clone() - u).norm(dim=(1, 2)).mean(0))
     return {"u": u, "v": v, "w": w, "criterions": torch.stack(criterions), "argmax": torch.stack(argmax),
             "seconds": time.time() - t0}
@@ -300,14 +302,14 @@ def _bdcspn_logits(w, samples):
     return -1 / 2 * (diff.square_()).sum(dim=-1)
 
 
-def run_bdcspn(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
+def run_bdcspn(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N", dtype=torch.float32):
     """BD-CSPN on probability features, the reference's torch op sequence
     (src/methods/few_shot/bdcspn.py:77-200): feature normalisation (CL2N / L2N / none), support
     class means, per task a query shift eta = mean(support) - mean(query), soft assignment of
     support + shifted queries to the means, rectified prototypes = assignment-weighted means of
     the normalised augmented set, prediction = argmax softmax(temp * -1/2 ||.||^2) against them.
     Returns dict(prototypes (N,K,C), u (N,Q,K), preds (N,Q), seconds)."""
-    support, query = x_s.clone().float(), x_q.clone().float()
+    support, query = x_s.clone().to(dtype), x_q.clone().to(dtype)
     y_s = y_s.long().view(support.shape[0], -1)
     t0 = time.time()
     train_mean = support.mean(1).unsqueeze(1)
@@ -320,8 +322,8 @@ def run_bdcspn(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
         support = support / support.norm(p=2, dim=2, keepdim=True)
         query = query / query.norm(p=2, dim=2, keepdim=True)
     n_task, n_query, dim = query.shape
-    prototypes = torch.zeros(n_task, n_class, dim)
-    ys_hot = one_hot_rows(y_s, n_class)
+    prototypes = torch.zeros(n_task, n_class, dim, dtype=dtype)
+    ys_hot = one_hot_rows(y_s, n_class, dtype)
     counts = ys_hot.sum(1).unsqueeze(-1)
     init = (ys_hot.unsqueeze(-1) * support.unsqueeze(2)).sum(1).div_(counts)
     for j in range(n_task):
@@ -335,16 +337,16 @@ def run_bdcspn(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
     return {"prototypes": prototypes, "u": u, "preds": u.argmax(2), "seconds": time.time() - t0}
 
 
-def run_em_gaussian_cov(x_q, *, n_class, iters, lambd):
+def run_em_gaussian_cov(x_q, *, n_class, iters, lambd, log=torch.log, dtype=torch.float32):
     """EM_GAUSSIAN_COV on probability features, the reference's torch op sequence
     (src/methods/zero_shot/em_gaussian_cov.py:106-257): EM_GAUSSIAN with a diagonal inverse
     covariance s per cluster, s = sum_q u / clamp(sum_q u (w - z_q)^2, eps),
     u = softmax_k(-1/2 sum_d s (w - z)^2 + 1/2 sum_d log(s + eps) + lambd v_k / Q); no temperature.
     Returns dict(u, v, w, s, criterions, argmax (iters,N,Q), seconds)."""
-    query = x_q.clone().float()
+    query = x_q.clone().to(dtype)
     n_task, n_query = query.shape[0], query.shape[1]
     t0 = time.time()
-    v = torch.zeros(n_task, n_class)
+    v = torch.zeros(n_task, n_class, dtype=dtype)
     u = query.clone()
     num = (query.unsqueeze(2) * u.unsqueeze(3)).sum(1)
     den = u.sum(1).clamp(min=EPS)
@@ -361,22 +363,23 @@ def run_em_gaussian_cov(x_q, *, n_class, iters, lambd):
         s = (u.sum(1)).unsqueeze(2) / d_q.clamp(min=EPS) * live + (s * (1 - 1 * live))
         diff = w.unsqueeze(1) - query.unsqueeze(2)
         logits = -1 / 2 * ((diff.square_()).mul_(s.unsqueeze(1))).sum(dim=-1)
-        det = 1 / 2 * (torch.log(s + EPS).sum(-1)).unsqueeze(1)
+        det = 1 / 2 * (log(s + EPS).sum(-1)).unsqueeze(1)
         u = (logits + det + lambd * v.unsqueeze(1) / n_query).softmax(2)
         argmax.append(u.argmax(2).clone())
-        v = torch.log(u.sum(1) / u.size(1) + EPS) + 1
+        v = log(u.sum(1) / u.size(1) + EPS) + 1
         criterions.append((u.clone() - u).norm(dim=(1, 2)).mean(0))
     return {"u": u, "v": v, "w": w, "s": s, "criterions": torch.stack(criterions), "argmax": torch.stack(argmax),
             "seconds": time.time() - t0}
 
 
-def run_kl_kmeans(x_q, *, n_class, iters):
+def run_kl_kmeans(x_q, *, n_class, iters, log=torch.log, bmm=None, dtype=torch.float32):
     """KL_KMEANS on probability features, the reference's torch op sequence
     (src/methods/zero_shot/kl_kmeans.py:123-189): centroids w = (u^T z) / max(sum u, 1) (a bmm),
     zero for empty clusters; every query goes to the centroid of smallest
     KL(z + eps || w + eps) = sum_d P log(P / Q).  Returns dict(u, w, criterions (iters,),
-    labels (iters,N,Q), seconds); the reference logs every criterion twice."""
-    query = x_q.clone().float()
+    labels (iters,N,Q), seconds); the reference logs every criterion twice.  `bmm`: a stand-in for the `@` of the centroids
+    (MKL's sgemm, whose sum order follows the host's CPU), as `log` is one for torch.log."""
+    query = x_q.clone().to(dtype)
     t0 = time.time()
     u = query.clone()
     u_old = u.clone()
@@ -385,11 +388,11 @@ def run_kl_kmeans(x_q, *, n_class, iters):
     for _ in range(iters):
         cluster_sizes = u.sum(1).unsqueeze(-1)
         nonzero = cluster_sizes > 0
-        w = (u.transpose(1, 2) @ query) / cluster_sizes.clamp(min=1)
-        w *= nonzero.float()
+        w = (u.transpose(1, 2) @ query if bmm is None else bmm(u.transpose(1, 2), query)) / cluster_sizes.clamp(min=1)
+        w *= nonzero.to(dtype)
         P = query.unsqueeze(2) + EPS
         Qm = w.unsqueeze(1) + EPS
-        divs = torch.sum(P * torch.log(P / Qm), dim=-1)
+        divs = torch.sum(P * log(P / Qm), dim=-1)
         labels = torch.argmin(divs, dim=-1)
         u = torch.zeros_like(u)
         u.scatter_(2, labels.unsqueeze(-1), 1.0)

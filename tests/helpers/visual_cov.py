@@ -10,26 +10,13 @@ A cluster whose size sum_q u is <= eps keeps its w and s.
 The logarithm is a parameter.  torch.log on the host is MKL's vsLn, whose kernel follows the host's CPU: on the machine the
 fixtures were made on it is the one csrc/tclip_math.h restates (log_f32; tests/test_math_host.py pins the two to each other
 there), on another CPU vendor it is a few ulp off on a fraction of the arguments, and two of the loop's steps go through it.
-restated_log() is that restatement's host build (oracle/mathcheck.cpp, mc_log): the same bits on every host."""
-import ctypes
-
-import numpy as np
+restated_log() (tests/helpers/restated.py, re-exported here) is that restatement's host build (oracle/mathcheck.cpp, mc_log):
+the same bits on every host."""
 import torch
 
+from helpers.restated import restated_log      # noqa: F401
+
 EPS = 1e-15
-
-
-def restated_log():
-    """x -> log(x) for a float32 tensor, MKL's vsLn as the reference's host evaluates it"""
-    from oracle import build as oracle_build
-    lib = ctypes.CDLL(oracle_build.build()[1])
-
-    def log(x):
-        a = np.ascontiguousarray(x.numpy(), np.float32)
-        y = np.empty_like(a)
-        lib.mc_log(a.ctypes.data_as(ctypes.c_void_p), y.ctypes.data_as(ctypes.c_void_p), ctypes.c_long(a.size))
-        return torch.from_numpy(y)
-    return log
 
 
 def _w_stats(query, u):
