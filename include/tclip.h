@@ -39,7 +39,10 @@ extern "C" {
  *    tclip_match_clusters_workspace_bytes, tclip_match_clusters;
  *    tclip_em_gaussian_cov_visual_workspace_bytes, tclip_em_gaussian_cov_visual_run;
  *    tclip_gather_task_rows, tclip_paddle_tasks_workspace_bytes, tclip_paddle_run_tasks,
- *    tclip_paddle_visual_tasks_workspace_bytes, tclip_paddle_visual_run_tasks
+ *    tclip_paddle_visual_tasks_workspace_bytes, tclip_paddle_visual_run_tasks;
+ *    tclip_bdcspn_tasks_workspace_bytes, tclip_bdcspn_run_tasks, tclip_bdcspn_visual_tasks_workspace_bytes,
+ *    tclip_bdcspn_visual_run_tasks, tclip_laplacian_shot_tasks_workspace_bytes, tclip_laplacian_shot_run_tasks,
+ *    tclip_laplacian_shot_visual_tasks_workspace_bytes, tclip_laplacian_shot_visual_run_tasks
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -288,6 +291,40 @@ size_t tclip_paddle_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t
 int tclip_paddle_visual_run_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s,
                                   float lambd, float* u, float* v, float* w, int32_t* preds,
                                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* BD-CSPN and LAPLACIAN_SHOT fed from the feature TABLES of the task-batch loop (`src` and `y_s` exactly as for
+ * tclip_paddle_run_tasks): row r of task t is table[idx[t,r]], on probability features with its columns permuted by
+ * src->cols[t].  In both methods the first kernels that touch a task row normalise it into the workspace (BD-CSPN's CL2N
+ * also takes the support's column means first); those kernels read the table rows in place, so neither x_s [T,S,D] nor x_q
+ * [T,Q,D] is ever built.  One output row is computed from one source row by the same operations in the same order: the
+ * results are those of the dense entries on the materialised tensors, bit for bit.
+ *   src->table_q device [rows_q, D] f32, src->q_idx device [T, Q] i64;  src->table_s device [rows_s, D] f32, src->s_idx device
+ *   [T, S] i64;  D = n_class and src->cols device [T, K] i32 or NULL (probability features), D = dim and src->cols == NULL
+ *   (visual features: a non-NULL cols is TCLIP_ERR_ARG);  y_s device [T, S] i64 in 0..n_class-1 (after get_task's re-indexing
+ *   on probability features);  the other arguments and the outputs as for tclip_bdcspn[_visual]_run /
+ *   tclip_laplacian_shot[_visual]_run.
+ * Workspace.  BD-CSPN: the dense entry's regions, except that the normalised support rows zs [T,S,D] have none of their own:
+ * they lie at the start of the logit region, sized max(T (S+Q) K, T S D) floats (zs is dead before the logits are first
+ * written) - the dense workspace minus the smaller of the two.  LAPLACIAN_SHOT: the dense entry's workspace.
+ * Limits and checks are the dense entries', all before any launch: n_support >= 1, n_class in 2..1024, dim in 1..1024,
+ * norm_type, knn, null pointers - members of src included - (TCLIP_ERR_ARG), workspace of the matching *_tasks_workspace_bytes
+ * query, 256-byte aligned (TCLIP_ERR_WORKSPACE; the queries return 0 on bad input).  The entries do not know the tables' row
+ * counts: call tclip_check_task_indices on the index tensors and cols first (the Python binding does). */
+size_t tclip_bdcspn_tasks_workspace_bytes(const tclip_problem* p);
+int tclip_bdcspn_run_tasks(const tclip_problem* p, const tclip_task_source* src, const int64_t* y_s, float temp, int32_t norm_type,
+                           float* prototypes, float* u, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream);
+size_t tclip_bdcspn_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_bdcspn_visual_run_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s, float temp,
+                                  int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+size_t tclip_laplacian_shot_tasks_workspace_bytes(const tclip_problem* p);
+int tclip_laplacian_shot_run_tasks(const tclip_problem* p, const tclip_task_source* src, const int64_t* y_s, int32_t knn, double lmd,
+                                   int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter, double* energies,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+size_t tclip_laplacian_shot_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_laplacian_shot_visual_run_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s,
+                                          int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours,
+                                          int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ALPHA_TIM on probability features (reference: src/methods/few_shot/tim.py:192-322; feature dimension =
  * n_class).  Weights start as the class means of the support set; each of `iters` iterations takes one

@@ -30,6 +30,7 @@
 //   k_gather_log_features   u = z and log z read from a feature table through index tensors (tclip_em_dirichlet_run_tasks)
 //   k_gather_rows, k_gather_task_rows   task construction from a feature table: rows, and rows with a column permutation per task
 //   k_col_mean, k_bdcspn_normalize, k_bdcspn_eta   BD-CSPN normalisation (torch's norm order) and query shift
+//                             (k_col_mean and k_bdcspn_normalize: dense rows, or table rows read in place through a RowSrc)
 //   k_argmax_rows   inductive CLIP baseline
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -2213,19 +2214,32 @@ __device__ __forceinline__ float row_norm_torch(int K, int j, F get) {
 }
 
 // out[t,c] = mean_r x[t,r,c] = (torch outer sum over the R rows) / R      (bdcspn.py:165 train_mean, :127 eta)
-__global__ void k_col_mean(const float* __restrict__ x, int T, int R, int K, float* __restrict__ out) {
+// kIdx: row r of task t is table row x.idx[t R + r], its column c table column x.cols[t K + c] (x.cols == nullptr: c) - the
+// rows read in place; the sum runs over the same values in the same order (the cascade is chosen by the OUTPUT column c).
+template <bool kIdx>
+__global__ void k_col_mean(RowSrc x, int T, int R, int K, float* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)T * K) return;
     const int t = i / K, c = i % K;
-    const float* xt = x + (size_t)t * R * K;
-    out[i] = dsum_outer(R, c, K, [&](int r) { return xt[(size_t)r * K + c]; }) / (float)R;
+    if (kIdx) {
+        const int64_t* it = x.idx + (size_t)t * R;
+        const int cc = x.cols ? x.cols[(size_t)t * K + c] : c;
+        out[i] = dsum_outer(R, c, K, [&](int r) { return x.base[(size_t)it[r] * K + cc]; }) / (float)R;
+    } else {
+        const float* xt = x.base + (size_t)t * R * K;
+        out[i] = dsum_outer(R, c, K, [&](int r) { return xt[(size_t)r * K + c]; }) / (float)R;
+    }
 }
 
 // Feature normalisation (bdcspn.py:77-100) and get_logits' own (:50-51), eight lanes per row:
 //   mode 0 (UN) copy; 1 (L2N) x / ||x||; 2 (CL2N) (x - mean_t) / ||x - mean_t||.
 // With `shift` (rows >= shift_from of every task get + shift[t,:] first; the augmented set of
-// proto_rectification, :128-131) the source rows come from two arrays: rows < R0 from x, the rest from x2.
-__global__ __launch_bounds__(256) void k_bdcspn_normalize(const float* __restrict__ x, const float* __restrict__ x2, int R0,
+// proto_rectification, :128-131) the source rows come from two arrays: rows < R0 from x.base, the rest from x2.
+// kIdx (one source, R0 == R, x2 unused): row r of task t is table row x.idx[t R + r] with its columns permuted by
+// x.cols[t,:] (nullptr: identity) - a row starts elsewhere and its element d sits at cols[d], nothing else changes.  The
+// permuted loads stay inside that one table row (at most 4 KB); the eight lanes of a row store consecutive words.
+template <bool kIdx>
+__global__ __launch_bounds__(256) void k_bdcspn_normalize(RowSrc x, const float* __restrict__ x2, int R0,
                                                           int R, int K, int mode, const float* __restrict__ mean,
                                                           const float* __restrict__ shift, int n_rows,
                                                           float* __restrict__ out) {
@@ -2233,11 +2247,18 @@ __global__ __launch_bounds__(256) void k_bdcspn_normalize(const float* __restric
     const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 3;
     if (row >= n_rows) return;
     const int t = row / R, r = row % R;
-    const float* src = r < R0 ? x + ((size_t)t * R0 + r) * K : x2 + ((size_t)t * (R - R0) + (r - R0)) * K;
+    const float* src;
+    const int32_t* ct = nullptr;
+    if (kIdx) {
+        src = x.base + (size_t)x.idx[(size_t)t * R + r] * K;
+        ct = x.cols ? x.cols + (size_t)t * K : nullptr;
+    } else {
+        src = r < R0 ? x.base + ((size_t)t * R0 + r) * K : x2 + ((size_t)t * (R - R0) + (r - R0)) * K;
+    }
     const float* mt = mean ? mean + (size_t)t * K : nullptr;
     const float* sh = (shift && r >= R0) ? shift + (size_t)t * K : nullptr;
     auto get = [&](int d) {
-        float v = src[d];
+        float v = src[(kIdx && ct) ? ct[d] : d];
         if (sh) v = v + sh[d];
         if (mode == 2) v = v - mt[d];
         return v;

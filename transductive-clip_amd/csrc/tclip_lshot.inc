@@ -4,6 +4,8 @@
 // count K: rows, prototypes and the kNN distances live in D, the unary term, Y and everything after the kNN step in K.
 // tclip_laplacian_shot_run is the probability-feature entry (D = K, distances inside k_lshot_task as before),
 // tclip_laplacian_shot_visual_run the one for D-dim embeddings (any D in 1..1024; distances by k_lshot_pairdist).
+// tclip_laplacian_shot[_visual]_run_tasks are the same two fed from the feature tables: k_lshot_normalize reads the task rows
+// in place through a RowSrc, everything after it is shared.
 //
 // Per task: L2-normalised features, prototypes = support class means, unary[q][k] = ||proto_k - z_q||^2, a kNN graph
 // over the task's queries (W[i][j] = 1 for the knn-1 nearest other queries j of i), then `iter` bound updates
@@ -26,18 +28,24 @@ __device__ __forceinline__ double lshot_wave_sum(double v) {
 }
 
 // out = x / ||x||_2 row by row (mode 1, laplacian_shot.py:83-85) or a plain copy (mode 0, 'UN').
-__global__ void k_lshot_normalize(const float* __restrict__ x, int n_rows, int D, int mode, float* __restrict__ out) {
+// kIdx: row `row` is table row x.idx[row], its element d table column x.cols[(row / rows_per_task) D + d] (x.cols == nullptr:
+// d) - the task rows read in place.  A lane still owns the elements d = lane, lane + 64, ...: same values, same sums; the
+// permuted loads stay inside one table row of at most 4 KB and the stores stay coalesced.
+template <bool kIdx>
+__global__ void k_lshot_normalize(RowSrc x, int rows_per_task, int n_rows, int D, int mode, float* __restrict__ out) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows) return;
-    const float* r = x + (size_t)row * D;
+    const float* r = kIdx ? x.base + (size_t)x.idx[row] * D : x.base + (size_t)row * D;
+    const int32_t* c = (kIdx && x.cols) ? x.cols + (size_t)(row / rows_per_task) * D : nullptr;
+    auto get = [&](int d) { return r[(kIdx && c) ? c[d] : d]; };
     float nrm = 1.0f;
     if (mode == 1) {
         double s = 0.0;
-        for (int d = lane; d < D; d += 64) s += (double)r[d] * (double)r[d];
+        for (int d = lane; d < D; d += 64) s += (double)get(d) * (double)get(d);
         s = lshot_wave_sum(s);
         nrm = (float)sqrt(s);
     }
-    for (int d = lane; d < D; d += 64) out[(size_t)row * D + d] = mode == 1 ? r[d] / nrm : r[d];
+    for (int d = lane; d < D; d += 64) out[(size_t)row * D + d] = mode == 1 ? get(d) / nrm : get(d);
 }
 
 // unary[t][q][k] = ||proto[t][k] - z[t][q]||^2 (the reference squares LA.norm's fp32 square root, :236-238).
@@ -324,7 +332,7 @@ static int check_lshot(const tclip_problem* pp, int32_t knn, int32_t norm_type) 
 // The launch sequence of both entries on rows of D elements: the support class sums of k_support_stats at D = K and of
 // k_vis_support_stats otherwise; pairdist = false (probability features): the distances inside k_lshot_task, true (visual
 // features): k_lshot_pairdist's table.
-static int lshot_run(const tclip_problem& p, int D, bool pairdist, const float* x_q, const float* x_s, const int64_t* y_s,
+static int lshot_run(const tclip_problem& p, int D, bool pairdist, const RowSrc& x_q, const RowSrc& x_s, const int64_t* y_s,
                      int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter,
                      double* energies, char* ws, hipStream_t st) {
     const LshotWs o = lshot_ws(p, D, pairdist);
@@ -337,9 +345,17 @@ static int lshot_run(const tclip_problem& p, int D, bool pairdist, const float* 
     float* cnt = (float*)(ws + o.cnt);
     float* proto = (float*)(ws + o.proto);
     double* d2 = pairdist ? (double*)(ws + o.d2) : nullptr;
-    // normalization (:66-89), prototypes = class means of the normalised support (:201-205)
-    hipLaunchKernelGGL(k_lshot_normalize, dim3((T * S + 3) / 4), dim3(256), 0, st, x_s, T * S, D, norm_type, zs);
-    hipLaunchKernelGGL(k_lshot_normalize, dim3((T * Q + 3) / 4), dim3(256), 0, st, x_q, T * Q, D, norm_type, zq);
+    // normalization (:66-89), prototypes = class means of the normalised support (:201-205); the only launches that read the
+    // task rows: a dense tensor, or table rows in place (x.idx != nullptr)
+    auto normalize = [&](const RowSrc& x, int rows_per_task, float* out) {
+        const int n_rows = T * rows_per_task;
+        if (x.idx)
+            hipLaunchKernelGGL(k_lshot_normalize<true>, dim3((n_rows + 3) / 4), dim3(256), 0, st, x, rows_per_task, n_rows, D, norm_type, out);
+        else
+            hipLaunchKernelGGL(k_lshot_normalize<false>, dim3((n_rows + 3) / 4), dim3(256), 0, st, x, rows_per_task, n_rows, D, norm_type, out);
+    };
+    normalize(x_s, S, zs);
+    normalize(x_q, Q, zq);
     if (D != K)                                                       // as tim_loop: D = K keeps the probability entry's sums
         launch_vis_support_stats(st, zs, y_s, T, S, K, D, sup, cnt);
     else
@@ -354,6 +370,21 @@ static int lshot_run(const tclip_problem& p, int D, bool pairdist, const float* 
     hipLaunchKernelGGL(k_lshot_task, dim3(T), dim3(64 * kLshotWaves), smem, st, a);
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
+}
+
+// The entries fed from the feature tables: check_lshot, then the dense entries' checks with `src` in place of x_q / x_s
+static int lshot_run_tasks(const tclip_problem* pp, int dim, bool visual, const tclip_task_source* src, const int64_t* y_s, int32_t knn,
+                           double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter, double* energies,
+                           void* workspace, size_t workspace_bytes, const char* query_name, void* stream) {
+    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
+    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !unary || !neighbours || !preds_iter ||
+        !energies || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT on visual features permutes no columns: cols must be NULL");
+    const tclip_problem p = *pp;
+    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, dim, visual).total, query_name)) return rc;
+    return lshot_run(p, dim, visual, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, knn,
+                     lmd, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace, (hipStream_t)stream);
 }
 
 }  // namespace tclip
@@ -375,8 +406,8 @@ int tclip_laplacian_shot_run(const tclip_problem* pp, const float* x_q, const fl
         return fail(TCLIP_ERR_ARG, "null pointer argument");
     if (int rc = check_lshot(pp, knn, norm_type)) return rc;
     if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, p.n_class, false).total, "tclip_laplacian_shot_workspace_bytes")) return rc;
-    return lshot_run(p, p.n_class, false, x_q, x_s, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace,
-                     (hipStream_t)stream);
+    return lshot_run(p, p.n_class, false, dense_rows(x_q), dense_rows(x_s), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter,
+                     energies, (char*)workspace, (hipStream_t)stream);
 }
 
 size_t tclip_laplacian_shot_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
@@ -396,8 +427,40 @@ int tclip_laplacian_shot_visual_run(const tclip_problem* pp, int32_t dim, const 
     const tclip_problem p = *pp;
     if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, dim, true).total, "tclip_laplacian_shot_visual_workspace_bytes"))
         return rc;
-    return lshot_run(p, dim, true, x_q, x_s, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace,
-                     (hipStream_t)stream);
+    return lshot_run(p, dim, true, dense_rows(x_q), dense_rows(x_s), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies,
+                     (char*)workspace, (hipStream_t)stream);
+}
+
+// ---- LAPLACIAN_SHOT fed from the feature tables: the two normalisations read the task rows in place, x_s and x_q are never
+// built; workspace, checks and everything after the normalisations are the dense entries'
+size_t tclip_laplacian_shot_tasks_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive"), 0;
+    return lshot_ws(*p, p->n_class, false).total;
+}
+
+size_t tclip_laplacian_shot_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024"), 0;
+    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive"), 0;
+    return lshot_ws(*p, dim, true).total;
+}
+
+int tclip_laplacian_shot_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, int32_t knn, double lmd,
+                                   int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter, double* energies,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    return lshot_run_tasks(pp, pp->n_class, false, src, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
+                           workspace_bytes, "tclip_laplacian_shot_tasks_workspace_bytes", stream);
+}
+
+int tclip_laplacian_shot_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s,
+                                          int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours,
+                                          int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
+    return lshot_run_tasks(pp, dim, true, src, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
+                           workspace_bytes, "tclip_laplacian_shot_visual_tasks_workspace_bytes", stream);
 }
 
 }  // extern "C"

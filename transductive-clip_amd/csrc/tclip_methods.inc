@@ -6,6 +6,8 @@
 // launchers whose work depends on the row length (three, and EM_GAUSSIAN_COV's two), everything else ([T, Q, K] / [T, K]
 // tensors: the softmax, the cluster sizes, v, the first-minimum one-hot, the criterion) is shared as it stands.  KL_KMEANS
 // exists on probability features only and keeps its own loop below.  EM-Dirichlet does not come through here.
+// PADDLE and BD-CSPN also run from the feature tables (tclip_*_run_tasks): PADDLE's class sums and BD-CSPN's normalisations
+// read the task rows in place through a RowSrc.
 
 namespace tclip {
 
@@ -151,6 +153,32 @@ struct BdcspnWs {
         w.total = o;
         return w;
     }
+    // BD-CSPN fed from the feature tables (bdcspn_pass with indexed sources): the dense regions, except that zs has none of its
+    // own - it lies at the start of the logit region, which holds max(T R K, T S D) floats.  Their lifetimes in bdcspn_pass do
+    // not overlap: zs is written by the first normalisation and last read by the normalisation that builds aug (after the
+    // support statistics and k_bdcspn_eta); logit is first written by the sp.dist that follows it, on the same stream, and
+    // nothing after that reads zs.
+    static BdcspnWs layout_tasks(const tclip_problem& p, int dim) {
+        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
+        BdcspnWs w;
+        size_t o = 0;
+        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
+        w.zq = take(T * Q * D * 4);
+        w.zqn = take(T * Q * D * 4);
+        w.mean = take(T * D * 4);
+        w.eta = take(T * D * 4);
+        w.sup = take(T * K * D * 4);
+        w.cnt = take(T * K * 4);
+        w.wn = take(T * K * D * 4);
+        w.aug = take(T * R * D * 4);
+        w.logit = take((R * K > S * D ? T * R * K : T * S * D) * 4);
+        w.zs = w.logit;
+        w.cs = take(T * K * 4);
+        w.live = take(T * K);
+        w.dummy = take(T * R * 4);
+        w.total = o;
+        return w;
+    }
 };
 
 // ---- SOFT_KMEANS, EM_GAUSSIAN, HARD_KMEANS (SURVEY.md section 8f, F1; BASELINE config 3's second method) ----------------
@@ -280,9 +308,10 @@ static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const flo
 
 // ---- BD-CSPN (SURVEY.md F4): one pass, no loop ------------------------------------------------------------------------
 // k_col_mean, k_bdcspn_normalize, k_bdcspn_eta and k_div_rows take the row length where their signatures say K.
-static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
-                       int norm_type, float* prototypes, float* u, int32_t* preds, char* ws, hipStream_t st) {
-    const BdcspnWs o = BdcspnWs::layout(p, sp.D);
+// x_q / x_s: dense tensors, or table rows read in place by the only three launches that touch them (the train mean and the
+// two normalisations into zs / zq); `o`: BdcspnWs::layout for the former, ::layout_tasks (zs inside logit) for the latter.
+static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const BdcspnWs& o, const RowSrc& x_q, const RowSrc& x_s,
+                       const int64_t* y_s, float temp, int norm_type, float* prototypes, float* u, int32_t* preds, char* ws, hipStream_t st) {
     const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, R = S + Q, T = p.n_batches * p.tasks_per_batch, TK = T * K;
     const int TD = T * D;
     float* zs = (float*)(ws + o.zs);
@@ -300,12 +329,24 @@ static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const flo
     int32_t* dummy = (int32_t*)(ws + o.dummy);
     auto rows_grid = [](int n_rows) { return dim3((unsigned)(((size_t)n_rows * 8 + 255) / 256)); };
     auto normalize = [&](const float* x, const float* x2, int R0, int Rr, int mode, const float* mn, const float* sh, float* out) {
-        hipLaunchKernelGGL(k_bdcspn_normalize, rows_grid(T * Rr), dim3(256), 0, st, x, x2, R0, Rr, D, mode, mn, sh, T * Rr, out);
+        hipLaunchKernelGGL(k_bdcspn_normalize<false>, rows_grid(T * Rr), dim3(256), 0, st, dense_rows(x), x2, R0, Rr, D, mode, mn, sh,
+                           T * Rr, out);
+    };
+    // the task rows: one source of Rr rows per task
+    auto normalize_rows = [&](const RowSrc& x, int Rr, float* out) {
+        if (x.idx)
+            hipLaunchKernelGGL(k_bdcspn_normalize<true>, rows_grid(T * Rr), dim3(256), 0, st, x, (const float*)nullptr, Rr, Rr, D,
+                               norm_type, (const float*)mean, (const float*)nullptr, T * Rr, out);
+        else
+            normalize(x.base, x.base, Rr, Rr, norm_type, (const float*)mean, (const float*)nullptr, out);
     };
     // normalization (bdcspn.py:77-100, :165-166): train_mean = support.mean(1), an outer sum over D columns; CL2N / L2N / none
-    if (norm_type == 2) hipLaunchKernelGGL(k_col_mean, dim3((TD + 255) / 256), dim3(256), 0, st, x_s, T, S, D, mean);
-    normalize(x_s, x_s, S, S, norm_type, (const float*)mean, (const float*)nullptr, zs);
-    normalize(x_q, x_q, Q, Q, norm_type, (const float*)mean, (const float*)nullptr, zq);
+    if (norm_type == 2) {
+        if (x_s.idx) hipLaunchKernelGGL(k_col_mean<true>, dim3((TD + 255) / 256), dim3(256), 0, st, x_s, T, S, D, mean);
+        else hipLaunchKernelGGL(k_col_mean<false>, dim3((TD + 255) / 256), dim3(256), 0, st, x_s, T, S, D, mean);
+    }
+    normalize_rows(x_s, S, zs);
+    normalize_rows(x_q, Q, zq);
     // initial prototypes: support class means (:117-120), L2-normalised for get_logits (:50)
     sp.support_stats(st, dense_rows(zs), y_s, T, S, K, sup, cnt);
     hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
@@ -589,8 +630,8 @@ int tclip_bdcspn_run(const tclip_problem* pp, const float* x_q, const float* x_s
     if (p.n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN");
     if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
     if (int rc = check_workspace(workspace, workspace_bytes, BdcspnWs::layout(p, p.n_class).total, "tclip_bdcspn_workspace_bytes")) return rc;
-    return bdcspn_pass(FeatureSpace{p.n_class, false}, p, x_q, x_s, y_s, temp, norm_type, prototypes, u, preds, (char*)workspace,
-                       (hipStream_t)stream);
+    return bdcspn_pass(FeatureSpace{p.n_class, false}, p, BdcspnWs::layout(p, p.n_class), dense_rows(x_q), dense_rows(x_s), y_s, temp,
+                       norm_type, prototypes, u, preds, (char*)workspace, (hipStream_t)stream);
 }
 
 size_t tclip_bdcspn_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
@@ -606,8 +647,50 @@ int tclip_bdcspn_visual_run(const tclip_problem* pp, int32_t dim, const float* x
     if (!x_q || !x_s || !y_s || !prototypes || !u || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
     if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
     if (int rc = check_workspace(workspace, workspace_bytes, BdcspnWs::layout(p, dim).total, "tclip_bdcspn_visual_workspace_bytes")) return rc;
-    return bdcspn_pass(FeatureSpace{dim, true}, p, x_q, x_s, y_s, temp, norm_type, prototypes, u, preds, (char*)workspace,
-                       (hipStream_t)stream);
+    return bdcspn_pass(FeatureSpace{dim, true}, p, BdcspnWs::layout(p, dim), dense_rows(x_q), dense_rows(x_s), y_s, temp, norm_type,
+                       prototypes, u, preds, (char*)workspace, (hipStream_t)stream);
+}
+
+// BD-CSPN from the feature tables on rows of `dim` elements: bdcspn_pass reads both row sets in place, neither x_s nor x_q is
+// built, and zs shares the logit region (BdcspnWs::layout_tasks)
+static int bdcspn_run_tasks(const FeatureSpace& sp, const tclip_problem& p, const tclip_task_source* src, const int64_t* y_s, float temp,
+                            int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace, size_t workspace_bytes,
+                            const char* query_name, hipStream_t st) {
+    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !prototypes || !u || !preds || !workspace)
+        return fail(TCLIP_ERR_ARG, kNullArg);
+    if (sp.visual && src->cols) return fail(TCLIP_ERR_ARG, "BDCSPN on visual features permutes no columns: cols must be NULL");
+    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
+    const BdcspnWs o = BdcspnWs::layout_tasks(p, sp.D);
+    if (int rc = check_workspace(workspace, workspace_bytes, o.total, query_name)) return rc;
+    return bdcspn_pass(sp, p, o, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, temp,
+                       norm_type, prototypes, u, preds, (char*)workspace, st);
+}
+
+size_t tclip_bdcspn_tasks_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    if (p->n_support < 1) { fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN"); return 0; }
+    return BdcspnWs::layout_tasks(*p, p->n_class).total;
+}
+
+int tclip_bdcspn_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, float temp, int32_t norm_type,
+                           float* prototypes, float* u, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    if (pp->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN");
+    return bdcspn_run_tasks(FeatureSpace{pp->n_class, false}, *pp, src, y_s, temp, norm_type, prototypes, u, preds, workspace,
+                            workspace_bytes, "tclip_bdcspn_tasks_workspace_bytes", (hipStream_t)stream);
+}
+
+size_t tclip_bdcspn_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    if (check_visual_fs(p, dim, "BDCSPN") != TCLIP_OK) return 0;
+    return BdcspnWs::layout_tasks(*p, dim).total;
+}
+
+int tclip_bdcspn_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, float temp,
+                                  int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (int rc = check_visual_fs(pp, dim, "BDCSPN")) return rc;
+    return bdcspn_run_tasks(FeatureSpace{dim, true}, *pp, src, y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes,
+                            "tclip_bdcspn_visual_tasks_workspace_bytes", (hipStream_t)stream);
 }
 
 }  // extern "C"

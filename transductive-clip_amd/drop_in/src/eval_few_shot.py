@@ -218,7 +218,11 @@ class Evaluator_few_shot:
                 rel = relabel_indices(y_s, y_q, K) if a.use_softmax_feature else (None, y_s, y_q)
             # The EM-Dirichlet classes and PADDLE read the task rows from the tables through the index tensors (label flip and
             # column permutation inside the kernels): x_s (T,S,K) - 1.6 GB per 100 tasks at K = 1000, 4 shots - is never built
+            # in_place_support (absent or False: the route above and below as it always was): BDCSPN and LAPLACIAN_SHOT, whose
+            # first kernels normalise the task rows into their workspace, read them from the tables too
             in_place = m.reads_rows_in_place(a.use_softmax_feature)
+            if not in_place and getattr(a, 'in_place_support', False) and hasattr(m, 'can_read_rows_in_place'):
+                in_place = m.can_read_rows_in_place(a.use_softmax_feature)
             if rel is not None:
                 cols, y_s, y_q = rel
             if rel is not None and in_place:

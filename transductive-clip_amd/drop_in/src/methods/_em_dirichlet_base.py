@@ -210,6 +210,14 @@ class FewShotMixin:
     def reads_rows_in_place(cls, use_softmax_feature):
         return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_FEATURES
 
+    # the feature kinds on which run_tables reads the task rows in place only when the evaluator is asked to
+    # (args.in_place_support): these classes keep the builder route by default
+    IN_PLACE_SUPPORT = ()
+
+    @classmethod
+    def can_read_rows_in_place(cls, use_softmax_feature):
+        return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_SUPPORT
+
     def run_task(self, task_dic, shot=10):
         y_s, y_q = task_dic['y_s'], task_dic['y_q']
         support, query = task_dic['x_s'], task_dic['x_q']

@@ -3,7 +3,9 @@ src/methods/few_shot/bdcspn.py.  Same constructor / run_task / lo
 (args.norm_type, args.temp, args.n_class; one timestamp, one zero criterion, plain accuracy); the
 whole pass runs in libtclip.so, all tasks of the batch at once instead of the reference's per-task
 Python loop (:124-141): tclip_bdcspn_run when the feature width equals args.n_class, tclip_bdcspn_visual_run
-for D-dim embeddings otherwise (the reference never looks at use_softmax_feature here)."""
+for D-dim embeddings otherwise (the reference never looks at use_softmax_feature here).  run_tables, which the task-batch
+loop takes with `in_place_support: True`, reads both row sets from the feature tables in place (tclip_bdcspn_run_tasks /
+tclip_bdcspn_visual_run_tasks): the same bits without the (T,S,D) and (T,Q,D) tensors."""
 import numpy as np
 import torch
 
@@ -13,6 +15,7 @@ from tclip_amd import engine
 
 class BDCSPN(FewShotMixin, MethodBase):
     LOGGER_NAME = __name__
+    IN_PLACE_SUPPORT = ("softmax", "visual")
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)
@@ -42,6 +45,25 @@ class BDCSPN(FewShotMixin, MethodBase):
         else:
             call = lambda: engine.run_bdcspn_visual(query, support, y_s, n_class=self.n_class, temp=self.temp,      # noqa: E731
                                                     norm_type=norm_type)
+        self._run(call, y_q)
+
+    def run_tables(self, table_s, s_idx, table_q, q_idx, cols, y_s, y_q, n_batches=1):
+        """run_batch for the task-batch loop (Evaluator_few_shot.evaluate_tasks with in_place_support): the support / query
+        rows of task t are table_s[s_idx[t]] / table_q[q_idx[t]], on softmax features with the columns permuted by cols[t]
+        (None on visual features, whose labels are not re-indexed either).  Neither (T,S,D) nor (T,Q,D) is built.  Overrides
+        FewShotMixin.run_tables, which drives the EM-Dirichlet engine."""
+        if table_q.shape[1] == self.n_class:
+            call = lambda: engine.run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, temp=self.temp,      # noqa: E731
+                                                   norm_type=self.norm_type)
+        else:
+            if cols is not None:
+                raise ValueError("BDCSPN on visual features permutes no columns: cols must be None")
+            call = lambda: engine.run_bdcspn_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, n_class=self.n_class,      # noqa: E731
+                                                          temp=self.temp, norm_type=self.norm_type)
+        self._run(call, y_q)
+
+    def _run(self, call, y_q):
+        """the engine call, then the reference's bookkeeping"""
         (self.prototypes, self.u, self.preds), total = self._execute(" ==> Executing BD-CSPN", call)
         self.record_convergence(new_time=total, criterions=torch.zeros(1))
         self.compute_acc(y_q)

@@ -4,7 +4,9 @@ update, the evaluator reads the last column; `ent_energy` (n_task, iter); `crite
 prototypes, unary term, kNN graph and the bound updates run in libtclip.so (tclip_laplacian_shot_run), one workgroup per
 task instead of the reference's numpy / scipy.sparse / sklearn host loop.  Pinned to reference-made fixtures within a
 tolerance (tests/test_laplacian_shot.py).  The reference class itself does not run on numpy >= 1.24
-(`dtype=np.float`, laplacian_shot.py:100)."""
+(`dtype=np.float`, laplacian_shot.py:100).  run_tables, which the task-batch loop takes with `in_place_support: True`, reads
+the task rows from the feature tables in place (tclip_laplacian_shot_run_tasks): the same bits without the (T,S,K) and
+(T,Q,K) tensors."""
 import numpy as np
 
 from src.methods._em_dirichlet_base import FewShotMixin, MethodBase
@@ -13,6 +15,7 @@ from tclip_amd import engine
 
 class LAPLACIAN_SHOT(FewShotMixin, MethodBase):
     LOGGER_NAME = __name__
+    IN_PLACE_SUPPORT = ("softmax",)          # run_method refuses visual features, and so does run_tables
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)
@@ -38,11 +41,22 @@ class LAPLACIAN_SHOT(FewShotMixin, MethodBase):
     def run_method(self, support, query, y_s, y_q, n_batches=1):
         if query.shape[2] != self.args.num_classes_test:
             raise NotImplementedError("LAPLACIAN_SHOT here takes probability features (use_softmax_feature: True, feature dimension = n_class)")
+        self._run(lambda: engine.run_laplacian_shot(query, support, y_s, iters=self.iter, knn=self.knn, lmd=self.lmd,
+                                                    norm_type=self.norm_type), query.shape[0], y_q)
+
+    def run_tables(self, table_s, s_idx, table_q, q_idx, cols, y_s, y_q, n_batches=1):
+        """run_method for the task-batch loop (Evaluator_few_shot.evaluate_tasks with in_place_support): the support / query
+        rows of task t are table_s[s_idx[t]] / table_q[q_idx[t]] with the columns permuted by cols[t]; neither (T,S,K) nor
+        (T,Q,K) is built.  Overrides FewShotMixin.run_tables, which drives the EM-Dirichlet engine."""
+        if table_q.shape[1] != self.args.num_classes_test:
+            raise NotImplementedError("LAPLACIAN_SHOT here takes probability features (use_softmax_feature: True, feature dimension = n_class)")
+        self._run(lambda: engine.run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, iters=self.iter, knn=self.knn,
+                                                          lmd=self.lmd, norm_type=self.norm_type), q_idx.shape[0], y_q)
+
+    def _run(self, call, n_task, y_q):
+        """the engine call, then the reference's bookkeeping"""
         (self.unary, self.neighbours, self.preds_iter, energies), total = self._execute(
-            " ==> Executing LAPLACIAN SHOT with lmd = {}".format(self.lmd),
-            lambda: engine.run_laplacian_shot(query, support, y_s, iters=self.iter, knn=self.knn, lmd=self.lmd,
-                                              norm_type=self.norm_type))
-        n_task = query.shape[0]
+            " ==> Executing LAPLACIAN SHOT with lmd = {}".format(self.lmd), call)
         self.preds = self.preds_iter[:, -1, :]
         # accuracy after every update, on the host: means of 75 zeros and ones rounded as the reference's CPU op rounds them
         hit = (self.preds_iter.long().cpu() == y_q.cpu().unsqueeze(1)).float()          # (n_task, iter, Q)

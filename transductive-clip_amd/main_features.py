@@ -30,7 +30,9 @@ Few-shot task tensors are built on the device; EM-Dirichlet and PADDLE read thei
 `batches_per_call N` (few-shot; not a default: absent or 0 runs all batches of a rank in one engine call) runs at most N
 batches per call, each call with a method object of its own - what bounds the (tasks, support, width) tensors of BDCSPN, TIM
 and LaplacianShot at ImageNet scale; `materialise_tasks True` takes the reference's route instead (gather, then a per-task
-relabelling on the host) - same results either way.
+relabelling on the host) - same results either way.  `in_place_support True` (not a default: absent unless given) lets BDCSPN
+(both feature kinds) and LaplacianShot (softmax features) read their task rows from the tables too - same results, without
+the (tasks, support, width) and (tasks, query, width) tensors and, for BDCSPN, with a smaller workspace.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse

@@ -67,6 +67,19 @@ _SIGNATURES = {
                                                        ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_bdcspn_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_bdcspn_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, ctypes.c_float, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_bdcspn_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
+    "tclip_bdcspn_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_float, ctypes.c_int32,
+                                              _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_bdcspn_visual_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_bdcspn_visual_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P, ctypes.c_float,
+                                                     ctypes.c_int32, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_laplacian_shot_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
+    "tclip_laplacian_shot_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_int32,
+                                                      ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_laplacian_shot_visual_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_laplacian_shot_visual_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P,
+                                                             ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P, _P,
+                                                             ctypes.c_size_t, _P]),
     "tclip_hard_kmeans_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_hard_kmeans_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_kl_kmeans_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),

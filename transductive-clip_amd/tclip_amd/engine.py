@@ -282,8 +282,10 @@ def run_paddle(x_q, x_s, y_s, *, iters, lambd):
     return _run_paddle(x_q, x_s, y_s, x_q.shape[2], iters, lambd, visual=False)
 
 
-def _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, lambd, visual):
-    """PADDLE from the feature tables on rows of D elements (tclip_paddle_run_tasks / tclip_paddle_visual_run_tasks)"""
+def _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, method):
+    """What the entries fed from the feature tables share: the tables as contiguous f32 (rows,D) tensors of one width on one
+    device, the index tensors and cols range-checked (IndexError) and on that device, the labels checked against K.
+    -> (table_q, q_idx, table_s, s_idx, y_s, cols, struct tclip_task_source)"""
     _require_cuda(table_q, "table_q")
     _require_cuda(table_s, "table_s")
     if table_q.dim() != 2 or table_s.dim() != 2 or q_idx.dim() != 2 or s_idx.dim() != 2:
@@ -294,10 +296,10 @@ def _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, lambd
         raise ValueError("table_q and table_s must be (rows,D) tensors of one width on one device")
     q_idx = _index_tensor(q_idx, table_q.shape[0], dev, "q_idx")
     s_idx = _index_tensor(s_idx, table_s.shape[0], dev, "s_idx")
-    T, Q = q_idx.shape
+    T = q_idx.shape[0]
     S = s_idx.shape[1]
     if S < 1:
-        raise ValueError("PADDLE is a few-shot method: s_idx must be (T,S) with n_support = S positive")
+        raise ValueError(f"{method} is a few-shot method: s_idx must be (T,S) with n_support = S positive")
     y_s = y_s.reshape(y_s.shape[0], -1).long().to(dev).contiguous()
     if s_idx.shape[0] != T or tuple(y_s.shape) != (T, S):
         raise ValueError("s_idx and y_s must be (T,S) with the T of q_idx")
@@ -305,11 +307,19 @@ def _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, lambd
         raise ValueError(f"y_s holds a label outside 0..{K - 1}")
     if cols is not None:
         cols = _cols_tensor(cols, T, D, dev)
+    src = _capi.TaskSource(table_q.data_ptr(), q_idx.data_ptr(), table_s.data_ptr(), s_idx.data_ptr(),
+                           cols.data_ptr() if cols is not None else None)
+    return table_q, q_idx, table_s, s_idx, y_s, cols, src
+
+
+def _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, lambd, visual):
+    """PADDLE from the feature tables on rows of D elements (tclip_paddle_run_tasks / tclip_paddle_visual_run_tasks)"""
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "PADDLE")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
     stem, dim = ("tclip_paddle_visual", (ctypes.c_int32(D),)) if visual else ("tclip_paddle", ())
     c = _Call(dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
     u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
-    src = _capi.TaskSource(table_q.data_ptr(), q_idx.data_ptr(), table_s.data_ptr(), s_idx.data_ptr(),
-                           cols.data_ptr() if cols is not None else None)
     c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_float(float(lambd)), _ptr(u),
                                                      _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
     return u, v, w, preds
@@ -445,6 +455,42 @@ def run_laplacian_shot_visual(x_q, x_s, y_s, *, n_class, iters, knn, lmd, norm_t
     return _run_laplacian_shot(x_q, x_s, y_s, K, iters, knn, lmd, norm_type, visual=True)
 
 
+def _run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, knn, lmd, norm_type, visual):
+    """LAPLACIAN_SHOT from the feature tables on rows of D elements (tclip_laplacian_shot_run_tasks /
+    tclip_laplacian_shot_visual_run_tasks)"""
+    _check_lshot_norm(norm_type)
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "LAPLACIAN_SHOT")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    stem, dim = ("tclip_laplacian_shot_visual", (ctypes.c_int32(D),)) if visual else ("tclip_laplacian_shot", ())
+    c = _Call(dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
+    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
+    preds_iter, energies = c.empty(T, max(iters, 1), Q, dtype=torch.int32), c.empty(T, max(iters, 1), dtype=torch.float64)
+    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_int32(int(knn)),
+                                                     ctypes.c_double(float(lmd)), ctypes.c_int32(NORM_TYPES[norm_type]),
+                                                     _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies), ws, n, st))
+    return unary, nbr, preds_iter, energies
+
+
+def run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, knn, lmd, norm_type="L2N"):
+    """LAPLACIAN_SHOT fed from the task-batch loop's feature tables (tclip_laplacian_shot_run_tasks): table_q, table_s (rows,K)
+    f32 cuda, q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column
+    permutation of Tasks_Generator_few_shot.get_task or None -> what run_laplacian_shot returns on the materialised tensors,
+    bit for bit; neither (T,S,K) nor (T,Q,K) is built.  Not synchronised."""
+    return _run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], iters, knn, lmd, norm_type,
+                                     visual=False)
+
+
+def run_laplacian_shot_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, knn, lmd, norm_type="L2N"):
+    """LAPLACIAN_SHOT on visual features fed from the feature tables (tclip_laplacian_shot_visual_run_tasks): tables (rows,D)
+    with any D in 1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> the bits of
+    run_laplacian_shot_visual on the materialised tensors.  Not synchronised."""
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    return _run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, iters, knn, lmd, norm_type, visual=True)
+
+
 def argmax_rows(x):
     """x (..., K) f32 cuda -> int32 (...) indices of the first maximum of every row, cuda, not synchronised."""
     _require_cuda(x, "x")
@@ -482,6 +528,41 @@ def run_bdcspn(x_q, x_s, y_s, *, temp, norm_type="L2N"):
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
     return _run_bdcspn(x_q, x_s, y_s, x_q.shape[2], temp, norm_type, visual=False)
+
+
+def _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, temp, norm_type, visual):
+    """BD-CSPN from the feature tables on rows of D elements (tclip_bdcspn_run_tasks / tclip_bdcspn_visual_run_tasks)"""
+    if norm_type not in NORM_TYPES:
+        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "BDCSPN")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    stem, dim = ("tclip_bdcspn_visual", (ctypes.c_int32(D),)) if visual else ("tclip_bdcspn", ())
+    c = _Call(dev, _capi.Problem(1, T, Q, K, S, 1, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
+    prototypes, u, preds = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
+    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_float(float(temp)),
+                                                     ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u), _ptr(preds),
+                                                     ws, n, st))
+    return prototypes, u, preds
+
+
+def run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, temp, norm_type="L2N"):
+    """BD-CSPN fed from the task-batch loop's feature tables (tclip_bdcspn_run_tasks): table_q, table_s (rows,K) f32 cuda,
+    q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column permutation
+    of Tasks_Generator_few_shot.get_task or None -> (prototypes (T,K,K), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised:
+    the bits of run_bdcspn on the materialised tensors.  Neither (T,S,K) nor (T,Q,K) is built, and the workspace is smaller than
+    the dense one by the normalised support rows (they share the logits' region)."""
+    return _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], temp, norm_type, visual=False)
+
+
+def run_bdcspn_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, temp, norm_type="L2N"):
+    """BD-CSPN on visual features fed from the feature tables (tclip_bdcspn_visual_run_tasks): tables (rows,D) with any D in
+    1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> (rectified prototypes (T,K,D),
+    u (T,Q,K), preds (T,Q) i32): the bits of run_bdcspn_visual on the materialised tensors.  Not synchronised."""
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    return _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, temp, norm_type, visual=True)
 
 
 MATCHING = ("host", "device")
