@@ -42,7 +42,9 @@ extern "C" {
  *    tclip_paddle_visual_tasks_workspace_bytes, tclip_paddle_visual_run_tasks;
  *    tclip_bdcspn_tasks_workspace_bytes, tclip_bdcspn_run_tasks, tclip_bdcspn_visual_tasks_workspace_bytes,
  *    tclip_bdcspn_visual_run_tasks, tclip_laplacian_shot_tasks_workspace_bytes, tclip_laplacian_shot_run_tasks,
- *    tclip_laplacian_shot_visual_tasks_workspace_bytes, tclip_laplacian_shot_visual_run_tasks
+ *    tclip_laplacian_shot_visual_tasks_workspace_bytes, tclip_laplacian_shot_visual_run_tasks;
+ *    tclip_alpha_tim_tasks_workspace_bytes, tclip_alpha_tim_run_tasks, tclip_alpha_tim_visual_tasks_workspace_bytes,
+ *    tclip_alpha_tim_visual_run_tasks, tclip_tim_gd_tasks_workspace_bytes, tclip_tim_gd_run_tasks
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -389,6 +391,36 @@ int tclip_tim_gd_run(const tclip_problem* p, int32_t dim, double lr, float temp,
                      const float* x_q /*[T,Q,dim]*/, const float* x_s /*[T,S,dim]*/, const int64_t* y_s /*[T,S]*/,
                      float* weights /*[T,K,dim]*/, float* logits_q /*[T,Q,K]*/, int32_t* preds /*[T,Q]*/,
                      float* criterions /*[iters,T]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ALPHA_TIM and TIM_GD fed from the feature TABLES of the task-batch loop (`src` and `y_s` exactly as for
+ * tclip_paddle_run_tasks): row r of task t is table[idx[t,r]], on probability features with its columns permuted by
+ * src->cols[t].  Unlike the other methods these two read their task rows in EVERY Adam step (both GEMMs), not once: the row
+ * norms, the GEMMs and the class sums of the initial weights fetch the table rows in place, step after step, and neither
+ * x_s [T,S,D] nor x_q [T,Q,D] is ever built.  Every thread loads the value the dense kernels load at the same position of the
+ * same sum: the outputs are those of the dense entries on the materialised tensors, bit for bit.  What the indirection costs in
+ * time is measured in DESIGN.md 8j, not promised.
+ *   src->table_q device [rows_q, D] f32, src->q_idx device [T, Q] i64;  src->table_s device [rows_s, D] f32, src->s_idx device
+ *   [T, S] i64;  src->cols device [T, D] i32 or NULL where D == n_class (tclip_alpha_tim_run_tasks, and tclip_tim_gd_run_tasks
+ *   with dim == n_class), NULL otherwise (a non-NULL cols on tclip_alpha_tim_visual_run_tasks, or on tclip_tim_gd_run_tasks with
+ *   dim != n_class, is TCLIP_ERR_ARG);  y_s device [T, S] i64 in 0..n_class-1 (after get_task's re-indexing on probability
+ *   features);  the other arguments and the outputs as for the dense entries.
+ * Workspace: the dense entries' (each *_tasks_workspace_bytes returns what its dense query returns), 256-byte aligned.
+ * Limits and checks are the dense entries', all before any launch; a NULL src or a NULL member of it other than cols is
+ * TCLIP_ERR_ARG.  The entries do not know the tables' row counts: call tclip_check_task_indices on the index tensors and cols
+ * first (the Python binding does).  Interior GEMM tiles keep their 128-bit loads when there is no cols, D is a multiple of 4 and
+ * both table pointers are 16-byte aligned; any other table is read element by element, with the same result. */
+size_t tclip_alpha_tim_tasks_workspace_bytes(const tclip_problem* p);
+int tclip_alpha_tim_run_tasks(const tclip_problem* p, const tclip_tim_params* prm, const tclip_task_source* src, const int64_t* y_s,
+                              float* weights, float* logits_q, int32_t* preds, float* criterions, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t tclip_alpha_tim_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_alpha_tim_visual_run_tasks(const tclip_problem* p, int32_t dim, const tclip_tim_params* prm, const tclip_task_source* src,
+                                     const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+size_t tclip_tim_gd_tasks_workspace_bytes(const tclip_problem* p, int32_t dim);
+int tclip_tim_gd_run_tasks(const tclip_problem* p, int32_t dim, double lr, float temp, const float loss_weights[3],
+                           const tclip_task_source* src, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds,
+                           float* criterions, void* workspace, size_t workspace_bytes, void* stream);
 
 /* LAPLACIAN_SHOT on probability features (reference: src/methods/few_shot/laplacian_shot.py:66-249; feature
  * dimension = n_class).  Rows L2-normalised (norm_type 1) or left as they are (0), prototypes = support class

@@ -10,18 +10,40 @@
 //   dL/dW[k,:]     = T (sum_i G[i,k] x_i - (sum_i G[i,k]) w_k).
 // The reference's matmuls go through MKL and its backward through autograd's own operation order, so there is
 // no bit-level target here (unlike EM-Dirichlet): parity is pinned to fixtures within a float tolerance.
+// tclip_alpha_tim[_visual]_run_tasks and tclip_tim_gd_run_tasks are the same loops fed from the feature tables: every kernel that
+// touches a task row goes through TimRows<kIdx>::row, and kIdx = true reads the table rows in place in every step.
 // Per iteration: k_tim_gemm_mfma<false> (logits; 64x64 tiles on the matrix cores), k_tim_softmax, k_tim_marginal, k_tim_grad,
 // k_tim_gemm_mfma<true> (dW, also the column sums of G), k_tim_adam (one wavefront per weight row), k_tim_criterion.
 
 namespace tclip {
 
-struct TimRows {            // the support rows of a task followed by its query rows, D elements each
+// The support rows of a task followed by its query rows, D elements each.  kIdx = false: dense x_s [T,S,D] and x_q [T,Q,D].
+// kIdx = true: the rows of two feature tables read in place (tclip_*_run_tasks): row i of task t is
+// xs[s_idx[t S + i]] for i < S and xq[q_idx[t Q + (i - S)]] otherwise, its element d table column cols[t D + d] (cols == nullptr:
+// d).  The dense form carries no member of the indexed one: its kernels take the arguments they always took.
+template <bool kIdx>
+struct TimRows;
+template <>
+struct TimRows<false> {
     const float* xs;
     const float* xq;
     int S, Q, D;
     __device__ const float* row(int t, int i) const {
         return i < S ? xs + ((size_t)t * S + i) * D : xq + ((size_t)t * Q + (i - S)) * D;
     }
+};
+template <>
+struct TimRows<true> {
+    const float* xs;         // table_s [rows_s, D]
+    const float* xq;         // table_q [rows_q, D]
+    const int64_t* s_idx;    // [T, S]
+    const int64_t* q_idx;    // [T, Q]
+    const int32_t* cols;     // [T, D] or nullptr
+    int S, Q, D;
+    __device__ const float* row(int t, int i) const {
+        return i < S ? xs + (size_t)s_idx[(size_t)t * S + i] * D : xq + (size_t)q_idx[(size_t)t * Q + (i - S)] * D;
+    }
+    __device__ const int32_t* task_cols(int t) const { return cols ? cols + (size_t)t * D : nullptr; }
 };
 
 constexpr int kTimMarginalGd = 2;   // TimLoss::ent1 of TIM_GD: Shannon with the 1e-12 of tim.py:171-172 inside the logarithm
@@ -32,6 +54,8 @@ struct TimLoss {
 
 static void launch_vis_support_stats(hipStream_t st, const float* xs, const int64_t* ys, int T, int S, int K, int D, float* sup,
                                      float* cnt);   // tclip_visual_fs.inc
+static void launch_vis_support_stats(hipStream_t st, const RowSrc& xs, const int64_t* ys, int T, int S, int K, int D, float* sup,
+                                     float* cnt);   // tclip_visual_fs.inc: dense rows, or a feature table read in place
 
 constexpr int kTimTile = 64;
 
@@ -40,14 +64,24 @@ __device__ __forceinline__ float tim_wave_sum(float v) {
     return v;
 }
 
-// |x_i|^2 of every support / query row, once per run.
-__global__ void k_tim_row_sqnorm(TimRows X, int n_rows_total, float* __restrict__ xn) {
+// |x_i|^2 of every support / query row, once per run.  kIdx: the rows of the tables in place; a lane owns the same elements
+// d = lane, lane + 64, ... of the (column-permuted) row, so the sum is the dense one.
+template <bool kIdx>
+__global__ void k_tim_row_sqnorm(TimRows<kIdx> X, int n_rows_total, float* __restrict__ xn) {
     const int R = X.S + X.Q;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows_total) return;
     const float* x = X.row(row / R, row % R);
     float s = 0.0f;
-    for (int d = lane; d < X.D; d += 64) s = fmaf(x[d], x[d], s);
+    if constexpr (kIdx) {
+        const int32_t* c = X.task_cols(row / R);
+        for (int d = lane; d < X.D; d += 64) {
+            const float v = x[c ? c[d] : d];
+            s = fmaf(v, v, s);
+        }
+    } else {
+        for (int d = lane; d < X.D; d += 64) s = fmaf(x[d], x[d], s);
+    }
     s = tim_wave_sum(s);
     if (lane == 0) xn[row] = s;
 }
@@ -82,8 +116,12 @@ typedef float tim_f16x __attribute__((ext_vector_type(16)));
 
 // TILE = 64: one 32 x 32 MFMA tile per wavefront (more, smaller blocks: few tasks, class counts just above a multiple of 64);
 // TILE = 128: 2 x 2 MFMA tiles per wavefront (4 MFMAs per 4 LDS reads)
-template <bool kTN, int TILE>
-__global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, int K, const float* __restrict__ Bmat /* W (logits) or G (dW) */,
+// kIdx: the rows of X are table rows read in place (TimRows<true>).  A thread stages the same (row, depth) / (depth, column)
+// positions of a slice into the same LDS words, so the MFMAs accumulate the dense kernel's values in its order.  With cols the
+// elements are fetched one by one inside the table row just addressed (at most 4 KB); without, interior tiles keep the 128-bit
+// loads when the tables' base pointers are 16-byte aligned too (a table may be a view at an odd offset).
+template <bool kTN, int TILE, bool kIdx>
+__global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, const float* __restrict__ Bmat /* W (logits) or G (dW) */,
                                                        const float* __restrict__ wn, const float* __restrict__ xn, float temp,
                                                        float* __restrict__ C, float* __restrict__ cs) {
     constexpr int kPad = 1;                                          // odd row stride: the transposed stores of two depth groups hit different banks
@@ -112,7 +150,19 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, int K, const f
     // interior tiles of a problem whose rows are 16-byte aligned (row lengths a multiple of 4: every base pointer is a 256-byte
     // aligned workspace offset or a torch allocation) take their PER floats as 128-bit loads: a quarter of the load instructions.
     // The logits read rows of F elements only, dW rows of G (K elements) and of X (F elements)
-    const bool vec = (F & 3) == 0 && (!kTN || (K & 3) == 0) && m0 + TILE <= M && n0 + TILE <= N;      // block-uniform
+    bool rows_vec = true;                                            // block-uniform, like the rest of the predicate
+    const int32_t* c = nullptr;                                      // this task's column permutation, if any
+    const float* arow_in_place = nullptr;                            // !kTN: a thread stages the same row of X in every slice
+    if constexpr (kIdx) {
+        c = X.task_cols(t);
+        rows_vec = !c && ((reinterpret_cast<uintptr_t>(X.xs) | reinterpret_cast<uintptr_t>(X.xq)) & 15) == 0;
+        if (!kTN && m0 + id / kThreadsPerRow < M) arow_in_place = X.row(t, m0 + id / kThreadsPerRow);
+    }
+    auto col = [&](int d) {
+        if constexpr (kIdx) return c ? c[d] : d;
+        else return d;
+    };
+    const bool vec = (F & 3) == 0 && (!kTN || (K & 3) == 0) && m0 + TILE <= M && n0 + TILE <= N && rows_vec;      // block-uniform
     auto fetch = [&](int d0) {
         if (kTN) {
             const int pp = (id % kThreadsPerDepth) * PER, i = d0 + id / kThreadsPerDepth;
@@ -131,11 +181,11 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, int K, const f
 #pragma unroll
             for (int j = 0; j < PER; j++) {
                 a[j] = (grow && m0 + pp + j < M) ? grow[m0 + pp + j] : 0.0f;
-                b[j] = (xrow && n0 + pp + j < N) ? xrow[n0 + pp + j] : 0.0f;
+                b[j] = (xrow && n0 + pp + j < N) ? xrow[col(n0 + pp + j)] : 0.0f;
             }
         } else {
             const int row = id / kThreadsPerRow, kp = (id % kThreadsPerRow) * PER;
-            const float* arow = m0 + row < M ? X.row(t, m0 + row) : nullptr;
+            const float* arow = kIdx ? arow_in_place : m0 + row < M ? X.row(t, m0 + row) : nullptr;
             const float* brow = n0 + row < N ? Bmat + ((size_t)t * K + n0 + row) * F : nullptr;   // W row
             if (vec && d0 + kTimMfmaDepth <= D) {
 #pragma unroll
@@ -150,7 +200,7 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows X, int K, const f
 #pragma unroll
             for (int j = 0; j < PER; j++) {
                 const int d = d0 + kp + j;
-                a[j] = (arow && d < D) ? arow[d] : 0.0f;
+                a[j] = (arow && d < D) ? arow[col(d)] : 0.0f;
                 b[j] = (brow && d < D) ? brow[d] : 0.0f;
             }
         }
@@ -382,9 +432,13 @@ static TimWs tim_ws(const tclip_problem& p, int dim) {
 
 // The Adam loop of both methods on rows of D elements.  per_task = false (ALPHA_TIM): criterions [n_batches, iters], the mean over a
 // batch's tasks and classes; per_task = true (TIM_GD, tim.py:181): criterions [iters, T], the mean over a task's classes.
-static int tim_loop(const tclip_problem& p, int D, double lr, float temp, const TimLoss& loss, bool per_task, const float* x_q,
-                    const float* x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
-                    char* ws, hipStream_t st) {
+// X: the task rows as the three kernels that touch them read them (k_tim_row_sqnorm and the two GEMMs of every step), x_s: the
+// support rows as the class sums of init_weights read them - both dense, or both the feature tables in place (kIdx).
+template <bool kIdx>
+static int tim_loop_on(const tclip_problem& p, const TimRows<kIdx>& X, const RowSrc& x_s, double lr, float temp, const TimLoss& loss,
+                       bool per_task, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                       char* ws, hipStream_t st) {
+    const int D = X.D;
     const TimWs o = tim_ws(p, D);
     const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
     const int TR = T * R;
@@ -399,28 +453,27 @@ static int tim_loop(const tclip_problem& p, int D, double lr, float temp, const 
     float* M = (float*)(ws + o.M);
     float* V = (float*)(ws + o.V);
     float* moved = (float*)(ws + o.moved);
-    const TimRows X{x_s, x_q, S, Q, D};
     const int tiles_k = (K + kTimTile - 1) / kTimTile, tiles_r = (R + kTimTile - 1) / kTimTile, tiles_d = (D + kTimTile - 1) / kTimTile;
     // init_weights (tim.py:115-134, :218-238): the class means of the support set; Adam state zero
     if (D == K)
-        hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, dense_rows(x_s), y_s, S, K, 0, sup, cnt);
+        hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, x_s, y_s, S, K, 0, sup, cnt);
     else
-        launch_vis_support_stats(st, x_s, y_s, T, S, K, D, sup, cnt);
+        launch_vis_support_stats(st, RowSrc{x_s.base, x_s.idx, nullptr}, y_s, T, S, K, D, sup, cnt);
     hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
                        (size_t)TK * D, D, weights);
     TCLIP_HIP(hipMemsetAsync(M, 0, (size_t)TK * D * 4, st));
     TCLIP_HIP(hipMemsetAsync(V, 0, (size_t)TK * D * 4, st));
-    hipLaunchKernelGGL(k_tim_row_sqnorm, dim3((TR + 3) / 4), dim3(256), 0, st, X, TR, xn);
+    hipLaunchKernelGGL(k_tim_row_sqnorm<kIdx>, dim3((TR + 3) / 4), dim3(256), 0, st, X, TR, xn);
     hipLaunchKernelGGL(k_tim_w_sqnorm, dim3((TK + 3) / 4), dim3(256), 0, st, (const float*)weights, TK, D, wn);
     for (int it = 0; it < p.iters; it++) {
         const bool last = it + 1 == p.iters;
-        hipLaunchKernelGGL((k_tim_gemm_mfma<false, kTimTile>), dim3(tiles_k, tiles_r, T), dim3(256), 0, st, X, K, (const float*)weights,
+        hipLaunchKernelGGL((k_tim_gemm_mfma<false, kTimTile, kIdx>), dim3(tiles_k, tiles_r, T), dim3(256), 0, st, X, K, (const float*)weights,
                            (const float*)wn, (const float*)xn, temp, P, (float*)nullptr);
         hipLaunchKernelGGL(k_tim_softmax, dim3((TR + 3) / 4), dim3(256), 0, st, P, TR, S, Q, K, last ? logits_q : (float*)nullptr,
                            preds);
         hipLaunchKernelGGL(k_tim_marginal, dim3((K + 127) / 128, T), dim3(128), 0, st, (const float*)P, S, Q, K, marg);
         hipLaunchKernelGGL(k_tim_grad, dim3((TR + 3) / 4), dim3(256), 0, st, P, y_s, (const float*)marg, TR, S, Q, K, loss);
-        hipLaunchKernelGGL((k_tim_gemm_mfma<true, kTimTile>), dim3(tiles_d, tiles_k, T), dim3(256), 0, st, X, K, (const float*)P,
+        hipLaunchKernelGGL((k_tim_gemm_mfma<true, kTimTile, kIdx>), dim3(tiles_d, tiles_k, T), dim3(256), 0, st, X, K, (const float*)P,
                            (const float*)nullptr, (const float*)nullptr, 0.0f, dW, cs);
         // Adam's step scalars, in double as torch computes them (torch/optim/adam.py, _single_tensor_adam)
         const double step = it + 1, bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
@@ -435,6 +488,18 @@ static int tim_loop(const tclip_problem& p, int D, double lr, float temp, const 
     return TCLIP_OK;
 }
 
+// x_q, x_s: dense tensors, or (idx != nullptr) the feature tables with the task-batch loop's index tensors and, at D = K, its
+// column permutation: both row sets are then read in place in every step, with the dense workspace and the dense launches.
+static int tim_loop(const tclip_problem& p, int D, double lr, float temp, const TimLoss& loss, bool per_task, const RowSrc& x_q,
+                    const RowSrc& x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                    char* ws, hipStream_t st) {
+    if (x_s.idx != nullptr)
+        return tim_loop_on(p, TimRows<true>{x_s.base, x_q.base, x_s.idx, x_q.idx, x_s.cols, p.n_support, p.n_query, D}, x_s, lr, temp,
+                           loss, per_task, y_s, weights, logits_q, preds, criterions, ws, st);
+    return tim_loop_on(p, TimRows<false>{x_s.base, x_q.base, p.n_support, p.n_query, D}, x_s, lr, temp, loss, per_task, y_s, weights,
+                       logits_q, preds, criterions, ws, st);
+}
+
 // what tclip_tim_gd_run and its workspace query check of the problem
 static int check_tim_gd(const tclip_problem* p, int32_t dim) {
     if (int rc = check_problem(p)) return rc;
@@ -446,13 +511,14 @@ static int check_tim_gd(const tclip_problem* p, int32_t dim) {
     return TCLIP_OK;
 }
 
-// ALPHA_TIM on rows of D elements: the checks and the loop of both entries (ws_query: the workspace query to name)
-static int alpha_tim_run(const tclip_problem* pp, int D, const tclip_tim_params* prm, const float* x_q, const float* x_s,
+// ALPHA_TIM on rows of D elements: the checks and the loop of all four entries (ws_query: the workspace query to name); x_q and
+// x_s dense, or the feature tables (the members of a tclip_task_source, checked by alpha_tim_run_tasks)
+static int alpha_tim_run(const tclip_problem* pp, int D, const tclip_tim_params* prm, const RowSrc& x_q, const RowSrc& x_s,
                          const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions, void* workspace,
                          size_t workspace_bytes, void* stream, const char* ws_query) {
     const tclip_problem p = *pp;
     if (p.iters < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM needs iters >= 1 (the accuracy is read from the last iteration's logits)");
-    if (!prm || !x_q || !x_s || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
+    if (!prm || !x_q.base || !x_s.base || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
         return fail(TCLIP_ERR_ARG, "null pointer argument");
     if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM is a few-shot method: n_support must be positive");
     for (int i = 0; i < 3; i++)
@@ -465,6 +531,21 @@ static int alpha_tim_run(const tclip_problem* pp, int D, const tclip_tim_params*
                        prm->entropies[0], prm->entropies[1], prm->entropies[2]};
     return tim_loop(p, D, prm->lr, prm->temp, loss, false, x_q, x_s, y_s, weights, logits_q, preds, criterions,
                     (char*)workspace, (hipStream_t)stream);
+}
+
+// a tclip_task_source whose members other than cols are all there
+static bool task_source_complete(const tclip_task_source* src) {
+    return src && src->table_q && src->q_idx && src->table_s && src->s_idx;
+}
+
+// The ALPHA_TIM entries fed from the feature tables: `src` in place of x_q / x_s, then alpha_tim_run
+static int alpha_tim_run_tasks(const tclip_problem* pp, int D, bool visual, const tclip_tim_params* prm, const tclip_task_source* src,
+                               const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                               void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (!task_source_complete(src)) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "ALPHA_TIM on visual features permutes no columns: cols must be NULL");
+    return alpha_tim_run(pp, D, prm, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s,
+                         weights, logits_q, preds, criterions, workspace, workspace_bytes, stream, ws_query);
 }
 
 // what tclip_alpha_tim_visual_run and its workspace query check of the problem
@@ -489,7 +570,7 @@ int tclip_alpha_tim_run(const tclip_problem* pp, const tclip_tim_params* prm, co
                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_problem(pp)) return rc;
-    return alpha_tim_run(pp, pp->n_class, prm, x_q, x_s, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
+    return alpha_tim_run(pp, pp->n_class, prm, dense_rows(x_q), dense_rows(x_s), y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
                          "tclip_alpha_tim_workspace_bytes");
 }
 
@@ -502,7 +583,7 @@ int tclip_alpha_tim_visual_run(const tclip_problem* pp, int32_t dim, const tclip
                                const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                                void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
-    return alpha_tim_run(pp, dim, prm, x_q, x_s, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
+    return alpha_tim_run(pp, dim, prm, dense_rows(x_q), dense_rows(x_s), y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
                          "tclip_alpha_tim_visual_workspace_bytes");
 }
 
@@ -521,8 +602,49 @@ int tclip_tim_gd_run(const tclip_problem* pp, int32_t dim, double lr, float temp
     if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, dim).total, "tclip_tim_gd_workspace_bytes")) return rc;
     // tim.py:166-175: all three entropies Shannon, the marginal one with 1e-12 inside its logarithm
     const TimLoss loss{loss_weights[0], loss_weights[1], loss_weights[2], 0.0f, TCLIP_TIM_SHANNON, kTimMarginalGd, TCLIP_TIM_SHANNON};
-    return tim_loop(p, dim, lr, temp, loss, true, x_q, x_s, y_s, weights, logits_q, preds, criterions, (char*)workspace,
-                    (hipStream_t)stream);
+    return tim_loop(p, dim, lr, temp, loss, true, dense_rows(x_q), dense_rows(x_s), y_s, weights, logits_q, preds, criterions,
+                    (char*)workspace, (hipStream_t)stream);
+}
+
+// ---- ALPHA_TIM and TIM_GD fed from the feature tables: k_tim_row_sqnorm, the two GEMMs of every Adam step and the class sums of
+// init_weights read the task rows in place, neither x_s nor x_q is built; workspace and checks are the dense entries'
+size_t tclip_alpha_tim_tasks_workspace_bytes(const tclip_problem* p) { return tclip_alpha_tim_workspace_bytes(p); }
+
+int tclip_alpha_tim_run_tasks(const tclip_problem* pp, const tclip_tim_params* prm, const tclip_task_source* src, const int64_t* y_s,
+                              float* weights, float* logits_q, int32_t* preds, float* criterions, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    return alpha_tim_run_tasks(pp, pp->n_class, false, prm, src, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes,
+                               stream, "tclip_alpha_tim_tasks_workspace_bytes");
+}
+
+size_t tclip_alpha_tim_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return tclip_alpha_tim_visual_workspace_bytes(p, dim);
+}
+
+int tclip_alpha_tim_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_tim_params* prm, const tclip_task_source* src,
+                                     const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
+    return alpha_tim_run_tasks(pp, dim, true, prm, src, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
+                               "tclip_alpha_tim_visual_tasks_workspace_bytes");
+}
+
+size_t tclip_tim_gd_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) { return tclip_tim_gd_workspace_bytes(p, dim); }
+
+int tclip_tim_gd_run_tasks(const tclip_problem* pp, int32_t dim, double lr, float temp, const float loss_weights[3],
+                           const tclip_task_source* src, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds,
+                           float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_tim_gd(pp, dim)) return rc;
+    const tclip_problem p = *pp;
+    if (!loss_weights || !task_source_complete(src) || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (src->cols && dim != p.n_class)
+        return fail(TCLIP_ERR_ARG, "TIM_GD permutes columns on probability features only: cols must be NULL unless dim == n_class");
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, dim).total, "tclip_tim_gd_tasks_workspace_bytes")) return rc;
+    const TimLoss loss{loss_weights[0], loss_weights[1], loss_weights[2], 0.0f, TCLIP_TIM_SHANNON, kTimMarginalGd, TCLIP_TIM_SHANNON};
+    return tim_loop(p, dim, lr, temp, loss, true, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols},
+                    y_s, weights, logits_q, preds, criterions, (char*)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

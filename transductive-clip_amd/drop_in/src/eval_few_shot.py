@@ -223,6 +223,10 @@ class Evaluator_few_shot:
             in_place = m.reads_rows_in_place(a.use_softmax_feature)
             if not in_place and getattr(a, 'in_place_support', False) and hasattr(m, 'can_read_rows_in_place'):
                 in_place = m.can_read_rows_in_place(a.use_softmax_feature)
+            # in_place_loop (absent or False: as above): TIM-GD and ALPHA_TIM, which read their task rows in both GEMMs of EVERY
+            # Adam step, read them from the tables too - a switch of its own, since they pay the indirection per step
+            if not in_place and getattr(a, 'in_place_loop', False) and hasattr(m, 'can_read_rows_in_place_per_step'):
+                in_place = m.can_read_rows_in_place_per_step(a.use_softmax_feature)
             if rel is not None:
                 cols, y_s, y_q = rel
             if rel is not None and in_place:

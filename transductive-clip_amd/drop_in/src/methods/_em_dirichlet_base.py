@@ -218,6 +218,15 @@ class FewShotMixin:
     def can_read_rows_in_place(cls, use_softmax_feature):
         return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_SUPPORT
 
+    # the feature kinds on which run_tables reads the task rows in place in EVERY step of the method's loop (TIM-GD, ALPHA_TIM:
+    # both GEMMs of an Adam step), taken only when the evaluator is asked to (args.in_place_loop): a switch of its own,
+    # because these classes pay the indirection per step, not once
+    IN_PLACE_LOOP = ()
+
+    @classmethod
+    def can_read_rows_in_place_per_step(cls, use_softmax_feature):
+        return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_LOOP
+
     def run_task(self, task_dic, shot=10):
         y_s, y_q = task_dic['y_s'], task_dic['y_q']
         support, query = task_dic['x_s'], task_dic['x_q']

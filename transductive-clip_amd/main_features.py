@@ -33,6 +33,9 @@ and LaplacianShot at ImageNet scale; `materialise_tasks True` takes the referenc
 relabelling on the host) - same results either way.  `in_place_support True` (not a default: absent unless given) lets BDCSPN
 (both feature kinds) and LaplacianShot (softmax features) read their task rows from the tables too - same results, without
 the (tasks, support, width) and (tasks, query, width) tensors and, for BDCSPN, with a smaller workspace.
+`in_place_loop True` (not a default: absent unless given) does the same for TIM-GD (both feature kinds) and ALPHA_TIM (softmax
+features), which read their task rows in every Adam step, not once: same results without the two tensors; what the indirection
+costs in time is measured in DESIGN.md 8j.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse

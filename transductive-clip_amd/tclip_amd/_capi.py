@@ -59,6 +59,16 @@ _SIGNATURES = {
     "tclip_tim_gd_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
     "tclip_tim_gd_run": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_double, ctypes.c_float,
                                         ctypes.POINTER(ctypes.c_float)] + [_P] * 8 + [ctypes.c_size_t, _P]),
+    "tclip_alpha_tim_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
+    "tclip_alpha_tim_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TimParams), ctypes.POINTER(TaskSource)] + [_P] * 6
+                                  + [ctypes.c_size_t, _P]),
+    "tclip_alpha_tim_visual_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_alpha_tim_visual_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TimParams),
+                                                        ctypes.POINTER(TaskSource)] + [_P] * 6 + [ctypes.c_size_t, _P]),
+    "tclip_tim_gd_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_tim_gd_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_double, ctypes.c_float,
+                                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(TaskSource)] + [_P] * 6
+                               + [ctypes.c_size_t, _P]),
     "tclip_laplacian_shot_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_laplacian_shot_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
                                                 _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),

@@ -417,6 +417,73 @@ def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.
     return weights, logits_q, preds, crit
 
 
+def _run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, temp, lr, alpha_value, loss_weights, entropies,
+                         n_batches, visual):
+    """ALPHA_TIM from the feature tables on rows of D elements (tclip_alpha_tim_run_tasks / tclip_alpha_tim_visual_run_tasks)"""
+    _check_entropies(entropies)
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "ALPHA_TIM")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    if T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+    prm = _capi.TimParams(float(lr), float(temp), float(alpha_value), (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
+                          (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
+    stem, dim = ("tclip_alpha_tim_visual", (ctypes.c_int32(D),)) if visual else ("tclip_alpha_tim", ())
+    c = _Call(dev, _capi.Problem(n_batches, T // n_batches, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
+    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(n_batches, iters)
+    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(prm), ctypes.byref(src), _ptr(y_s), _ptr(weights),
+                                                     _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
+    return weights, logits_q, preds, crit
+
+
+def run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, temp, lr, alpha_value,
+                        loss_weights=(1.0, 1.0, 1.0), entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
+    """ALPHA_TIM fed from the task-batch loop's feature tables (tclip_alpha_tim_run_tasks): table_q, table_s (rows,K) f32 cuda,
+    q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column permutation
+    of Tasks_Generator_few_shot.get_task or None -> what run_alpha_tim returns on the materialised tensors, bit for bit; neither
+    (T,S,K) nor (T,Q,K) is built: the table rows are read in place in every Adam step.  Not synchronised."""
+    return _run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], iters, temp, lr, alpha_value,
+                                loss_weights, entropies, n_batches, visual=False)
+
+
+def run_alpha_tim_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, temp, lr, alpha_value,
+                               loss_weights=(1.0, 1.0, 1.0), entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
+    """ALPHA_TIM on visual features fed from the feature tables (tclip_alpha_tim_visual_run_tasks): tables (rows,D) with any D
+    in 1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> the bits of run_alpha_tim_visual
+    on the materialised tensors.  Not synchronised."""
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    return _run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, iters, temp, lr, alpha_value, loss_weights,
+                                entropies, n_batches, visual=True)
+
+
+def run_tim_gd_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0),
+                     n_batches=1):
+    """TIM_GD on either feature kind fed from the feature tables (tclip_tim_gd_run_tasks): tables (rows,D) f32 cuda with any D in
+    1..1024, q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) int64 labels in 0..n_class-1 (re-indexed on probability
+    features), cols (T,D) the per-task column permutation on probability features (D = n_class) or None -> what run_tim_gd
+    returns on the materialised tensors, bit for bit; the table rows are read in place in every Adam step.  Not synchronised."""
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    if cols is not None and table_q.dim() == 2 and table_q.shape[1] != n_class:
+        raise ValueError("TIM_GD permutes columns on probability features only: cols needs tables of n_class columns")
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, n_class, "TIM_GD")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    if T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+    dim = ctypes.c_int32(D)
+    lw = (ctypes.c_float * 3)(*[float(w) for w in loss_weights])
+    c = _Call(dev, _capi.Problem(n_batches, T // n_batches, Q, n_class, S, iters, 1, 0, 0), "tclip_tim_gd_tasks_workspace_bytes", dim)
+    weights, logits_q, preds, crit = c.empty(T, n_class, D), c.empty(T, Q, n_class), c.empty(T, Q, dtype=torch.int32), c.empty(iters, T)
+    c.launch("tclip_tim_gd_run_tasks", lambda ws, n, st: (dim, ctypes.c_double(float(lr)), ctypes.c_float(float(temp)), lw,
+                                                          ctypes.byref(src), _ptr(y_s), _ptr(weights), _ptr(logits_q), _ptr(preds),
+                                                          _ptr(crit), ws, n, st))
+    return weights, logits_q, preds, crit
+
+
 def _run_laplacian_shot(x_q, x_s, y_s, K, iters, knn, lmd, norm_type, visual):
     """LAPLACIAN_SHOT on rows of D elements: D = K and tclip_laplacian_shot_run for probability features,
     tclip_laplacian_shot_visual_run with D as its first argument for visual ones."""
