@@ -6,48 +6,58 @@ import os
 import numpy as np
 import torch
 
-from helpers import visual_fs
+from helpers import tim_gd, visual_fs
 
 VISUAL = ["fs_vis_alpha_tim_D512_K10_S4_N3", "fs_vis_alpha_tim_D1024_K37_S2_N2", "fs_vis_alpha_tim_D768_K100_S1_N1"]
+
+
+def loss(weights, support, query, hot, *, temp, alpha_value, loss_weights, entropies):
+    """ALPHA_TIM's objective (:262-305), summed over the tasks -> (loss, logits_q)"""
+    lw, a = list(loss_weights), alpha_value
+    logits_s, logits_q = tim_gd.get_logits(weights, support, temp), tim_gd.get_logits(weights, query, temp)   # :203-217
+    q_probs = logits_q.softmax(2)
+    if entropies[0] == "Shannon":                                                      # :270-280
+        ce = -(hot * torch.log(logits_s.softmax(2) + 1e-12)).sum(2).mean(1).sum(0)
+    else:
+        ce = torch.pow(hot, a) * torch.pow(logits_s.softmax(2) + 1e-12, 1 - a)
+        ce = ((1 - ce.sum(2)) / (a - 1)).mean(1).sum(0)
+    if entropies[1] == "Shannon":                                                      # :282-290
+        q_ent = -(q_probs.mean(1) * torch.log(q_probs.mean(1))).sum(1).sum(0)
+    else:
+        q_ent = ((1 - (torch.pow(q_probs.mean(1), a)).sum(1)) / (a - 1)).sum(0)
+    if entropies[2] == "Shannon":                                                      # :292-300
+        q_cond_ent = -(q_probs * torch.log(q_probs + 1e-12)).sum(2).mean(1).sum(0)
+    else:
+        q_cond_ent = ((1 - (torch.pow(q_probs + 1e-12, a)).sum(2)) / (a - 1)).mean(1).sum(0)
+    return lw[0] * ce - (lw[1] * q_ent - lw[2] * q_cond_ent), logits_q
+
+
+def loss_gradient(x_q, x_s, y_s, *, n_class, temp, alpha_value, loss_weights=(1.0, 1.0, 1.0),
+                  entropies=("Shannon", "Alpha", "Alpha"), dtype=torch.float64):
+    """-> (w0 (N,K,D): the class means the loop starts from, d loss / d weights there, logits_q of that forward pass), one
+    backward pass in `dtype`"""
+    support, query, hot, w0 = tim_gd.setup(x_q, x_s, y_s, n_class, dtype)             # init_weights (:219-238)
+    w0.requires_grad_()
+    value, logits_q = loss(w0, support, query, hot, temp=temp, alpha_value=alpha_value, loss_weights=loss_weights,
+                           entropies=entropies)
+    value.backward()
+    return w0.detach(), w0.grad.detach(), logits_q.detach()
 
 
 def run_alpha_tim(x_q, x_s, y_s, *, n_class, iters, temp, lr, alpha_value, loss_weights=(1.0, 1.0, 1.0),
                   entropies=("Shannon", "Alpha", "Alpha"), dtype=torch.float32):
     """x_q (N,Q,D), x_s (N,S,D), y_s (N,S) or (N,S,1), all tasks one batch -> dict(weights (N,K,D), logits_q (N,Q,K) of the last
     iteration's forward pass, criterions (iters,): mean over tasks and classes of ||w_old - w|| per step, argmax (N,Q))."""
-    support, query = x_s.clone().to(dtype), x_q.clone().to(dtype)
-    n_task = query.shape[0]
-    y_s = y_s.long().view(n_task, -1)
-    hot = torch.zeros(y_s.shape + (n_class,), dtype=dtype).scatter_(-1, y_s.unsqueeze(-1), 1.0)
-    counts = hot.sum(1).view(n_task, -1, 1)
-    weights = (hot.transpose(1, 2).matmul(support) / counts).requires_grad_()          # init_weights (:219-238)
-
-    def get_logits(samples):                                                           # :203-217
-        return temp * (samples.matmul(weights.transpose(1, 2)) - 1 / 2 * (weights ** 2).sum(2).view(n_task, 1, -1)
-                       - 1 / 2 * (samples ** 2).sum(2).view(n_task, -1, 1))
-
+    support, query, hot, weights = tim_gd.setup(x_q, x_s, y_s, n_class, dtype)        # init_weights (:219-238)
+    weights.requires_grad_()
     optimizer = torch.optim.Adam([weights], lr=lr)
-    lw, a, criterions, logits_q = list(loss_weights), alpha_value, [], None
+    criterions, logits_q = [], None
     for _ in range(iters):
         weights_old = weights.detach().clone()
-        logits_s, logits_q = get_logits(support), get_logits(query)
-        q_probs = logits_q.softmax(2)
-        if entropies[0] == "Shannon":                                                  # :270-280
-            ce = -(hot * torch.log(logits_s.softmax(2) + 1e-12)).sum(2).mean(1).sum(0)
-        else:
-            ce = torch.pow(hot, a) * torch.pow(logits_s.softmax(2) + 1e-12, 1 - a)
-            ce = ((1 - ce.sum(2)) / (a - 1)).mean(1).sum(0)
-        if entropies[1] == "Shannon":                                                  # :282-290
-            q_ent = -(q_probs.mean(1) * torch.log(q_probs.mean(1))).sum(1).sum(0)
-        else:
-            q_ent = ((1 - (torch.pow(q_probs.mean(1), a)).sum(1)) / (a - 1)).sum(0)
-        if entropies[2] == "Shannon":                                                  # :292-300
-            q_cond_ent = -(q_probs * torch.log(q_probs + 1e-12)).sum(2).mean(1).sum(0)
-        else:
-            q_cond_ent = ((1 - (torch.pow(q_probs + 1e-12, a)).sum(2)) / (a - 1)).mean(1).sum(0)
-        loss = lw[0] * ce - (lw[1] * q_ent - lw[2] * q_cond_ent)
+        value, logits_q = loss(weights, support, query, hot, temp=temp, alpha_value=alpha_value, loss_weights=loss_weights,
+                               entropies=entropies)
         optimizer.zero_grad()
-        loss.backward()
+        value.backward()
         optimizer.step()
         criterions.append((weights_old - weights.detach()).norm(dim=-1).mean())        # one value per step (:313-314)
     logits_q = logits_q.detach()

@@ -4,33 +4,56 @@ class count; nothing is normalised."""
 import torch
 
 
-def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0), dtype=torch.float32):
-    """x_q (N,Q,D), x_s (N,S,D), y_s (N,S) or (N,S,1) -> dict(weights (N,K,D), logits_q (N,Q,K) of the last iteration's forward
-    pass, criterions (iters, N): mean_class ||w_old - w|| per step and task, argmax (N,Q)).  dtype=torch.float64 runs the
-    inputs, the weights and the whole loop in double."""
+def setup(x_q, x_s, y_s, n_class, dtype):
+    """-> (support, query, hot (N,S,K), the class means of the support rows: init_weights, :115-131), all of `dtype`"""
     support, query = x_s.clone().to(dtype), x_q.clone().to(dtype)
     n_task = query.shape[0]
     y_s = y_s.long().view(n_task, -1)
     hot = torch.zeros(y_s.shape + (n_class,), dtype=dtype).scatter_(-1, y_s.unsqueeze(-1), 1.0)
     counts = hot.sum(1).view(n_task, -1, 1)
-    weights = (hot.transpose(1, 2).matmul(support) / counts).requires_grad_()          # init_weights (:115-131)
+    return support, query, hot, hot.transpose(1, 2).matmul(support) / counts
 
-    def get_logits(samples):                                                           # :99-113
-        return temp * (samples.matmul(weights.transpose(1, 2)) - 1 / 2 * (weights ** 2).sum(2).view(n_task, 1, -1)
-                       - 1 / 2 * (samples ** 2).sum(2).view(n_task, -1, 1))
 
+def get_logits(weights, samples, temp):                                                # :99-113
+    n_task = samples.shape[0]
+    return temp * (samples.matmul(weights.transpose(1, 2)) - 1 / 2 * (weights ** 2).sum(2).view(n_task, 1, -1)
+                   - 1 / 2 * (samples ** 2).sum(2).view(n_task, -1, 1))
+
+
+def loss(weights, support, query, hot, *, temp, loss_weights):
+    """TIM_GD's objective (:160-175), summed over the tasks -> (loss, logits_q)"""
+    lw = list(loss_weights)
+    logits_s, logits_q = get_logits(weights, support, temp), get_logits(weights, query, temp)
+    ce = -(hot * torch.log(logits_s.softmax(2) + 1e-12)).sum(2).mean(1).sum(0)
+    q_probs = logits_q.softmax(2)
+    q_cond_ent = -(q_probs * torch.log(q_probs + 1e-12)).sum(2).mean(1).sum(0)
+    q_ent = -(q_probs.mean(1) * torch.log(q_probs.mean(1) + 1e-12)).sum(1).sum(0)
+    return lw[0] * ce - (lw[1] * q_ent - lw[2] * q_cond_ent), logits_q
+
+
+def loss_gradient(x_q, x_s, y_s, *, n_class, temp, loss_weights=(1.0, 0.3, 1.0), dtype=torch.float64):
+    """-> (w0 (N,K,D): the class means the loop starts from, d loss / d weights there, logits_q of that forward pass), one
+    backward pass in `dtype`"""
+    support, query, hot, w0 = setup(x_q, x_s, y_s, n_class, dtype)
+    w0.requires_grad_()
+    value, logits_q = loss(w0, support, query, hot, temp=temp, loss_weights=loss_weights)
+    value.backward()
+    return w0.detach(), w0.grad.detach(), logits_q.detach()
+
+
+def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0), dtype=torch.float32):
+    """x_q (N,Q,D), x_s (N,S,D), y_s (N,S) or (N,S,1) -> dict(weights (N,K,D), logits_q (N,Q,K) of the last iteration's forward
+    pass, criterions (iters, N): mean_class ||w_old - w|| per step and task, argmax (N,Q)).  dtype=torch.float64 runs the
+    inputs, the weights and the whole loop in double."""
+    support, query, hot, weights = setup(x_q, x_s, y_s, n_class, dtype)
+    weights.requires_grad_()
     optimizer = torch.optim.Adam([weights], lr=lr)
-    lw, criterions, logits_q = list(loss_weights), [], None
+    criterions, logits_q = [], None
     for _ in range(iters):
         weights_old = weights.detach().clone()
-        logits_s, logits_q = get_logits(support), get_logits(query)
-        ce = -(hot * torch.log(logits_s.softmax(2) + 1e-12)).sum(2).mean(1).sum(0)
-        q_probs = logits_q.softmax(2)
-        q_cond_ent = -(q_probs * torch.log(q_probs + 1e-12)).sum(2).mean(1).sum(0)
-        q_ent = -(q_probs.mean(1) * torch.log(q_probs.mean(1) + 1e-12)).sum(1).sum(0)
-        loss = lw[0] * ce - (lw[1] * q_ent - lw[2] * q_cond_ent)
+        value, logits_q = loss(weights, support, query, hot, temp=temp, loss_weights=loss_weights)
         optimizer.zero_grad()
-        loss.backward()
+        value.backward()
         optimizer.step()
         criterions.append((weights_old - weights.detach()).norm(dim=-1).mean(-1))      # one value per task (:181)
     logits_q = logits_q.detach()

@@ -98,8 +98,8 @@ __global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int D, f
 
 // L[t][i][k] = T ((x_i . w_k - |w_k|^2 / 2) - |x_i|^2 / 2)   (tim.py:212-216)   and   dW[t][k][d] = sum_i G[i][k] x_i[d]:
 // The two GEMMs of a step on the matrix cores.  v_mfma_f32_32x32x2_f32 takes ONE fp32 of A and ONE of B per lane (lane l:
-// A[row l & 31][k = l >> 5], B[k = l >> 5][column l & 31]) and is exact fp32 multiply-add, accumulated over k in order - the
-// deviations from the reference's fixtures are the FMA tiles' to the last digit.  Its peak is the vector FMA peak (157 TFLOP/s),
+// A[row l & 31][k = l >> 5], B[k = l >> 5][column l & 31]) and is exact fp32 multiply-add, accumulated over k in order within a
+// block of kTimSumSlices slices.  Its peak is the vector FMA peak (157 TFLOP/s),
 // so the gain is what the freed vector pipe is worth to the staging code: measured against round 2's 4 x 4-per-thread FMA tiles
 // (64 x 64, 1000 Adam steps): K = 10 +6 %, K = 100 +9 %, K = 397 36.5 against 35.1 TFLOP/s, K = 1000 (S = 4000, 4 tasks) 59.0 against 49.2
 // (52.7 before interior tiles took their slices with 128-bit loads).
@@ -111,11 +111,20 @@ __global__ void k_tim_w_sqnorm(const float* __restrict__ W, int n_rows, int D, f
 // depth of R; W and dW rows have D elements, G and the logits' rows K.
 // Epilogue: the logits' scaling and norms, or (dW) the column sums of G by the blocks of the first column tile.
 // TILE = 128 (2 x 2 MFMA tiles per wavefront) loses to partial tiles and to fewer blocks: K = 397 25.4, K = 1000 48.9 TFLOP/s.
+// The contraction is summed in two levels: the MFMAs accumulate kTimSumSlices slices (64 products) from zero, then that block sum
+// is added to the running total.  One accumulator over a depth of 1000 rounds every addition at the size of the whole sum: on
+// probability features at K ~ 1000 (all products of one sign in the logits, R = S + Q > 1000 rows in dW) the gradient was 6 to
+// 12 times, the logits up to 25 times as far from float64 as the reference's fp32 run (tests/test_gpu_tim_gradient.py); with
+// block sums of 64 both are as close as the reference (DESIGN.md 8d).  The column sums of G are taken the same way.
+// The throughput figures in this comment were measured with the single accumulator; the two-level sum costs 1.4 to 3.5 % of a
+// run of 1000 Adam steps (K = 397, D = 1024, 20 tasks: 59.5 against 61.3 TFLOP/s; K = 1000, D = 1024, 4 tasks: 51.5 against 52.2).
+constexpr int kTimSumSlices = 4;
 constexpr int kTimMfmaDepth = 16;    // measured at 64 x 64 tiles: depth 16 52.7, 32 45.9, 64 25.2 TFLOP/s (K = 1000, S = 4000, 4 tasks)
 typedef float tim_f16x __attribute__((ext_vector_type(16)));
 
-// TILE = 64: one 32 x 32 MFMA tile per wavefront (more, smaller blocks: few tasks, class counts just above a multiple of 64);
-// TILE = 128: 2 x 2 MFMA tiles per wavefront (4 MFMAs per 4 LDS reads)
+// TILE = 64, the one instantiation launched: one 32 x 32 MFMA tile per wavefront (more, smaller blocks: few tasks, class counts just
+// above a multiple of 64), 16 + 16 accumulator registers per lane for the two levels of the sum.  TILE = 128 (2 x 2 MFMA tiles per
+// wavefront, 4 MFMAs per 4 LDS reads) would hold 64 + 64.
 // kIdx: the rows of X are table rows read in place (TimRows<true>).  A thread stages the same (row, depth) / (depth, column)
 // positions of a slice into the same LDS words, so the MFMAs accumulate the dense kernel's values in its order.  With cols the
 // elements are fetched one by one inside the table row just addressed (at most 4 KB); without, interior tiles keep the 128-bit
@@ -133,15 +142,15 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
     const int M = kTN ? K : R, N = kTN ? F : K, D = kTN ? R : F;     // C is M x N, the contraction runs over D
     const int m0 = blockIdx.y * TILE, n0 = blockIdx.x * TILE;
     const int id = threadIdx.x, wave = id >> 6, lane = id & 63, wm = wave >> 1, wnn = wave & 1, half = lane >> 5, li = lane & 31;
-    tim_f16x acc[MI][MI];
+    tim_f16x acc[MI][MI], total[MI][MI];                             // the current block of kTimSumSlices slices; the blocks before it
 #pragma unroll
     for (int i = 0; i < MI; i++)
 #pragma unroll
         for (int j = 0; j < MI; j++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+            for (int r = 0; r < 16; r++) acc[i][j][r] = total[i][j][r] = 0.0f;
     const bool sums = kTN && blockIdx.x == 0 && id < TILE;
-    float colsum = 0.0f;
+    float colsum = 0.0f, colsum_total = 0.0f;
     // this thread's part of a depth-16 slice of both operands, global memory -> registers.  The NEXT slice is requested
     // before the current one's MFMAs are issued, so its latency hides behind them.
     float a[PER], b[PER];
@@ -242,6 +251,19 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
 #pragma unroll
                 for (int j = 0; j < MI; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
         }
+        if ((d0 / kTimMfmaDepth + 1) % kTimSumSlices == 0 || d0 + kTimMfmaDepth >= D) {      // block-uniform: a block sum is complete
+#pragma unroll
+            for (int i = 0; i < MI; i++)
+#pragma unroll
+                for (int j = 0; j < MI; j++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        total[i][j][r] += acc[i][j][r];
+                        acc[i][j][r] = 0.0f;
+                    }
+            colsum_total += colsum;
+            colsum = 0.0f;
+        }
     }
     // C/D map of the 32 x 32 tile: register r of lane l holds row 8 (r >> 2) + 4 (l >> 5) + (r & 3), column l & 31
 #pragma unroll
@@ -255,12 +277,12 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
             for (int r = 0; r < 16; r++) {
                 const int m = m0 + wm * (TILE / 2) + i * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
                 if (m >= M) continue;
-                const float v = acc[i][j][r];
+                const float v = total[i][j][r];
                 if (kTN) C[((size_t)t * K + m) * F + n] = v;
                 else C[((size_t)t * R + m) * K + n] = temp * ((v - 0.5f * wnv) - 0.5f * xn[(size_t)t * R + m]);
             }
         }
-    if (sums && m0 + id < M) cs[(size_t)t * K + m0 + id] = colsum;
+    if (sums && m0 + id < M) cs[(size_t)t * K + m0 + id] = colsum_total;
 }
 
 // Row softmax in place (one wavefront per row); on request the raw query logits and their first-maximum index
@@ -306,13 +328,16 @@ __global__ void k_tim_softmax(float* __restrict__ P, int n_rows_total, int S, in
 }
 
 // marginal[t][k] = mean over the query rows of p[q][k]                                              (q_probs.mean(1))
+// Summed in double: the Alpha marginal term is m^(alpha-1), six times m's relative error at alpha = 7, and a sequential fp32 sum
+// over 128 rows put the gradient 3 to 8 times as far from float64 as the reference's fp32 run, whose mean is a cascade sum
+// (tests/test_gpu_tim_gradient.py).  The mean is rounded to fp32 once.
 __global__ void k_tim_marginal(const float* __restrict__ P, int S, int Q, int K, float* __restrict__ marg) {
     const int t = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
     const float* p = P + ((size_t)t * (S + Q) + S) * K + k;
-    float s = 0.0f;
-    for (int q = 0; q < Q; q++) s += p[(size_t)q * K];
-    marg[(size_t)t * K + k] = s / (float)Q;
+    double s = 0.0;
+    for (int q = 0; q < Q; q++) s += (double)p[(size_t)q * K];
+    marg[(size_t)t * K + k] = (float)(s / (double)Q);
 }
 
 // P -> G = dLoss/dlogits, row by row (tim.py:276-305 differentiated by hand; 1e-12 where the reference adds it).
