@@ -460,7 +460,8 @@ def run_laplacian_shot(x_q, x_s, y_s, y_q, *, n_class, iters, knn, lmd, norm_typ
     """LAPLACIAN_SHOT, the reference's numpy / scipy.sparse / sklearn op sequence
     (src/methods/few_shot/laplacian_shot.py:66-249) with `dtype=float` where the reference writes the removed alias
     `np.float` (:100).  Returns dict(unary (N,Q,K) f32, neighbours (N,Q,knn-1) sorted, preds (N,Q), acc (N,iters),
-    ent_energy (N,iters) f64)."""
+    ent_energy (N,iters) f64, preds_iter (N,iters,Q): the argmax of every update, repeated after the freeze as acc is,
+    frozen_at (N,): the update at which the break of :165 was taken, -1 if it was not)."""
     import numpy as np
     from numpy import linalg as LA
     from scipy import sparse
@@ -484,7 +485,7 @@ def run_laplacian_shot(x_q, x_s, y_s, y_q, *, n_class, iters, knn, lmd, norm_typ
         y_out = np.exp(y_in)
         return y_out / (np.sum(y_out, axis=1)[:, None])
 
-    out = {"unary": [], "neighbours": [], "preds": [], "acc": [], "ent_energy": []}
+    out = {"unary": [], "neighbours": [], "preds": [], "acc": [], "ent_energy": [], "preds_iter": [], "frozen_at": []}
     for i in range(n_task):
         distance = LA.norm(support[i][:, None, :] - query[i], 2, axis=-1)
         unary = distance.transpose() ** 2
@@ -493,6 +494,7 @@ def run_laplacian_shot(x_q, x_s, y_s, y_q, *, n_class, iters, knn, lmd, norm_typ
         row, col = np.repeat(range(n), knn - 1), knnind[:, 1:].flatten()
         kernel = sparse.csc_matrix((np.ones(n * (knn - 1)), (row, col)), shape=(n, n), dtype=float)
         old_e, y, energies, accs, pred = float("inf"), normalize(-unary), [], [], None
+        preds_iter, frozen_at = [], -1
         for it in range(iters):
             y = normalize(-unary - (-lmd * kernel.dot(y)))
             pairwise = kernel.dot(y)
@@ -500,9 +502,12 @@ def run_laplacian_shot(x_q, x_s, y_s, y_q, *, n_class, iters, knn, lmd, norm_typ
             energies.append(e)
             pred = np.argmax(y, axis=1)
             accs.append(np.float32((y_q[i] == pred).astype(np.float32).mean()))
+            preds_iter.append(pred)
             if it > 1 and abs(e - old_e) <= 1e-6 * abs(old_e):
                 energies += [e] * (iters - it - 1)
                 accs += [accs[-1]] * (iters - it - 1)
+                preds_iter += [pred] * (iters - it - 1)
+                frozen_at = it
                 break
             old_e = e
         out["unary"].append(unary.astype(np.float32))
@@ -510,4 +515,6 @@ def run_laplacian_shot(x_q, x_s, y_s, y_q, *, n_class, iters, knn, lmd, norm_typ
         out["preds"].append(pred)
         out["acc"].append(accs)
         out["ent_energy"].append(energies)
+        out["preds_iter"].append(preds_iter)
+        out["frozen_at"].append(frozen_at)
     return {k: np.asarray(v) for k, v in out.items()}

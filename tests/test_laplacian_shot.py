@@ -31,6 +31,13 @@ def test_oracle_reproduces_reference(name):
     assert np.array_equal(t["neighbours"], g["neighbours"]) and np.array_equal(t["preds"], g["preds"])
     assert np.allclose(t["unary"], g["unary"], rtol=1e-6, atol=0) and np.array_equal(t["acc"].astype(np.float32), g["acc"])
     assert np.allclose(t["ent_energy"], g["ent_energy"], rtol=1e-9, atol=0)
+    # the per-update assignments: the accuracies recomputed from them are the fixture's, and the freeze is where they say
+    iters = int(g["iters"])
+    assert t["preds_iter"].shape == (g["y_q"].shape[0], iters, g["preds"].shape[1]) and t["frozen_at"].shape == (g["y_q"].shape[0],)
+    acc = (t["preds_iter"] == g["y_q"].reshape(g["y_q"].shape[0], 1, -1)).astype(np.float32).mean(2)
+    assert np.array_equal(acc, g["acc"]) and np.array_equal(t["preds_iter"][:, -1], g["preds"])
+    for f, e, p in zip(t["frozen_at"], g["ent_energy"], t["preds_iter"]):
+        assert -1 <= f < iters and (f < 0 or (f >= 2 and np.all(e[f:] == e[f]) and np.all(p[f:] == p[f])))
 
 
 @pytest.mark.gpu
