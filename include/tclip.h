@@ -465,6 +465,8 @@ int tclip_argmax_rows(const float* x, int64_t n_rows, int32_t n_class, int32_t* 
  * src/utils.py:287-290): out[n,:] = softmax_k(T * (visual[n]/||visual[n]||) . text[k]).
  *   visual device [n_rows, dim] f32 (any norm), text device [n_class, dim] f32 (unit-norm rows, as
  *   clip_weights returns them, src/utils.py:363-377), out device [n_rows, n_class] f32.
+ *   text may start at any float: it is read 16 bytes at a time only when dim % 4 == 0 and text is 16-byte aligned, and the
+ *   result has the same bits either way.  dim + n_class <= 15000 (TCLIP_ERR_ARG beyond); n_rows = 0 is TCLIP_OK.
  * This is the only reference-consistent way to feed visual features to EM-Dirichlet (which raises
  * ValueError on features outside the simplex, em_dirichlet.py:204-208). */
 int tclip_probability_features(const float* visual, const float* text, int64_t n_rows, int32_t dim, int32_t n_class,

@@ -434,7 +434,7 @@ int tclip_visual_init(const float* visual, const float* text, int64_t n_rows, in
     const size_t lds = ((size_t)dim + (size_t)n_class) * sizeof(float);
     if (lds > 60000 || n_rows > 0x7fffffff) return fail(TCLIP_ERR_ARG, "dim + n_class must be <= 15000");
     hipLaunchKernelGGL(k_probability_features<true>, dim3((unsigned)n_rows), dim3(256), lds, (hipStream_t)stream, visual, text, dim,
-                       n_class, temperature, out);
+                       n_class, temperature, front_end_vec(text, dim), out);
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
 }
