@@ -44,7 +44,10 @@ extern "C" {
  *    tclip_bdcspn_visual_run_tasks, tclip_laplacian_shot_tasks_workspace_bytes, tclip_laplacian_shot_run_tasks,
  *    tclip_laplacian_shot_visual_tasks_workspace_bytes, tclip_laplacian_shot_visual_run_tasks;
  *    tclip_alpha_tim_tasks_workspace_bytes, tclip_alpha_tim_run_tasks, tclip_alpha_tim_visual_tasks_workspace_bytes,
- *    tclip_alpha_tim_visual_run_tasks, tclip_tim_gd_tasks_workspace_bytes, tclip_tim_gd_run_tasks
+ *    tclip_alpha_tim_visual_run_tasks, tclip_tim_gd_tasks_workspace_bytes, tclip_tim_gd_run_tasks;
+ *    tclip_paddle_sweep_tasks_workspace_bytes, tclip_paddle_sweep_tasks, tclip_bdcspn_sweep_tasks_workspace_bytes,
+ *    tclip_bdcspn_sweep_tasks, tclip_laplacian_shot_sweep_tasks_workspace_bytes, tclip_laplacian_shot_sweep_tasks,
+ *    tclip_alpha_tim_sweep_tasks_workspace_bytes, tclip_alpha_tim_sweep_tasks
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -622,6 +625,47 @@ int tclip_debug_set_kmeans_tile(int32_t mode);
  *           csrc/tclip_selftest_inputs.h; oracle/mathcheck.cpp computes the host values.
  * [0]..[4] must be 0.  Allocates (and frees) 112 bytes of device memory for the counters. */
 int tclip_selftest_primitives(uint64_t* mismatches);
+
+/* Value sweeps: the four tunable few-shot methods (PADDLE: lambd, BD-CSPN: temp, LAPLACIAN_SHOT: lmd, ALPHA_TIM: alpha_value)
+ * solved for a LIST of values on the same tasks in one call - what the reference's scripts/opt_parameters.sh does with one
+ * process per value.  `src`, `y_s` and every argument not named here are those of the method's *_run_tasks entry.
+ *   dim       0: probability features (rows of n_class elements, src->cols allowed) - the problem of <method>_run_tasks;
+ *             1..1024: visual features (rows of dim elements, src->cols must be NULL) - that of <method>_visual_run_tasks
+ *   values    HOST array [n_values] of finite doubles, n_values >= 1; value i is converted as the single-value entry converts
+ *             its scalar ((float) for lambd, temp and alpha_value; lmd stays double).  Read before the call returns.
+ * Outputs that depend on the value are value-major, [n_values] in front of the single-value entry's layout; LAPLACIAN_SHOT's
+ * unary and neighbours do not depend on it and are written once:
+ *   PADDLE          u [P,T,Q,K], v [P,T,K], w [P,T,K,D], preds [P,T,Q]
+ *   BD-CSPN         prototypes [P,T,K,D], u [P,T,Q,K], preds [P,T,Q]
+ *   LAPLACIAN_SHOT  unary [T,Q,K], neighbours [T,Q,knn-1], preds_iter [P,T,iters,Q], energies [P,T,iters]
+ *   ALPHA_TIM       weights [P,T,K,D], logits_q [P,T,Q,K], preds [P,T,Q], criterions [P,B,iters]; prm->alpha_value is not read
+ *                   (each value must differ from 1 where an entropy is TCLIP_TIM_ALPHA)
+ * Slice i of every such output holds the bits the single-value entry returns for values[i] on the same source; repeated values
+ * give repeated slices.  What does not read the value runs once per task: PADDLE's support class sums; BD-CSPN up to and
+ * including its augmented set; LAPLACIAN_SHOT's normalisation, prototypes, unary term and kNN graph.  PADDLE and BD-CSPN then
+ * run their values one after the other on the stream, reusing one value's scratch; LAPLACIAN_SHOT runs its updates on a grid of
+ * (task, value); ALPHA_TIM runs its Adam loop over n_values * T solves in one set of launches per step, solve p T + t reading
+ * the rows of task t in place.
+ * Limits and checks are the single-value entry's, all before any launch, and: dim outside 0..1024, n_values < 1, a NULL or
+ * non-finite value, n_values * T > 65535 (TCLIP_ERR_ARG).  Workspace: <entry>_workspace_bytes(p, dim, n_values) bytes (0 on
+ * bad input), 256-byte aligned; it grows with n_values for LAPLACIAN_SHOT (the fp64 assignments, 16 T Q K bytes per value)
+ * and ALPHA_TIM (everything but the support class sums), not for PADDLE and BD-CSPN. */
+size_t tclip_paddle_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values);
+int tclip_paddle_sweep_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
+                             int32_t n_values, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t tclip_bdcspn_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values);
+int tclip_bdcspn_sweep_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
+                             int32_t n_values, int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                             size_t workspace_bytes, void* stream);
+size_t tclip_laplacian_shot_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values);
+int tclip_laplacian_shot_sweep_tasks(const tclip_problem* p, int32_t dim, const tclip_task_source* src, const int64_t* y_s, int32_t knn,
+                                     const double* values, int32_t n_values, int32_t norm_type, float* unary, int32_t* neighbours,
+                                     int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream);
+size_t tclip_alpha_tim_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values);
+int tclip_alpha_tim_sweep_tasks(const tclip_problem* p, int32_t dim, const tclip_tim_params* prm, const tclip_task_source* src,
+                                const int64_t* y_s, const double* values, int32_t n_values, float* weights, float* logits_q,
+                                int32_t* preds, float* criterions, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,9 @@
 // tclip_laplacian_shot_visual_run the one for D-dim embeddings (any D in 1..1024; distances by k_lshot_pairdist).
 // tclip_laplacian_shot[_visual]_run_tasks are the same two fed from the feature tables: k_lshot_normalize reads the task rows
 // in place through a RowSrc, everything after it is shared.
+// tclip_laplacian_shot_sweep_tasks solves the same tasks for a list of lmd values: everything up to the kNN graph once per task
+// (k_lshot_knn), the updates on a grid of (task, value) (k_lshot_sweep_updates); lshot_knn_rows and lshot_solve are the code
+// k_lshot_task runs, so every value's slice holds the single-value entry's bits.
 //
 // Per task: L2-normalised features, prototypes = support class means, unary[q][k] = ||proto_k - z_q||^2, a kNN graph
 // over the task's queries (W[i][j] = 1 for the knn-1 nearest other queries j of i), then `iter` bound updates
@@ -153,25 +156,14 @@ struct LshotArgs {
     double lmd;
 };
 
-// One workgroup per task: kNN graph, then the bound updates.
-__global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
-    extern __shared__ char lshot_smem[];
-    const int Q = a.Q, K = a.K, D = a.D, nn = a.knn - 1, t = blockIdx.x;
-    int* nbr = reinterpret_cast<int*>(lshot_smem);                     // [Q][nn]
-    double* row_e = reinterpret_cast<double*>(lshot_smem + (((size_t)Q * nn * sizeof(int) + 7) & ~(size_t)7));   // [Q]
-    __shared__ int frozen;
-    __shared__ double e_old;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const float* zq = a.zq + (size_t)t * Q * D;
-    const double* pd = a.d2 ? a.d2 + (size_t)t * Q * Q : nullptr;
-    const float* unary = a.unary + (size_t)t * Q * K;
-    double* y0 = a.ybuf + (size_t)t * 2 * Q * K;
-    double* y1 = y0 + (size_t)Q * K;
-
-    // ---- kNN over the task's queries (create_affinity, :91-101): squared distances in fp64 (computed here, or read from
-    // k_lshot_pairdist's table: coalesced, a lane's 64-strided columns of row i), the nn nearest others, ties to the lower
-    // index (exact ties do not occur between distinct images)
-    for (int i = wave; i < Q; i += kLshotWaves) {
+// The kNN lists of the query rows i = first, first + step, ... of one task, one wavefront per row (create_affinity, :91-101):
+// squared distances in fp64 (computed here, or read from k_lshot_pairdist's table `pd`: coalesced, a lane's 64-strided columns
+// of row i), the nn nearest others, ties to the lower index (exact ties do not occur between distinct images).  A row's list
+// depends on that row alone, so which wavefront of which block takes it changes nothing.  nbr_lds [Q][nn] (or nullptr) and
+// nbr_out [Q][nn] are this task's lists.
+__device__ __forceinline__ void lshot_knn_rows(const float* zq, const double* pd, int Q, int D, int nn, int first, int step, int lane,
+                                               int* nbr_lds, int32_t* nbr_out) {
+    for (int i = first; i < Q; i += step) {
         double d2[kLshotMaxQ / 64];
         const float* zi = zq + (size_t)i * D;
 #pragma unroll
@@ -208,11 +200,22 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
                 if (e * 64 + lane == arg) d2[e] = INFINITY;
             if (arg >= Q) arg = i;                                    // only with NaN features: stay inside the task
             if (lane == 0) {
-                nbr[i * nn + r] = arg;
-                a.neighbours[((size_t)t * Q + i) * nn + r] = arg;
+                if (nbr_lds) nbr_lds[i * nn + r] = arg;
+                nbr_out[(size_t)i * nn + r] = arg;
             }
         }
     }
+}
+
+// One solve by one workgroup of kLshotWaves wavefronts, the neighbour lists nbr [Q][nn] already in LDS: Y = normalize(-unary),
+// then the bound updates with their energies, the freeze rule and the tail fill.  k_lshot_task (one value) and
+// k_lshot_sweep_updates (a list of values) both call this, so both compile the same expressions.
+// unary [Q][K], y0 / y1 [Q][K] each, preds_iter [iters][Q] and energies [iters] are this solve's; row_e [Q], frozen and e_old
+// are the block's LDS.
+__device__ __forceinline__ void lshot_solve(const float* unary, const int* nbr, double* row_e, int* frozen, double* e_old, double* y0,
+                                            double* y1, int32_t* preds_iter, double* energies, int Q, int K, int nn, int iters,
+                                            double lmd) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // ---- Y = normalize(-unary), fp32 as in the reference (:143)
     for (int q = wave; q < Q; q += kLshotWaves) {
         const float* u = unary + (size_t)q * K;
@@ -225,15 +228,15 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
         for (int k = lane; k < K; k += 64) y0[(size_t)q * K + k] = (double)(expf(-u[k] - mx) / s);
     }
     if (threadIdx.x == 0) {
-        frozen = 0;
-        e_old = INFINITY;
+        *frozen = 0;
+        *e_old = INFINITY;
     }
     __syncthreads();
 
     double* yold = y0;
     double* ynew = y1;
     int it = 0;
-    for (; it < a.iters; it++) {
+    for (; it < iters; it++) {
         // Y_new[q] = softmax_k(-unary[q] + lmd * sum_{j in nbr(q)} Y_old[j])                                (:150-154)
         for (int q = wave; q < Q; q += kLshotWaves) {
             const float* u = unary + (size_t)q * K;
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
             for (int k = lane; k < K; k += 64) {
                 double m = 0.0;
                 for (int r = 0; r < nn; r++) m += yold[(size_t)nbr[q * nn + r] * K + k];
-                const double add = -(double)u[k] - (-a.lmd * m);
+                const double add = -(double)u[k] - (-lmd * m);
                 ynew[(size_t)q * K + k] = add;
                 if (add > mx) { mx = add; arg = k; }
             }
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
             }
             s = lshot_wave_sum(s);
             for (int k = lane; k < K; k += 64) ynew[(size_t)q * K + k] /= s;
-            if (lane == 0) a.preds_iter[((size_t)t * a.iters + it) * Q + q] = arg < K ? arg : 0;   // argmax of Y = argmax of its logits (0 for a NaN row)
+            if (lane == 0) preds_iter[(size_t)it * Q + q] = arg < K ? arg : 0;   // argmax of Y = argmax of its logits (0 for a NaN row)
         }
         __syncthreads();
         // E = sum Y log max(Y, 1e-20) + unary Y - lmd (W Y) Y, with the NEW Y on both sides of W                 (:120-126)
@@ -270,7 +273,7 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
                 const double y = ynew[(size_t)q * K + k];
                 double m = 0.0;
                 for (int r = 0; r < nn; r++) m += ynew[(size_t)nbr[q * nn + r] * K + k];
-                e += y * log(fmax(y, 1e-20)) + ((double)u[k] * y + (-a.lmd * m * y));
+                e += y * log(fmax(y, 1e-20)) + ((double)u[k] * y + (-lmd * m * y));
             }
             e = lshot_wave_sum(e);
             if (lane == 0) row_e[q] = e;
@@ -279,29 +282,74 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
         if (threadIdx.x == 0) {
             double e = 0.0;
             for (int q = 0; q < Q; q++) e += row_e[q];
-            a.energies[(size_t)t * a.iters + it] = e;
-            if (it > 1 && fabs(e - e_old) <= 1e-6 * fabs(e_old)) frozen = 1;          // (:162)
-            else e_old = e;
+            energies[it] = e;
+            if (it > 1 && fabs(e - *e_old) <= 1e-6 * fabs(*e_old)) *frozen = 1;          // (:162)
+            else *e_old = e;
         }
         __syncthreads();
         double* sw = yold;
         yold = ynew;
         ynew = sw;
-        if (frozen) break;
+        if (*frozen) break;
     }
     // frozen: the assignment and the energy of update `it` are repeated for the remaining entries               (:164-171)
-    if (it < a.iters) {
-        for (int j = it + 1; j < a.iters; j++) {
-            for (int q = threadIdx.x; q < Q; q += blockDim.x)
-                a.preds_iter[((size_t)t * a.iters + j) * Q + q] = a.preds_iter[((size_t)t * a.iters + it) * Q + q];
-            if (threadIdx.x == 0) a.energies[(size_t)t * a.iters + j] = a.energies[(size_t)t * a.iters + it];
+    if (it < iters) {
+        for (int j = it + 1; j < iters; j++) {
+            for (int q = threadIdx.x; q < Q; q += blockDim.x) preds_iter[(size_t)j * Q + q] = preds_iter[(size_t)it * Q + q];
+            if (threadIdx.x == 0) energies[j] = energies[it];
         }
     }
 }
 
-struct LshotWs { size_t zs, zq, sup, cnt, proto, ybuf, d2, total; };
-// rows of `dim` elements; pairdist: room for k_lshot_pairdist's [T][Q][Q] fp64 table (the visual entry)
-static LshotWs lshot_ws(const tclip_problem& p, int dim, bool pairdist) {
+// One workgroup per task: kNN graph, then the bound updates.
+__global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_task(LshotArgs a) {
+    extern __shared__ char lshot_smem[];
+    const int Q = a.Q, K = a.K, D = a.D, nn = a.knn - 1, t = blockIdx.x;
+    int* nbr = reinterpret_cast<int*>(lshot_smem);                     // [Q][nn]
+    double* row_e = reinterpret_cast<double*>(lshot_smem + (((size_t)Q * nn * sizeof(int) + 7) & ~(size_t)7));   // [Q]
+    __shared__ int frozen;
+    __shared__ double e_old;
+    double* y0 = a.ybuf + (size_t)t * 2 * Q * K;
+    lshot_knn_rows(a.zq + (size_t)t * Q * D, a.d2 ? a.d2 + (size_t)t * Q * Q : nullptr, Q, D, nn, threadIdx.x >> 6, kLshotWaves,
+                   threadIdx.x & 63, nbr, a.neighbours + (size_t)t * Q * nn);
+    lshot_solve(a.unary + (size_t)t * Q * K, nbr, row_e, &frozen, &e_old, y0, y0 + (size_t)Q * K, a.preds_iter + (size_t)t * a.iters * Q,
+                a.energies + (size_t)t * a.iters, Q, K, nn, a.iters, a.lmd);
+}
+
+// ---- the value sweep (tclip_laplacian_shot_sweep_tasks): the graph once per task, the updates once per (task, value) -------
+// The neighbour lists of every task into global memory: grid (ceil(Q / kLshotWaves), T), one wavefront per query row.
+__global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_knn(const float* __restrict__ zq, const double* __restrict__ d2, int Q, int D,
+                                                                int nn, int32_t* __restrict__ neighbours) {
+    const int t = blockIdx.y, i = blockIdx.x * kLshotWaves + (threadIdx.x >> 6);
+    if (i >= Q) return;
+    lshot_knn_rows(zq + (size_t)t * Q * D, d2 ? d2 + (size_t)t * Q * Q : nullptr, Q, D, nn, i, Q, threadIdx.x & 63, nullptr,
+                   neighbours + (size_t)t * Q * nn);
+}
+
+// Grid (task, value): block (t, p) solves task t of T with lmd[p].  It reads the task's unary term and neighbour lists (into
+// LDS, as k_lshot_task keeps them) and owns slice p T + t of ybuf [P][T][2][Q][K], preds_iter [P][T][iters][Q] and
+// energies [P][T][iters].
+__global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_sweep_updates(LshotArgs a, const double* __restrict__ lmd, int T) {
+    extern __shared__ char lshot_smem[];
+    const int Q = a.Q, K = a.K, nn = a.knn - 1, t = blockIdx.x, p = blockIdx.y;
+    int* nbr = reinterpret_cast<int*>(lshot_smem);                     // [Q][nn]
+    double* row_e = reinterpret_cast<double*>(lshot_smem + (((size_t)Q * nn * sizeof(int) + 7) & ~(size_t)7));   // [Q]
+    __shared__ int frozen;
+    __shared__ double e_old;
+    const int32_t* lists = a.neighbours + (size_t)t * Q * nn;
+    for (int i = threadIdx.x; i < Q * nn; i += blockDim.x) nbr[i] = lists[i];
+    __syncthreads();
+    const size_t vt = (size_t)p * T + t;                              // < P T
+    double* y0 = a.ybuf + vt * 2 * Q * K;
+    lshot_solve(a.unary + (size_t)t * Q * K, nbr, row_e, &frozen, &e_old, y0, y0 + (size_t)Q * K, a.preds_iter + vt * a.iters * Q,
+                a.energies + vt * a.iters, Q, K, nn, a.iters, lmd[p]);
+}
+
+struct LshotWs { size_t zs, zq, sup, cnt, proto, ybuf, d2, vals, total; };
+// rows of `dim` elements; pairdist: room for k_lshot_pairdist's [T][Q][Q] fp64 table (the visual entry); n_values > 0 (the
+// sweep entry): ybuf for every (value, task) - the only region that grows with the values - and the values themselves; both
+// take a whole number of 256-byte units PER VALUE, so that the total is affine in n_values
+static LshotWs lshot_ws(const tclip_problem& p, int dim, bool pairdist, int n_values = 0) {
     const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, D = dim;
     LshotWs w;
     size_t o = 0;
@@ -311,8 +359,9 @@ static LshotWs lshot_ws(const tclip_problem& p, int dim, bool pairdist) {
     w.sup = take(T * K * D * 4);
     w.cnt = take(T * K * 4);
     w.proto = take(T * K * D * 4);
-    w.ybuf = take(T * 2 * Q * K * 8);
+    w.ybuf = take((n_values > 0 ? (size_t)n_values : 1) * align_up(T * 2 * Q * K * 8));
     w.d2 = pairdist ? take(T * Q * Q * 8) : 0;
+    w.vals = n_values > 0 ? take((size_t)n_values * align_up(8)) : 0;
     w.total = o;
     return w;
 }
@@ -332,10 +381,13 @@ static int check_lshot(const tclip_problem* pp, int32_t knn, int32_t norm_type) 
 // The launch sequence of both entries on rows of D elements: the support class sums of k_support_stats at D = K and of
 // k_vis_support_stats otherwise; pairdist = false (probability features): the distances inside k_lshot_task, true (visual
 // features): k_lshot_pairdist's table.
+// values == nullptr: one solve per task with `lmd` (k_lshot_task; preds_iter [T][iters][Q], energies [T][iters]).  Otherwise the
+// sweep: everything up to the distances runs once per task as it stands - none of it reads lmd -, k_lshot_knn writes the
+// neighbour lists and k_lshot_sweep_updates solves every (task, value) (preds_iter [P][T][iters][Q], energies [P][T][iters]).
 static int lshot_run(const tclip_problem& p, int D, bool pairdist, const RowSrc& x_q, const RowSrc& x_s, const int64_t* y_s,
                      int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter,
-                     double* energies, char* ws, hipStream_t st) {
-    const LshotWs o = lshot_ws(p, D, pairdist);
+                     double* energies, char* ws, hipStream_t st, const double* values = nullptr, int n_values = 0) {
+    const LshotWs o = lshot_ws(p, D, pairdist, values ? n_values : 0);
     const size_t smem = (((size_t)p.n_query * (knn - 1) * sizeof(int) + 7) & ~(size_t)7) + (size_t)p.n_query * sizeof(double);
     if (smem > 60000) return fail(TCLIP_ERR_ARG, "n_query * knn too large for the neighbour lists in LDS");
     const int Q = p.n_query, K = p.n_class, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
@@ -367,7 +419,15 @@ static int lshot_run(const tclip_problem& p, int D, bool pairdist, const RowSrc&
     if (pairdist)
         hipLaunchKernelGGL(k_lshot_pairdist, dim3((Q + kLshotPdTile - 1) / kLshotPdTile, T), dim3(256), 0, st, (const float*)zq, Q, D, d2);
     const LshotArgs a{zq, d2, unary, (double*)(ws + o.ybuf), neighbours, preds_iter, energies, Q, K, D, knn, p.iters, lmd};
-    hipLaunchKernelGGL(k_lshot_task, dim3(T), dim3(64 * kLshotWaves), smem, st, a);
+    if (!values) {
+        hipLaunchKernelGGL(k_lshot_task, dim3(T), dim3(64 * kLshotWaves), smem, st, a);
+    } else {
+        double* lmds = (double*)(ws + o.vals);
+        launch_sweep_values(st, values, n_values, lmds, nullptr);
+        hipLaunchKernelGGL(k_lshot_knn, dim3((Q + kLshotWaves - 1) / kLshotWaves, T), dim3(64 * kLshotWaves), 0, st, (const float*)zq,
+                           (const double*)d2, Q, D, knn - 1, neighbours);
+        hipLaunchKernelGGL(k_lshot_sweep_updates, dim3(T, n_values), dim3(64 * kLshotWaves), smem, st, a, (const double*)lmds, T);
+    }
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
 }
@@ -390,6 +450,36 @@ static int lshot_run_tasks(const tclip_problem* pp, int dim, bool visual, const 
 }  // namespace tclip
 
 extern "C" {
+
+// ---- LAPLACIAN_SHOT for a list of lmd values on the same tasks (see lshot_run): dim == 0 is tclip_laplacian_shot_run_tasks'
+// problem, dim > 0 tclip_laplacian_shot_visual_run_tasks'
+size_t tclip_laplacian_shot_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    if (check_problem(p) != TCLIP_OK || check_sweep_dim(dim) != TCLIP_OK) return 0;
+    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive"), 0;
+    if (check_sweep_count(p, n_values) != TCLIP_OK) return 0;
+    return lshot_ws(*p, dim ? dim : p->n_class, dim > 0, n_values).total;
+}
+
+int tclip_laplacian_shot_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, int32_t knn,
+                                     const double* values, int32_t n_values, int32_t norm_type, float* unary, int32_t* neighbours,
+                                     int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    if (int rc = check_sweep_dim(dim)) return rc;
+    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
+    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !unary || !neighbours || !preds_iter ||
+        !energies || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    const bool visual = dim > 0;
+    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT on visual features permutes no columns: cols must be NULL");
+    if (int rc = check_sweep_values(pp, values, n_values)) return rc;
+    const tclip_problem p = *pp;
+    const int D = visual ? dim : p.n_class;
+    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, D, visual, n_values).total,
+                                 "tclip_laplacian_shot_sweep_tasks_workspace_bytes"))
+        return rc;
+    return lshot_run(p, D, visual, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, knn,
+                     0.0, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace, (hipStream_t)stream, values, n_values);
+}
 
 size_t tclip_laplacian_shot_workspace_bytes(const tclip_problem* p) {
     if (check_problem(p) != TCLIP_OK) return 0;

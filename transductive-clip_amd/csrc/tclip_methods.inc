@@ -131,7 +131,7 @@ struct PaddleTasksWs {
 };
 
 struct BdcspnWs {
-    size_t zs, zq, zqn, mean, eta, sup, cnt, wn, aug, logit, cs, live, dummy, total;
+    size_t zs, zq, zqn, mean, eta, sup, cnt, wn, aug, logit, cs, live, dummy, wn0, total;
     static BdcspnWs layout(const tclip_problem& p, int dim) {
         const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
         BdcspnWs w;
@@ -150,6 +150,7 @@ struct BdcspnWs {
         w.cs = take(T * K * 4);
         w.live = take(T * K);
         w.dummy = take(T * R * 4);
+        w.wn0 = w.wn;
         w.total = o;
         return w;
     }
@@ -158,7 +159,9 @@ struct BdcspnWs {
     // not overlap: zs is written by the first normalisation and last read by the normalisation that builds aug (after the
     // support statistics and k_bdcspn_eta); logit is first written by the sp.dist that follows it, on the same stream, and
     // nothing after that reads zs.
-    static BdcspnWs layout_tasks(const tclip_problem& p, int dim) {
+    // sweep (tclip_bdcspn_sweep_tasks): the normalised initial prototypes get a region of their own, wn0 - every value reads
+    // them, and wn is overwritten by each value's rectified prototypes.  No region depends on the number of values.
+    static BdcspnWs layout_tasks(const tclip_problem& p, int dim, bool sweep = false) {
         const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
         BdcspnWs w;
         size_t o = 0;
@@ -176,6 +179,7 @@ struct BdcspnWs {
         w.cs = take(T * K * 4);
         w.live = take(T * K);
         w.dummy = take(T * R * 4);
+        w.wn0 = sweep ? take(T * K * D * 4) : w.wn;
         w.total = o;
         return w;
     }
@@ -276,10 +280,16 @@ static int em_gaussian_cov_loop(const FeatureSpace& sp, const tclip_problem& p, 
 
 // ---- PADDLE (SURVEY.md section 8f, F4): few-shot soft k-means with the class-proportion penalty -------------------------
 // The support set is read exactly once, for the class sums: `x_s` is a dense tensor or table rows read in place.
+// values != nullptr (tclip_paddle_sweep_tasks): the loop runs once per value, one after the other on the stream, with
+// lambd = (float)values[i] and slice i of u [P,T,Q,K], v [P,T,K], w [P,T,K,D], preds [P,T,Q].  The class sums - the one launch
+// that reads the support set, and the only one before the loop that is more than a fill - are taken once; cs, live and the
+// logits are scratch every value reuses.  Each value sees the launches of a single-value call with the same arguments.
 static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const RowSrc& x_s, const int64_t* y_s,
-                       float lambd, float* u, float* v, float* w, int32_t* preds, char* ws, hipStream_t st) {
+                       float lambd, float* u, float* v, float* w, int32_t* preds, char* ws, hipStream_t st,
+                       const double* values = nullptr, int n_values = 0) {
     const PaddleWs o = PaddleWs::layout(p, sp.D);
     const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
+    const size_t TQ = (size_t)T * Q;
     float* sup = (float*)(ws + o.sup);
     float* cnt = (float*)(ws + o.cnt);
     float* cs = (float*)(ws + o.cs);
@@ -287,20 +297,23 @@ static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const flo
     float* logit0 = (float*)(ws + o.logit);
     // init (paddle.py:180-197): v = 0, w = class means of the support set (on visual features the text-prompt u is overwritten
     // before it is read); every centroid moves every iteration
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    sp.support_stats(st, x_s, y_s, T, S, K, sup, cnt);
-    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
-                       (size_t)TK * D, D, w);
-    TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
-    for (int it = 0; it < p.iters; it++) {
-        // u_update (:105-116): softmax_k(-1/2 ||w_k - z_q||^2 + lambd v_k / Q)
-        if (int rc = sp.dist(T, st, w, x_q, live, Q, K, -0.5f, 1.0f, logit0)) return rc;
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
-                           T * Q, Q, K, lambd, 0, 0, u, preds);
-        // v_update (:118-124) and w_update (:142-158)
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 0, cs, live, v,
-                           (int32_t*)nullptr);
-        sp.mstats(st, u, x_q, cs, live, T, Q, K, Mstats::PaddleAdd, w, sup, cnt, false);
+    for (int i = 0; i < (values ? n_values : 1); i++, u += TQ * K, v += TK, w += (size_t)TK * D, preds += TQ) {
+        if (values) lambd = (float)values[i];
+        hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
+        if (i == 0) sp.support_stats(st, x_s, y_s, T, S, K, sup, cnt);
+        hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
+                           (size_t)TK * D, D, w);
+        TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
+        for (int it = 0; it < p.iters; it++) {
+            // u_update (:105-116): softmax_k(-1/2 ||w_k - z_q||^2 + lambd v_k / Q)
+            if (int rc = sp.dist(T, st, w, x_q, live, Q, K, -0.5f, 1.0f, logit0)) return rc;
+            hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
+                               T * Q, Q, K, lambd, 0, 0, u, preds);
+            // v_update (:118-124) and w_update (:142-158)
+            hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 0, cs, live, v,
+                               (int32_t*)nullptr);
+            sp.mstats(st, u, x_q, cs, live, T, Q, K, Mstats::PaddleAdd, w, sup, cnt, false);
+        }
     }
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
@@ -310,8 +323,13 @@ static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const flo
 // k_col_mean, k_bdcspn_normalize, k_bdcspn_eta and k_div_rows take the row length where their signatures say K.
 // x_q / x_s: dense tensors, or table rows read in place by the only three launches that touch them (the train mean and the
 // two normalisations into zs / zq); `o`: BdcspnWs::layout for the former, ::layout_tasks (zs inside logit) for the latter.
+// values != nullptr (tclip_bdcspn_sweep_tasks; o.wn0 a region of its own): everything up to and including the augmented set
+// reads no temp and runs once; from the first soft assignment on the pass runs once per value, one after the other on the
+// stream, with temp = (float)values[i] and slice i of prototypes [P,T,K,D], u [P,T,Q,K], preds [P,T,Q].  Each value sees the
+// launches of a single-value call with the same arguments.
 static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const BdcspnWs& o, const RowSrc& x_q, const RowSrc& x_s,
-                       const int64_t* y_s, float temp, int norm_type, float* prototypes, float* u, int32_t* preds, char* ws, hipStream_t st) {
+                       const int64_t* y_s, float temp, int norm_type, float* prototypes, float* u, int32_t* preds, char* ws, hipStream_t st,
+                       const double* values = nullptr, int n_values = 0) {
     const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, R = S + Q, T = p.n_batches * p.tasks_per_batch, TK = T * K;
     const int TD = T * D;
     float* zs = (float*)(ws + o.zs);
@@ -322,6 +340,7 @@ static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const Bdc
     float* sup = (float*)(ws + o.sup);
     float* cnt = (float*)(ws + o.cnt);
     float* wn = (float*)(ws + o.wn);
+    float* wn0 = (float*)(ws + o.wn0);                                // the normalised initial prototypes: wn itself but in a sweep
     float* aug = (float*)(ws + o.aug);
     float* logit = (float*)(ws + o.logit);
     float* cs = (float*)(ws + o.cs);
@@ -351,25 +370,28 @@ static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const Bdc
     sp.support_stats(st, dense_rows(zs), y_s, T, S, K, sup, cnt);
     hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
                        (size_t)TK * D, D, prototypes);
-    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
+    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn0);
     // augmented set: support rows, then query rows shifted by eta = mean(support) - mean(query); normalised (:127-131, :51, :137)
     hipLaunchKernelGGL(k_bdcspn_eta, dim3((TD + 255) / 256), dim3(256), 0, st, (const float*)zs, (const float*)zq, T, S, Q, D, eta);
     normalize((const float*)zs, (const float*)zq, S, R, 1, (const float*)nullptr, (const float*)eta, aug);
-    // soft assignment of the augmented set to the initial prototypes (:133-134)
-    TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
-    if (int rc = sp.dist(T, st, wn, aug, live, R, K, -0.5f, temp, logit)) return rc;
-    hipLaunchKernelGGL(k_softmax, dim3((T * R * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
-                       T * R, R, K, 0.0f, 0, 0, logit, dummy);
-    // rectified prototypes = assignment-weighted means of the normalised augmented set (:137-141)
-    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)logit, T, R, K, 0, cs, live,
-                       (float*)nullptr, (int32_t*)nullptr);
-    sp.mstats(st, logit, aug, cs, live, T, R, K, Mstats::PlainQuotient, prototypes, nullptr, nullptr, false);
-    // prediction (:190-193): softmax(temp * get_logits(prototypes, query)), argmax
-    normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
-    normalize((const float*)zq, (const float*)zq, Q, Q, 1, (const float*)nullptr, (const float*)nullptr, zqn);
-    if (int rc = sp.dist(T, st, wn, zqn, live, Q, K, -0.5f, temp, logit)) return rc;
-    hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
-                       T * Q, Q, K, 0.0f, 0, 0, u, preds);
+    for (int i = 0; i < (values ? n_values : 1); i++, prototypes += (size_t)TK * D, u += (size_t)T * Q * K, preds += (size_t)T * Q) {
+        if (values) temp = (float)values[i];
+        // soft assignment of the augmented set to the initial prototypes (:133-134)
+        TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
+        if (int rc = sp.dist(T, st, wn0, aug, live, R, K, -0.5f, temp, logit)) return rc;
+        hipLaunchKernelGGL(k_softmax, dim3((T * R * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
+                           T * R, R, K, 0.0f, 0, 0, logit, dummy);
+        // rectified prototypes = assignment-weighted means of the normalised augmented set (:137-141)
+        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)logit, T, R, K, 0, cs, live,
+                           (float*)nullptr, (int32_t*)nullptr);
+        sp.mstats(st, logit, aug, cs, live, T, R, K, Mstats::PlainQuotient, prototypes, nullptr, nullptr, false);
+        // prediction (:190-193): softmax(temp * get_logits(prototypes, query)), argmax
+        normalize((const float*)prototypes, (const float*)prototypes, K, K, 1, (const float*)nullptr, (const float*)nullptr, wn);
+        normalize((const float*)zq, (const float*)zq, Q, Q, 1, (const float*)nullptr, (const float*)nullptr, zqn);
+        if (int rc = sp.dist(T, st, wn, zqn, live, Q, K, -0.5f, temp, logit)) return rc;
+        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit, (const float*)nullptr,
+                           T * Q, Q, K, 0.0f, 0, 0, u, preds);
+    }
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
 }
@@ -560,19 +582,23 @@ int tclip_paddle_run(const tclip_problem* pp, const float* x_q, const float* x_s
 
 // PADDLE from the feature tables on rows of `dim` elements: the queries are gathered (and, probability features, permuted)
 // once into the workspace, the support rows are read in place by the support statistics; then paddle_loop as it stands
+// sweep: values / n_values in place of lambd (paddle_loop), checked here
 static int paddle_run_tasks(const FeatureSpace& sp, const tclip_problem& p, const tclip_task_source* src, const int64_t* y_s, float lambd,
                             float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes, const char* query_name,
-                            hipStream_t st) {
+                            hipStream_t st, bool sweep = false, const double* values = nullptr, int n_values = 0) {
     if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !u || !v || !w || !preds || !workspace)
         return fail(TCLIP_ERR_ARG, kNullArg);
     if (sp.visual && src->cols) return fail(TCLIP_ERR_ARG, "PADDLE on visual features permutes no columns: cols must be NULL");
+    if (sweep)
+        if (int rc = check_sweep_values(&p, values, n_values)) return rc;
     const PaddleTasksWs o = PaddleTasksWs::layout(p, sp.D);
     if (int rc = check_workspace(workspace, workspace_bytes, o.total, query_name)) return rc;
     const int64_t T = (int64_t)p.n_batches * p.tasks_per_batch;
     float* x_q = (float*)((char*)workspace + o.xq);
     // every q_idx value has been checked by the caller (tclip_check_task_indices): no row of x_q stays unwritten
     launch_gather_task_rows(st, src->table_q, INT64_MAX, sp.D, src->q_idx, p.n_query, src->cols, T * p.n_query, x_q);
-    return paddle_loop(sp, p, x_q, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, lambd, u, v, w, preds, (char*)workspace, st);
+    return paddle_loop(sp, p, x_q, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, lambd, u, v, w, preds, (char*)workspace, st, values,
+                       n_values);
 }
 
 size_t tclip_paddle_tasks_workspace_bytes(const tclip_problem* p) {
@@ -653,17 +679,20 @@ int tclip_bdcspn_visual_run(const tclip_problem* pp, int32_t dim, const float* x
 
 // BD-CSPN from the feature tables on rows of `dim` elements: bdcspn_pass reads both row sets in place, neither x_s nor x_q is
 // built, and zs shares the logit region (BdcspnWs::layout_tasks)
+// sweep: values / n_values in place of temp (bdcspn_pass), checked here
 static int bdcspn_run_tasks(const FeatureSpace& sp, const tclip_problem& p, const tclip_task_source* src, const int64_t* y_s, float temp,
                             int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace, size_t workspace_bytes,
-                            const char* query_name, hipStream_t st) {
+                            const char* query_name, hipStream_t st, bool sweep = false, const double* values = nullptr, int n_values = 0) {
     if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !prototypes || !u || !preds || !workspace)
         return fail(TCLIP_ERR_ARG, kNullArg);
     if (sp.visual && src->cols) return fail(TCLIP_ERR_ARG, "BDCSPN on visual features permutes no columns: cols must be NULL");
     if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
-    const BdcspnWs o = BdcspnWs::layout_tasks(p, sp.D);
+    if (sweep)
+        if (int rc = check_sweep_values(&p, values, n_values)) return rc;
+    const BdcspnWs o = BdcspnWs::layout_tasks(p, sp.D, sweep);
     if (int rc = check_workspace(workspace, workspace_bytes, o.total, query_name)) return rc;
     return bdcspn_pass(sp, p, o, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, temp,
-                       norm_type, prototypes, u, preds, (char*)workspace, st);
+                       norm_type, prototypes, u, preds, (char*)workspace, st, values, n_values);
 }
 
 size_t tclip_bdcspn_tasks_workspace_bytes(const tclip_problem* p) {
@@ -691,6 +720,43 @@ int tclip_bdcspn_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tc
     if (int rc = check_visual_fs(pp, dim, "BDCSPN")) return rc;
     return bdcspn_run_tasks(FeatureSpace{dim, true}, *pp, src, y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes,
                             "tclip_bdcspn_visual_tasks_workspace_bytes", (hipStream_t)stream);
+}
+
+// ---- PADDLE and BD-CSPN for a list of values on the same tasks (paddle_loop / bdcspn_pass with `values`): dim == 0 is the
+// problem of tclip_paddle_run_tasks / tclip_bdcspn_run_tasks, dim > 0 that of the _visual_run_tasks entries
+// the checks before `src` is looked at: the problem, dim, and what the entry for this feature kind checks of both
+static int check_sweep_fs(const tclip_problem* p, int32_t dim, const char* who) {
+    if (int rc = check_problem(p)) return rc;
+    if (int rc = check_sweep_dim(dim)) return rc;
+    if (dim > 0) return check_visual_fs(p, dim, who);
+    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, who);
+    return TCLIP_OK;
+}
+
+size_t tclip_paddle_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    if (check_sweep_fs(p, dim, "PADDLE") != TCLIP_OK || check_sweep_count(p, n_values) != TCLIP_OK) return 0;
+    return PaddleTasksWs::layout(*p, dim ? dim : p->n_class).total;
+}
+
+int tclip_paddle_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
+                             int32_t n_values, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    if (int rc = check_sweep_fs(pp, dim, "PADDLE")) return rc;
+    return paddle_run_tasks(FeatureSpace{dim ? dim : pp->n_class, dim > 0}, *pp, src, y_s, 0.0f, u, v, w, preds, workspace, workspace_bytes,
+                            "tclip_paddle_sweep_tasks_workspace_bytes", (hipStream_t)stream, true, values, n_values);
+}
+
+size_t tclip_bdcspn_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    if (check_sweep_fs(p, dim, "BDCSPN") != TCLIP_OK || check_sweep_count(p, n_values) != TCLIP_OK) return 0;
+    return BdcspnWs::layout_tasks(*p, dim ? dim : p->n_class, true).total;
+}
+
+int tclip_bdcspn_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
+                             int32_t n_values, int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    if (int rc = check_sweep_fs(pp, dim, "BDCSPN")) return rc;
+    return bdcspn_run_tasks(FeatureSpace{dim ? dim : pp->n_class, dim > 0}, *pp, src, y_s, 0.0f, norm_type, prototypes, u, preds, workspace,
+                            workspace_bytes, "tclip_bdcspn_sweep_tasks_workspace_bytes", (hipStream_t)stream, true, values, n_values);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@
 // touches a task row goes through TimRows<kIdx>::row, and kIdx = true reads the table rows in place in every step.
 // Per iteration: k_tim_gemm_mfma<false> (logits; 64x64 tiles on the matrix cores), k_tim_softmax, k_tim_marginal, k_tim_grad,
 // k_tim_gemm_mfma<true> (dW, also the column sums of G), k_tim_adam (one wavefront per weight row), k_tim_criterion.
+// tclip_alpha_tim_sweep_tasks runs the same loop over n_values x tasks solves for a list of alpha values (tim_loop_on with
+// `values`); the helpers all four sweep entries share (check_sweep_*, k_sweep_values) are here too, this file being included first.
 
 namespace tclip {
 
@@ -28,6 +30,7 @@ struct TimRows<false> {
     const float* xs;
     const float* xq;
     int S, Q, D;
+    __device__ int real(int t) const { return t; }
     __device__ const float* row(int t, int i) const {
         return i < S ? xs + ((size_t)t * S + i) * D : xq + ((size_t)t * Q + (i - S)) * D;
     }
@@ -40,11 +43,63 @@ struct TimRows<true> {
     const int64_t* q_idx;    // [T, Q]
     const int32_t* cols;     // [T, D] or nullptr
     int S, Q, D;
+    int n_real;              // 0: every task has index rows of its own.  T > 0 (a value sweep): task t reads the rows of task t % T
+    // the task whose rows task t reads: a kernel takes it once and passes IT to row() and task_cols()
+    __device__ int real(int t) const { return n_real ? t % n_real : t; }
     __device__ const float* row(int t, int i) const {
         return i < S ? xs + (size_t)s_idx[(size_t)t * S + i] * D : xq + (size_t)q_idx[(size_t)t * Q + (i - S)] * D;
     }
     __device__ const int32_t* task_cols(int t) const { return cols ? cols + (size_t)t * D : nullptr; }
 };
+
+// ---- value sweeps (tclip_*_sweep_tasks): what the four entries share ---------------------------------------------------------
+// dim of a sweep entry: 0 = probability features (rows of n_class elements), 1..1024 = visual features
+static int check_sweep_dim(int32_t dim) {
+    if (dim < 0 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be 0 (probability features) or in 1..1024 (visual features)");
+    return TCLIP_OK;
+}
+
+// A sweep solves the same T tasks for P values: P T solves, value-major.  Grids carry a solve in blockIdx.y / .z, hence the cap.
+static int check_sweep_count(const tclip_problem* p, int32_t n_values) {
+    if (n_values < 1) return fail(TCLIP_ERR_ARG, "n_values must be >= 1");
+    const size_t VT = (size_t)n_values * p->n_batches * p->tasks_per_batch;
+    if (VT > 65535) return fail(TCLIP_ERR_ARG, "n_values*n_batches*tasks_per_batch must be <= 65535 per call");
+    if (VT * p->n_class > 0x7fffffffu || VT * ((size_t)p->n_support + p->n_query) > 0x7fffffffu)
+        return fail(TCLIP_ERR_ARG, "n_values*tasks*n_class and n_values*tasks*(n_support + n_query) must fit in int32");
+    return TCLIP_OK;
+}
+
+static int check_sweep_values(const tclip_problem* p, const double* values, int32_t n_values) {
+    if (!values) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (int rc = check_sweep_count(p, n_values)) return rc;
+    for (int i = 0; i < n_values; i++)
+        if (!(values[i] - values[i] == 0.0)) return fail(TCLIP_ERR_ARG, "every value of a sweep must be finite");
+    return TCLIP_OK;
+}
+
+// The values on the device for the kernels that read one per solve: kSweepChunk of them per launch as a kernel argument.  (A
+// copy from the caller's pageable host array would make the call wait for the stream.)
+constexpr int kSweepChunk = 16;
+struct SweepChunk { double v[kSweepChunk]; };
+__global__ void k_sweep_values(SweepChunk c, int n, double* __restrict__ out_d, float* __restrict__ out_f) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    double v = c.v[0];
+#pragma unroll
+    for (int j = 1; j < kSweepChunk; j++) v = i == j ? c.v[j] : v;
+    if (out_d) out_d[i] = v;
+    if (out_f) out_f[i] = (float)v;
+}
+
+// out_d [n_values] f64 and / or out_f [n_values] f32 (the conversion the single-value entries apply to their scalar)
+static void launch_sweep_values(hipStream_t st, const double* values, int n_values, double* out_d, float* out_f) {
+    for (int i0 = 0; i0 < n_values; i0 += kSweepChunk) {
+        SweepChunk c = {};
+        const int n = n_values - i0 < kSweepChunk ? n_values - i0 : kSweepChunk;
+        for (int j = 0; j < n; j++) c.v[j] = values[i0 + j];
+        hipLaunchKernelGGL(k_sweep_values, dim3(1), dim3(64), 0, st, c, n, out_d ? out_d + i0 : nullptr, out_f ? out_f + i0 : nullptr);
+    }
+}
 
 constexpr int kTimMarginalGd = 2;   // TimLoss::ent1 of TIM_GD: Shannon with the 1e-12 of tim.py:171-172 inside the logarithm
 struct TimLoss {
@@ -71,10 +126,11 @@ __global__ void k_tim_row_sqnorm(TimRows<kIdx> X, int n_rows_total, float* __res
     const int R = X.S + X.Q;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows_total) return;
-    const float* x = X.row(row / R, row % R);
+    const int tx = X.real(row / R);
+    const float* x = X.row(tx, row % R);
     float s = 0.0f;
     if constexpr (kIdx) {
-        const int32_t* c = X.task_cols(row / R);
+        const int32_t* c = X.task_cols(tx);
         for (int d = lane; d < X.D; d += 64) {
             const float v = x[c ? c[d] : d];
             s = fmaf(v, v, s);
@@ -139,6 +195,7 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
     __shared__ float As[kTimMfmaDepth][TILE + kPad];
     __shared__ float Bs[kTimMfmaDepth][TILE + kPad];
     const int F = X.D, R = X.S + X.Q, t = blockIdx.z;               // F: elements of a feature row
+    const int tx = X.real(t);                                        // the task whose rows this one reads: t itself outside a value sweep
     const int M = kTN ? K : R, N = kTN ? F : K, D = kTN ? R : F;     // C is M x N, the contraction runs over D
     const int m0 = blockIdx.y * TILE, n0 = blockIdx.x * TILE;
     const int id = threadIdx.x, wave = id >> 6, lane = id & 63, wm = wave >> 1, wnn = wave & 1, half = lane >> 5, li = lane & 31;
@@ -163,9 +220,9 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
     const int32_t* c = nullptr;                                      // this task's column permutation, if any
     const float* arow_in_place = nullptr;                            // !kTN: a thread stages the same row of X in every slice
     if constexpr (kIdx) {
-        c = X.task_cols(t);
+        c = X.task_cols(tx);
         rows_vec = !c && ((reinterpret_cast<uintptr_t>(X.xs) | reinterpret_cast<uintptr_t>(X.xq)) & 15) == 0;
-        if (!kTN && m0 + id / kThreadsPerRow < M) arow_in_place = X.row(t, m0 + id / kThreadsPerRow);
+        if (!kTN && m0 + id / kThreadsPerRow < M) arow_in_place = X.row(tx, m0 + id / kThreadsPerRow);
     }
     auto col = [&](int d) {
         if constexpr (kIdx) return c ? c[d] : d;
@@ -176,7 +233,7 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
         if (kTN) {
             const int pp = (id % kThreadsPerDepth) * PER, i = d0 + id / kThreadsPerDepth;
             const float* grow = i < R ? Bmat + ((size_t)t * R + i) * K : nullptr;      // G row i
-            const float* xrow = i < R ? X.row(t, i) : nullptr;
+            const float* xrow = i < R ? X.row(tx, i) : nullptr;
             if (vec && grow) {
 #pragma unroll
                 for (int j = 0; j < PER; j += 4) {
@@ -194,7 +251,7 @@ __global__ __launch_bounds__(256) void k_tim_gemm_mfma(TimRows<kIdx> X, int K, c
             }
         } else {
             const int row = id / kThreadsPerRow, kp = (id % kThreadsPerRow) * PER;
-            const float* arow = kIdx ? arow_in_place : m0 + row < M ? X.row(t, m0 + row) : nullptr;
+            const float* arow = kIdx ? arow_in_place : m0 + row < M ? X.row(tx, m0 + row) : nullptr;
             const float* brow = n0 + row < N ? Bmat + ((size_t)t * K + n0 + row) * F : nullptr;   // W row
             if (vec && d0 + kTimMfmaDepth <= D) {
 #pragma unroll
@@ -341,24 +398,27 @@ __global__ void k_tim_marginal(const float* __restrict__ P, int S, int Q, int K,
 }
 
 // P -> G = dLoss/dlogits, row by row (tim.py:276-305 differentiated by hand; 1e-12 where the reference adds it).
+// alphas == nullptr: every task takes c.alpha and its own labels.  Otherwise (a value sweep over n_real tasks): task t takes
+// alphas[t / n_real] and the labels of task t % n_real.
 __global__ void k_tim_grad(float* __restrict__ P, const int64_t* __restrict__ ys, const float* __restrict__ marg,
-                           int n_rows_total, int S, int Q, int K, TimLoss c) {
+                           int n_rows_total, int S, int Q, int K, TimLoss c, const float* __restrict__ alphas, int n_real) {
     const int R = S + Q;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows_total) return;
     const int t = row / R, i = row % R;
+    const float alpha = alphas ? alphas[t / n_real] : c.alpha;
     float* p = P + (size_t)row * K;
     if (i < S) {                                                      // cross-entropy of a support row: only g_y is non-zero
-        const int y = (int)ys[(size_t)t * S + i];
+        const int y = (int)ys[(size_t)(alphas ? t % n_real : t) * S + i];
         const float py = (y >= 0 && y < K) ? p[y] : 1.0f;
         const float gy = c.ent0 == 0 ? -c.lw0 / ((py + 1e-12f) * (float)S)
-                                     : c.lw0 * powf(py + 1e-12f, -c.alpha) / (float)S;
+                                     : c.lw0 * powf(py + 1e-12f, -alpha) / (float)S;
         const float dot = gy * py;
         for (int k = lane; k < K; k += 64) p[k] = p[k] * ((k == y ? gy : 0.0f) - dot);
         return;
     }
     const float* m = marg + (size_t)t * K;
-    const float invQ = 1.0f / (float)Q, a = c.alpha, am1 = c.alpha - 1.0f;
+    const float invQ = 1.0f / (float)Q, a = alpha, am1 = alpha - 1.0f;
     float g[16], pv[16];
     float dot = 0.0f;
 #pragma unroll
@@ -434,23 +494,30 @@ __global__ void k_tim_criterion(const float* __restrict__ moved, int n, float* _
     if (threadIdx.x == 0) out[(size_t)blockIdx.x * stride] = part[0] / (float)n;
 }
 
-struct TimWs { size_t sup, cnt, P, xn, wn, marg, cs, dW, M, V, moved, total; };
-static TimWs tim_ws(const tclip_problem& p, int dim) {
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, R = (size_t)p.n_support + p.n_query, D = dim;
+struct TimWs { size_t sup, cnt, P, xn, wn, marg, cs, dW, M, V, moved, alphas, total; };
+// n_values > 0 (the sweep entry): the support class sums stay per task; every other region holds n_values * tasks solves, and
+// the values follow as floats.  A region takes a whole number of 256-byte units PER VALUE (more than its contiguous contents
+// need), so that the total is affine in n_values.
+static TimWs tim_ws(const tclip_problem& p, int dim, int n_values = 0) {
+    const size_t K = p.n_class, R = (size_t)p.n_support + p.n_query, D = dim;
+    size_t T = (size_t)p.n_batches * p.tasks_per_batch;
     TimWs w;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
     w.sup = take(T * K * D * 4);
     w.cnt = take(T * K * 4);
-    w.P = take(T * R * K * 4);
-    w.xn = take(T * R * 4);
-    w.wn = take(T * K * 4);
-    w.marg = take(T * K * 4);
-    w.cs = take(T * K * 4);
-    w.dW = take(T * K * D * 4);
-    w.M = take(T * K * D * 4);
-    w.V = take(T * K * D * 4);
-    w.moved = take(T * K * 4);
+    const size_t P = n_values > 0 ? (size_t)n_values : 1;
+    auto take_per_value = [&](size_t bytes) { return take(P * align_up(bytes)); };
+    w.P = take_per_value(T * R * K * 4);
+    w.xn = take_per_value(T * R * 4);
+    w.wn = take_per_value(T * K * 4);
+    w.marg = take_per_value(T * K * 4);
+    w.cs = take_per_value(T * K * 4);
+    w.dW = take_per_value(T * K * D * 4);
+    w.M = take_per_value(T * K * D * 4);
+    w.V = take_per_value(T * K * D * 4);
+    w.moved = take_per_value(T * K * 4);
+    w.alphas = n_values > 0 ? take_per_value(4) : 0;
     w.total = o;
     return w;
 }
@@ -459,13 +526,19 @@ static TimWs tim_ws(const tclip_problem& p, int dim) {
 // batch's tasks and classes; per_task = true (TIM_GD, tim.py:181): criterions [iters, T], the mean over a task's classes.
 // X: the task rows as the three kernels that touch them read them (k_tim_row_sqnorm and the two GEMMs of every step), x_s: the
 // support rows as the class sums of init_weights read them - both dense, or both the feature tables in place (kIdx).
+// values != nullptr (tclip_alpha_tim_sweep_tasks; X.n_real = the tasks): the loop runs over n_values * tasks solves in one set
+// of launches per step, value-major.  Solve t reads the rows and labels of task t % tasks (X.real, k_tim_grad) and takes
+// alpha = values[t / tasks]; the class means are computed once per task and written into every value's weights; a criterion is
+// the mean over one batch's tasks within one value (criterions [n_values, n_batches, iters]).  No kernel mixes two solves, so
+// each computes what the single-value loop computes for its task and its alpha.
 template <bool kIdx>
 static int tim_loop_on(const tclip_problem& p, const TimRows<kIdx>& X, const RowSrc& x_s, double lr, float temp, const TimLoss& loss,
                        bool per_task, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
-                       char* ws, hipStream_t st) {
+                       char* ws, hipStream_t st, const double* values = nullptr, int n_values = 0) {
     const int D = X.D;
-    const TimWs o = tim_ws(p, D);
-    const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
+    const TimWs o = tim_ws(p, D, values ? n_values : 0);
+    const int n_real = p.n_batches * p.tasks_per_batch, n_sweep = values ? n_values : 1;      // n_sweep * n_real <= 65535 (checked)
+    const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches * n_sweep, N = p.tasks_per_batch, T = B * N, TK = T * K;
     const int TR = T * R;
     float* sup = (float*)(ws + o.sup);
     float* cnt = (float*)(ws + o.cnt);
@@ -478,14 +551,19 @@ static int tim_loop_on(const tclip_problem& p, const TimRows<kIdx>& X, const Row
     float* M = (float*)(ws + o.M);
     float* V = (float*)(ws + o.V);
     float* moved = (float*)(ws + o.moved);
+    float* alphas = values ? (float*)(ws + o.alphas) : nullptr;
+    if (values) launch_sweep_values(st, values, n_values, nullptr, alphas);
     const int tiles_k = (K + kTimTile - 1) / kTimTile, tiles_r = (R + kTimTile - 1) / kTimTile, tiles_d = (D + kTimTile - 1) / kTimTile;
-    // init_weights (tim.py:115-134, :218-238): the class means of the support set; Adam state zero
+    // init_weights (tim.py:115-134, :218-238): the class means of the support set (of the n_real tasks; one copy per value); Adam
+    // state zero
     if (D == K)
-        hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, x_s, y_s, S, K, 0, sup, cnt);
+        hipLaunchKernelGGL(k_support_stats, dim3(K, n_real), dim3(128), (size_t)S * sizeof(int), st, x_s, y_s, S, K, 0, sup, cnt);
     else
-        launch_vis_support_stats(st, RowSrc{x_s.base, x_s.idx, nullptr}, y_s, T, S, K, D, sup, cnt);
-    hipLaunchKernelGGL(k_div_rows, dim3(ew_grid((size_t)TK * D)), dim3(256), 0, st, (const float*)sup, (const float*)cnt,
-                       (size_t)TK * D, D, weights);
+        launch_vis_support_stats(st, RowSrc{x_s.base, x_s.idx, nullptr}, y_s, n_real, S, K, D, sup, cnt);
+    const size_t real_kd = (size_t)n_real * K * D;
+    for (int v = 0; v < n_sweep; v++)
+        hipLaunchKernelGGL(k_div_rows, dim3(ew_grid(real_kd)), dim3(256), 0, st, (const float*)sup, (const float*)cnt, real_kd, D,
+                           weights + (size_t)v * real_kd);
     TCLIP_HIP(hipMemsetAsync(M, 0, (size_t)TK * D * 4, st));
     TCLIP_HIP(hipMemsetAsync(V, 0, (size_t)TK * D * 4, st));
     hipLaunchKernelGGL(k_tim_row_sqnorm<kIdx>, dim3((TR + 3) / 4), dim3(256), 0, st, X, TR, xn);
@@ -497,7 +575,8 @@ static int tim_loop_on(const tclip_problem& p, const TimRows<kIdx>& X, const Row
         hipLaunchKernelGGL(k_tim_softmax, dim3((TR + 3) / 4), dim3(256), 0, st, P, TR, S, Q, K, last ? logits_q : (float*)nullptr,
                            preds);
         hipLaunchKernelGGL(k_tim_marginal, dim3((K + 127) / 128, T), dim3(128), 0, st, (const float*)P, S, Q, K, marg);
-        hipLaunchKernelGGL(k_tim_grad, dim3((TR + 3) / 4), dim3(256), 0, st, P, y_s, (const float*)marg, TR, S, Q, K, loss);
+        hipLaunchKernelGGL(k_tim_grad, dim3((TR + 3) / 4), dim3(256), 0, st, P, y_s, (const float*)marg, TR, S, Q, K, loss,
+                           (const float*)alphas, n_real);
         hipLaunchKernelGGL((k_tim_gemm_mfma<true, kTimTile, kIdx>), dim3(tiles_d, tiles_k, T), dim3(256), 0, st, X, K, (const float*)P,
                            (const float*)nullptr, (const float*)nullptr, 0.0f, dW, cs);
         // Adam's step scalars, in double as torch computes them (torch/optim/adam.py, _single_tensor_adam)
@@ -653,6 +732,48 @@ int tclip_alpha_tim_visual_run_tasks(const tclip_problem* pp, int32_t dim, const
     if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
     return alpha_tim_run_tasks(pp, dim, true, prm, src, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
                                "tclip_alpha_tim_visual_tasks_workspace_bytes");
+}
+
+// ---- ALPHA_TIM for a list of alpha values on the same tasks (see tim_loop_on): dim == 0 is tclip_alpha_tim_run_tasks' problem,
+// dim > 0 tclip_alpha_tim_visual_run_tasks'; prm->alpha_value is not read
+size_t tclip_alpha_tim_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    if (check_problem(p) != TCLIP_OK || check_sweep_dim(dim) != TCLIP_OK) return 0;
+    if (dim > 0 && check_alpha_tim_visual(p, dim) != TCLIP_OK) return 0;
+    if (check_sweep_count(p, n_values) != TCLIP_OK) return 0;
+    return tim_ws(*p, dim ? dim : p->n_class, n_values).total;
+}
+
+int tclip_alpha_tim_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_tim_params* prm, const tclip_task_source* src,
+                                const int64_t* y_s, const double* values, int32_t n_values, float* weights, float* logits_q,
+                                int32_t* preds, float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    if (int rc = check_sweep_dim(dim)) return rc;
+    const bool visual = dim > 0;
+    if (visual)
+        if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
+    if (!task_source_complete(src)) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "ALPHA_TIM on visual features permutes no columns: cols must be NULL");
+    const tclip_problem p = *pp;
+    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM needs iters >= 1 (the accuracy is read from the last iteration's logits)");
+    if (!prm || !y_s || !weights || !logits_q || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM is a few-shot method: n_support must be positive");
+    for (int i = 0; i < 3; i++)
+        if (prm->entropies[i] != TCLIP_TIM_SHANNON && prm->entropies[i] != TCLIP_TIM_ALPHA)
+            return fail(TCLIP_ERR_ARG, "entropies must be TCLIP_TIM_SHANNON or TCLIP_TIM_ALPHA");
+    if (int rc = check_sweep_values(pp, values, n_values)) return rc;
+    const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
+    for (int i = 0; i < n_values; i++)
+        if (any_alpha && !((float)values[i] != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
+    const int D = visual ? dim : p.n_class;
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, D, n_values).total, "tclip_alpha_tim_sweep_tasks_workspace_bytes"))
+        return rc;
+    const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], 0.0f,
+                       prm->entropies[0], prm->entropies[1], prm->entropies[2]};
+    const RowSrc x_s{src->table_s, src->s_idx, src->cols};
+    const TimRows<true> X{src->table_s, src->table_q, src->s_idx, src->q_idx, src->cols, p.n_support, p.n_query, D,
+                          p.n_batches * p.tasks_per_batch};
+    return tim_loop_on(p, X, x_s, prm->lr, prm->temp, loss, false, y_s, weights, logits_q, preds, criterions, (char*)workspace,
+                       (hipStream_t)stream, values, n_values);
 }
 
 size_t tclip_tim_gd_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) { return tclip_tim_gd_workspace_bytes(p, dim); }

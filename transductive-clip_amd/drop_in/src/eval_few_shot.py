@@ -57,6 +57,30 @@ def relabel_indices(y_s, y_q, n_class):
     return torch.stack(cols, 0), torch.stack(ys2, 0), torch.stack(yq2, 0)
 
 
+def checked_sweep_values(args, values, distributed=None):
+    """What a parameter sweep (Evaluator_few_shot.evaluate_sweep, main_features.py `--opts sweep_values "[...]"`) refuses, checked
+    before any device work: a split other than `val` (the sweep file is the validation file), a method without a
+    validation-tuned parameter, an empty list or an element that is not a finite number, and a job under torch.distributed
+    (`distributed`: None asks torch).  Returns the values as a list, every element with the type it was written with."""
+    if getattr(args, 'used_test_set', 'test') != 'val':
+        raise ValueError("sweep_values tunes a parameter on the validation split: used_test_set must be 'val', not {!r}".format(
+            getattr(args, 'used_test_set', 'test')))
+    if getattr(args, 'name_method', None) not in reporting.VAL_PARAM:
+        raise ValueError("method {} has no validation-tuned parameter to sweep (the tunable methods: {})".format(
+            getattr(args, 'name_method', None), ', '.join(sorted(reporting.VAL_PARAM))))
+    if not isinstance(values, (list, tuple)) or len(values) == 0:
+        raise ValueError("sweep_values must be a non-empty list of numbers, e.g. \"[1.0, 2.0, 5.0]\"")
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float('inf'), float('-inf')):
+            raise ValueError("sweep_values must be a list of finite numbers: {!r} is not one".format(v))
+    if distributed is None:
+        distributed = torch.distributed.is_available() and torch.distributed.is_initialized()
+    if distributed:
+        raise RuntimeError("parameter sweeps are single-process: run sweep_values without torch.distributed "
+                           "(one process already solves every value on the same tasks)")
+    return list(values)
+
+
 _METHODS = {'EM_DIRICHLET': EM_DIRICHLET, 'HARD_EM_DIRICHLET': HARD_EM_DIRICHLET, 'PADDLE': PADDLE, 'BDCSPN': BDCSPN,
             'ALPHA_TIM': ALPHA_TIM, 'LAPLACIAN_SHOT': LAPLACIAN_SHOT,
             'TIM-GD': TIM_GD, 'TIM_GD': TIM_GD}      # tim.yaml's name_method is 'TIM-GD'
@@ -72,6 +96,8 @@ class Evaluator_few_shot:
     def run_full_evaluation(self, model, preprocess):
         """eval_few_shot.py:42-74 from saved feature files (see Evaluator_zero_shot.run_full_evaluation): the
         support table is the train split, the query table the `used_test_set` split."""
+        if getattr(self.args, 'sweep_values', None) is not None:
+            return self.run_full_sweep(model)
         dic_s, dic_q = self.extract_and_load_features(model, None, None)
         mean_accuracies, mean_times = self.evaluate_tasks(
             model, dic_s['concat_features'].to('cpu'), dic_s['concat_labels'].long().to('cpu'),
@@ -79,6 +105,28 @@ class Evaluator_few_shot:
         if mean_accuracies is not None:
             self.report_results(mean_accuracies, mean_times)
         return mean_accuracies, mean_times
+
+    def run_full_sweep(self, model, tables=None):
+        """run_full_evaluation with `sweep_values`: what the reference's scripts/opt_parameters.sh does with one process per
+        value.  One evaluate_sweep, then one `val_param<TAB>acc` row per value through report_results, in the order given -
+        the file separate runs with the same seed write, byte for byte.  `tables`: (features_s, labels_s, features_q, labels_q)
+        already loaded (main_features.py), None loads them from the reference's layout."""
+        a = self.args
+        values = checked_sweep_values(a, a.sweep_values)
+        if tables is None:
+            dic_s, dic_q = self.extract_and_load_features(model, None, None)
+            tables = (dic_s['concat_features'].to('cpu'), dic_s['concat_labels'].long().to('cpu'),
+                      dic_q['concat_features'].to('cpu'), dic_q['concat_labels'].long().to('cpu'))
+        accs, mean_time = self.evaluate_sweep(model, *tables, values=values)
+        attr = self._TUNED[a.name_method]
+        saved = a[attr]
+        try:
+            for v, acc in zip(values, accs):
+                a[attr] = v
+                self.report_results(acc, mean_time)
+        finally:
+            a[attr] = saved
+        return accs, mean_time
 
     def extract_and_load_features(self, model, dataset, data_loaders):
         """eval_few_shot.py:91-128, loading only."""
@@ -155,6 +203,62 @@ class Evaluator_few_shot:
             q_all.append(torch.stack(list(SamplerQuery_few_shot(sampler)), 0))
             s_all.append(torch.stack(list(SamplerSupport_few_shot(sampler)), 0))
         return torch.stack(s_all, 0), torch.stack(q_all, 0)
+
+    def evaluate_sweep(self, model, all_features_support, all_labels_support, all_features_query, all_labels_query, values,
+                       indices=None):
+        """evaluate_tasks for every value of the method's validation-tuned parameter (`_TUNED`) on the SAME tasks, in one
+        engine call per method (engine.sweep_*_tasks through the class's run_tables_sweep): the indices are drawn once, with
+        the stream evaluate_tasks draws them with, and relabelled once.  Returns (mean accuracies [len(values)], mean time);
+        entry p is what evaluate_tasks returns with the parameter set to values[p].  The task rows are always read from the
+        tables in place (in_place_support, in_place_loop, materialise_tasks and batches_per_call do not apply; the results
+        are the same bits either way).  When a support set misses a class the tasks cannot be addressed in place
+        (relabel_indices) and the values run one after the other as ordinary evaluate_tasks calls on the same indices."""
+        a = self.args
+        values = checked_sweep_values(a, values)
+        attr = self._TUNED[a.name_method]
+        self.logger.info("=> Runnning a sweep of {} over {} with method {} on {} dataset".format(
+            attr, values, a.name_method, a.used_test_set))
+        lab_s = _as_tensor(all_labels_support).long().cpu()
+        lab_q = _as_tensor(all_labels_query).long().cpu()
+        s_idx, q_idx = self.sample_indices(lab_s.numpy(), lab_q.numpy()) if indices is None else indices
+        n_batches, N, S = s_idx.shape
+        Q = q_idx.shape[2]
+        si, qi = s_idx.reshape(-1, S), q_idx.reshape(-1, Q)
+        y_s, y_q = lab_s[si.reshape(-1)].view(-1, S), lab_q[qi.reshape(-1)].view(-1, Q)
+        W = _as_tensor(all_features_query).shape[1]
+        K = W if a.use_softmax_feature else int(a.n_class)
+        rel = relabel_indices(y_s, y_q, K) if a.use_softmax_feature else (None, y_s, y_q)
+        saved = a[attr]
+        try:
+            if rel is None:
+                accs, times = [], []
+                for v in values:
+                    a[attr] = v
+                    acc, t = self.evaluate_tasks(model, all_features_support, all_labels_support, all_features_query,
+                                                 all_labels_query, indices=(s_idx, q_idx))
+                    accs.append(acc)
+                    times.append(t)
+                return np.asarray(accs), float(np.mean(times))
+            methods = []
+            for v in values:                       # one object per value, built as a run with that value builds it
+                a[attr] = v
+                methods.append(self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file))
+        finally:
+            a[attr] = saved
+        dev = torch.device(self.device)
+        tab_s = _as_tensor(all_features_support).float().to(dev)
+        tab_q = _as_tensor(all_features_query).float().to(dev)
+        cols, y_s, y_q = rel
+        type(methods[0]).run_tables_sweep(methods, table_s=tab_s, s_idx=si, table_q=tab_q, q_idx=qi, cols=cols, y_s=y_s.to(dev),
+                                          y_q=y_q.to(dev), n_batches=n_batches)
+        accs, times = [], []
+        for m in methods:
+            logs = m.get_logs()
+            acc = torch.from_numpy(logs['acc'][:, -1].copy()).view(n_batches, N).float().numpy()      # as sharding.method_parts
+            accs.append(np.asarray([compute_confidence_interval(acc[b])[0] for b in range(n_batches)]).mean())
+            times.append(float(logs['timestamps']))
+        self.last_methods = methods
+        return np.asarray(accs), float(np.mean(times))
 
     def evaluate_tasks(self, model, all_features_support, all_labels_support, all_features_query, all_labels_query,
                        indices=None):

@@ -227,6 +227,33 @@ class FewShotMixin:
     def can_read_rows_in_place_per_step(cls, use_softmax_feature):
         return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_LOOP
 
+    # ---- a sweep of the class's validation-tuned parameter over the same tasks (Evaluator_few_shot.evaluate_sweep) ----------
+    # The four tunable classes name the attribute (SWEEP_ATTR) and split their `_run` into `_banner` and `_finish`, so that
+    # the reference's bookkeeping of one run can follow an engine call that served several objects.
+    SWEEP_ATTR = None
+
+    @classmethod
+    def run_tables_sweep(cls, methods, table_s, s_idx, table_q, q_idx, cols, y_s, y_q, n_batches=1):
+        """run_tables for a list of objects of this class that differ in SWEEP_ATTR only (one per value, built from args as a
+        run with that value builds it): ONE engine call (engine.sweep_*_tasks) solves the tasks for every object's value, then
+        each object keeps its slice and does the bookkeeping of a run of its own - test_acc, criterions, and timestamps from an
+        equal share of the call's wall time.  The task rows are always read from the tables in place."""
+        if cls.SWEEP_ATTR is None:
+            raise NotImplementedError("{} has no validation-tuned parameter to sweep".format(cls.__name__))
+        first = methods[0]
+        first._cuda_device()
+        values = [getattr(m, cls.SWEEP_ATTR) for m in methods]
+        for m in methods:
+            m.logger.info(m._banner())
+        outs, total = first._timed(lambda: first._sweep(values, table_s, s_idx, table_q, q_idx, cols, y_s, n_batches))
+        for i, m in enumerate(methods):
+            m._finish(first._sweep_slice(outs, i), total / len(methods), q_idx.shape[0], y_q, n_batches)
+
+    @staticmethod
+    def _sweep_slice(outs, i):
+        """what the single-value engine call returns for value i, out of the sweep's value-major outputs"""
+        return tuple(o[i] for o in outs)
+
     def run_task(self, task_dic, shot=10):
         y_s, y_q = task_dic['y_s'], task_dic['y_q']
         support, query = task_dic['x_s'], task_dic['x_q']

@@ -16,6 +16,7 @@ from tclip_amd import engine
 class BDCSPN(FewShotMixin, MethodBase):
     LOGGER_NAME = __name__
     IN_PLACE_SUPPORT = ("softmax", "visual")
+    SWEEP_ATTR = "temp"
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)
@@ -62,8 +63,22 @@ class BDCSPN(FewShotMixin, MethodBase):
                                                           temp=self.temp, norm_type=self.norm_type)
         self._run(call, y_q)
 
+    def _sweep(self, values, table_s, s_idx, table_q, q_idx, cols, y_s, n_batches):
+        """run_tables' engine call for a list of temp values (FewShotMixin.run_tables_sweep)"""
+        visual = table_q.shape[1] != self.n_class
+        if visual and cols is not None:
+            raise ValueError("BDCSPN on visual features permutes no columns: cols must be None")
+        return engine.sweep_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, values=values, norm_type=self.norm_type,
+                                         n_class=self.n_class if visual else None)
+
+    def _banner(self):
+        return " ==> Executing BD-CSPN"
+
     def _run(self, call, y_q):
         """the engine call, then the reference's bookkeeping"""
-        (self.prototypes, self.u, self.preds), total = self._execute(" ==> Executing BD-CSPN", call)
+        self._finish(*self._execute(self._banner(), call), None, y_q)
+
+    def _finish(self, result, total, n_task, y_q, n_batches=1):
+        self.prototypes, self.u, self.preds = result
         self.record_convergence(new_time=total, criterions=torch.zeros(1))
         self.compute_acc(y_q)

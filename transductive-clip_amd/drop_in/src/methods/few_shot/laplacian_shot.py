@@ -16,6 +16,7 @@ from tclip_amd import engine
 class LAPLACIAN_SHOT(FewShotMixin, MethodBase):
     LOGGER_NAME = __name__
     IN_PLACE_SUPPORT = ("softmax",)          # run_method refuses visual features, and so does run_tables
+    SWEEP_ATTR = "lmd"
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)
@@ -53,10 +54,28 @@ class LAPLACIAN_SHOT(FewShotMixin, MethodBase):
         self._run(lambda: engine.run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, iters=self.iter, knn=self.knn,
                                                           lmd=self.lmd, norm_type=self.norm_type), q_idx.shape[0], y_q)
 
+    def _sweep(self, values, table_s, s_idx, table_q, q_idx, cols, y_s, n_batches):
+        """run_tables' engine call for a list of lmd values (FewShotMixin.run_tables_sweep); visual features are refused as
+        run_tables refuses them"""
+        if table_q.shape[1] != self.args.num_classes_test:
+            raise NotImplementedError("LAPLACIAN_SHOT here takes probability features (use_softmax_feature: True, feature dimension = n_class)")
+        return engine.sweep_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, iters=self.iter, knn=self.knn,
+                                                 values=values, norm_type=self.norm_type)
+
+    @staticmethod
+    def _sweep_slice(outs, i):
+        # the unary term and the neighbour lists do not depend on lmd: one copy serves every value
+        return outs[0], outs[1], outs[2][i], outs[3][i]
+
+    def _banner(self):
+        return " ==> Executing LAPLACIAN SHOT with lmd = {}".format(self.lmd)
+
     def _run(self, call, n_task, y_q):
         """the engine call, then the reference's bookkeeping"""
-        (self.unary, self.neighbours, self.preds_iter, energies), total = self._execute(
-            " ==> Executing LAPLACIAN SHOT with lmd = {}".format(self.lmd), call)
+        self._finish(*self._execute(self._banner(), call), n_task, y_q)
+
+    def _finish(self, result, total, n_task, y_q, n_batches=1):
+        self.unary, self.neighbours, self.preds_iter, energies = result
         self.preds = self.preds_iter[:, -1, :]
         # accuracy after every update, on the host: means of 75 zeros and ones rounded as the reference's CPU op rounds them
         hit = (self.preds_iter.long().cpu() == y_q.cpu().unsqueeze(1)).float()          # (n_task, iter, Q)

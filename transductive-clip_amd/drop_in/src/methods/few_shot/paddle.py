@@ -18,6 +18,7 @@ class PADDLE(BASE):
     BANNER = "PADDLE"
     ARG_DEFAULTS = {"iter_mm": 0}          # paddle.yaml has no iter_mm
     IN_PLACE_FEATURES = ("softmax", "visual")
+    SWEEP_ATTR = "lambd"
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)
@@ -46,10 +47,22 @@ class PADDLE(BASE):
                                                           n_class=self.args.num_classes_test, iters=self.iter, lambd=self.lambd)
         self._run(call, q_idx.shape[0], y_q)
 
+    def _sweep(self, values, table_s, s_idx, table_q, q_idx, cols, y_s, n_batches):
+        """run_tables' engine call for a list of lambd values (FewShotMixin.run_tables_sweep)"""
+        if not self.args.use_softmax_feature and cols is not None:
+            raise ValueError("PADDLE on visual features permutes no columns: cols must be None")
+        return engine.sweep_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, iters=self.iter, values=values,
+                                         n_class=None if self.args.use_softmax_feature else self.args.num_classes_test)
+
+    def _banner(self):
+        return " ==> Executing PADDLE with LAMBDA = {} and T = {}".format(self.lambd, self.args.T)
+
     def _run(self, call, n_task, y_q):
         """the engine call, then the reference's bookkeeping"""
-        (self.u, self.v, self.w, self.preds), total = self._execute(
-            " ==> Executing PADDLE with LAMBDA = {} and T = {}".format(self.lambd, self.args.T), call)
+        self._finish(*self._execute(self._banner(), call), n_task, y_q)
+
+    def _finish(self, result, total, n_task, y_q, n_batches=1):
+        self.u, self.v, self.w, self.preds = result
         # cumulative wall time per iteration over n_task (paddle.py:214-216)
         self.timestamps += self.spread_time("cumulative", total, self.iter, n_task)
         self.criterions = [0.0] * self.iter       # the reference compares u with a copy of itself (:211-212)

@@ -61,6 +61,7 @@ class ALPHA_TIM(BASE):
     BANNER = "ALPHA_TIM"
     ARG_DEFAULTS = _ARG_DEFAULTS
     IN_PLACE_LOOP = ("softmax",)
+    SWEEP_ATTR = "alpha_value"
     _VISUAL = "ALPHA_TIM here takes probability features (use_softmax_feature: True, feature dimension = n_class)"
 
     def __init__(self, model, device, log_file, args):
@@ -89,10 +90,24 @@ class ALPHA_TIM(BASE):
                                                      entropies=self.entropies, n_batches=n_batches),
                   q_idx.shape[0], y_q, n_batches)
 
+    def _sweep(self, values, table_s, s_idx, table_q, q_idx, cols, y_s, n_batches):
+        """run_tables' engine call for a list of alpha values (FewShotMixin.run_tables_sweep); visual features are refused as
+        run_tables refuses them"""
+        if table_q.shape[1] != self.args.num_classes_test:
+            raise NotImplementedError(self._VISUAL)
+        return engine.sweep_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, iters=self.iter, temp=self.temp, lr=self.lr,
+                                            values=values, loss_weights=self.loss_weights, entropies=self.entropies,
+                                            n_batches=n_batches)
+
+    def _banner(self):
+        return " ==> Executing ALPHA_TIM with ALPHA = {} and T = {}".format(self.alpha_value, self.args.T)
+
     def _run(self, call, n_task, y_q, n_batches):
         """the engine call, then the reference's bookkeeping"""
-        (self.weights, self.logits_q, self.preds, crit), total = self._execute(
-            " ==> Executing ALPHA_TIM with ALPHA = {} and T = {}".format(self.alpha_value, self.args.T), call)
+        self._finish(*self._execute(self._banner(), call), n_task, y_q, n_batches)
+
+    def _finish(self, result, total, n_task, y_q, n_batches=1):
+        self.weights, self.logits_q, self.preds, crit = result
         # cumulative wall time per iteration over n_task (tim.py:317-319)
         self.timestamps += self.spread_time("cumulative", total, self.iter, n_task)
         crit = crit.cpu().numpy()                        # (n_batches, iter): mean_{task,class} ||w_old - w||

@@ -36,6 +36,10 @@ the (tasks, support, width) and (tasks, query, width) tensors and, for BDCSPN, w
 `in_place_loop True` (not a default: absent unless given) does the same for TIM-GD (both feature kinds) and ALPHA_TIM (softmax
 features), which read their task rows in every Adam step, not once: same results without the two tensors; what the indirection
 costs in time is measured in DESIGN.md 8j.
+`sweep_values "[1.0, 2.0, 5.0]"` (few-shot, `used_test_set val`, one of the four tunable methods; single process) tunes in one
+run: the tasks are drawn once, every value of the method's tuned parameter is solved on them in one engine call, and one
+`val_param<TAB>acc` row per value is appended to the validation file, in the order given - the file that one run per value with
+the same seed writes.  Each element keeps the type it is written with (`5` and `5.0` are different rows).
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse
@@ -112,6 +116,12 @@ def main(argv=None, keep_process_group=False):
     """keep_process_group: a caller that runs several evaluations in one process destroys the group itself"""
     ns, args = parse_args(argv)
     dist_on = "RANK" in os.environ
+    sweep = getattr(args, "sweep_values", None)
+    if sweep is not None:                      # refused here, before the device is touched
+        from src.eval_few_shot import checked_sweep_values
+        if int(args.shots) < 1:
+            raise ValueError("sweep_values tunes a few-shot method: shots must be positive")
+        sweep = checked_sweep_values(args, sweep, distributed=True if dist_on else None)
     local_rank = int(os.environ.get("LOCAL_RANK", args.device))
     if args.seed is not None:                  # main.py:42-46
         random.seed(args.seed)
@@ -146,6 +156,14 @@ def main(argv=None, keep_process_group=False):
         if not args.use_softmax_feature:       # visual features: the class count comes from the labels of both splits
             args.num_classes_test = args.n_class = max(args.num_classes_test, int(labels_s.max()) + 1)
         ev = Evaluator_few_shot(device=device, args=args, log_file=None)
+        if sweep is not None:
+            accs, t = ev.run_full_sweep(None, (feats_s, labels_s, feats_q, labels_q))
+            path = os.path.join(ns.results_root, "results_few_shot", "val", str(args.dataset), "{}_s{}.txt".format(
+                args.name_method + ("_softmax" if args.use_softmax_feature else "_visual"), args.shots))
+            for v, acc in zip(sweep, accs):
+                print(f"{reporting.VAL_PARAM[args.name_method]} = {v}: mean accuracy {100 * float(acc):.2f} %")
+            print(f"mean time/task statistic {t:.3e} s  -> {path}")
+            return accs, t, path
         acc, t = ev.evaluate_tasks(None, feats_s, labels_s, feats_q, labels_q)
     else:
         from src.eval_zero_shot import Evaluator_zero_shot

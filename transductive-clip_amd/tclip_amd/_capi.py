@@ -90,6 +90,22 @@ _SIGNATURES = {
     "tclip_laplacian_shot_visual_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P,
                                                              ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P, _P,
                                                              ctypes.c_size_t, _P]),
+    # value sweeps: (problem, dim, n_values) / (problem, dim, [params,] source, y_s, ..., values, n_values, ..., outputs, workspace)
+    "tclip_paddle_sweep_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_int32]),
+    "tclip_paddle_sweep_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P,
+                                                ctypes.POINTER(ctypes.c_double), ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_bdcspn_sweep_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_int32]),
+    "tclip_bdcspn_sweep_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P,
+                                                ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P,
+                                                ctypes.c_size_t, _P]),
+    "tclip_laplacian_shot_sweep_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_int32]),
+    "tclip_laplacian_shot_sweep_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TaskSource), _P,
+                                                        ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_int32,
+                                                        _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "tclip_alpha_tim_sweep_tasks_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.c_int32]),
+    "tclip_alpha_tim_sweep_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.c_int32, ctypes.POINTER(TimParams),
+                                                   ctypes.POINTER(TaskSource), _P, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
+                                                   _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_hard_kmeans_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_hard_kmeans_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "tclip_kl_kmeans_run": (ctypes.c_int, [ctypes.POINTER(Problem), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),

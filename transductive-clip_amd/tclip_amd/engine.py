@@ -632,6 +632,125 @@ def run_bdcspn_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, tem
     return _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, temp, norm_type, visual=True)
 
 
+# ---- value sweeps: the four tunable few-shot methods for a list of values on the same tasks (tclip_*_sweep_tasks) ----------
+def _sweep_values(values, name):
+    """the list of values as a C double array; ValueError for an empty list or a value that is not a finite number - before
+    anything touches the device"""
+    import math
+    try:
+        vals = [float(v) for v in values]
+    except TypeError:
+        raise ValueError(f"{name} must be a non-empty list of finite numbers")
+    if not vals or not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{name} must be a non-empty list of finite numbers")
+    return (ctypes.c_double * len(vals))(*vals), len(vals)
+
+
+def _sweep_n_class(table_q, n_class):
+    """(K, visual): n_class=None is the probability form (K = the tables' width), a number the visual one"""
+    if n_class is None:
+        return (table_q.shape[1] if table_q.dim() == 2 else 0), False
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    return n_class, True
+
+
+def _sweep_call(stem, dev, problem, D, visual, P):
+    dim = ctypes.c_int32(D if visual else 0)
+    return _Call(dev, problem, stem + "_sweep_tasks_workspace_bytes", dim, ctypes.c_int32(P)), dim
+
+
+def sweep_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, values, n_class=None):
+    """run_paddle_tasks (n_class=None) / run_paddle_visual_tasks (n_class given; cols must be None) for every lambd of `values`
+    in one call (tclip_paddle_sweep_tasks) -> (u (P,T,Q,K), v (P,T,K), w (P,T,K,D), preds (P,T,Q) i32): slice i holds the
+    bits of the single-value call with lambd = values[i].  The support class sums are taken once.  Not synchronised."""
+    vals, P = _sweep_values(values, "values")
+    K, visual = _sweep_n_class(table_q, n_class)
+    if visual and cols is not None:
+        raise ValueError("PADDLE on visual features permutes no columns: cols must be None")
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "PADDLE")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    c, dim = _sweep_call("tclip_paddle", dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), D, visual, P)
+    u, v, w, preds = c.empty(P, T, Q, K), c.empty(P, T, K), c.empty(P, T, K, D), c.empty(P, T, Q, dtype=torch.int32)
+    c.launch("tclip_paddle_sweep_tasks", lambda ws, n, st: (dim, ctypes.byref(src), _ptr(y_s), vals, ctypes.c_int32(P), _ptr(u),
+                                                            _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
+    return u, v, w, preds
+
+
+def sweep_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, values, norm_type="L2N", n_class=None):
+    """run_bdcspn_tasks (n_class=None) / run_bdcspn_visual_tasks (n_class given) for every temp of `values` in one call
+    (tclip_bdcspn_sweep_tasks) -> (prototypes (P,T,K,D), u (P,T,Q,K), preds (P,T,Q) i32), slice i the bits of the single-value
+    call with temp = values[i].  Everything up to the augmented set runs once.  Not synchronised."""
+    vals, P = _sweep_values(values, "values")
+    if norm_type not in NORM_TYPES:
+        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
+    K, visual = _sweep_n_class(table_q, n_class)
+    if visual and cols is not None:
+        raise ValueError("BDCSPN on visual features permutes no columns: cols must be None")
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "BDCSPN")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    c, dim = _sweep_call("tclip_bdcspn", dev, _capi.Problem(1, T, Q, K, S, 1, 1, 0, 0), D, visual, P)
+    prototypes, u, preds = c.empty(P, T, K, D), c.empty(P, T, Q, K), c.empty(P, T, Q, dtype=torch.int32)
+    c.launch("tclip_bdcspn_sweep_tasks", lambda ws, n, st: (dim, ctypes.byref(src), _ptr(y_s), vals, ctypes.c_int32(P),
+                                                            ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u),
+                                                            _ptr(preds), ws, n, st))
+    return prototypes, u, preds
+
+
+def sweep_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, knn, values, norm_type="L2N", n_class=None):
+    """run_laplacian_shot_tasks (n_class=None) / run_laplacian_shot_visual_tasks (n_class given) for every lmd of `values` in one
+    call (tclip_laplacian_shot_sweep_tasks) -> (unary (T,Q,K) and neighbours (T,Q,knn-1) i32, which no lmd enters, once;
+    preds_iter (P,T,iters,Q) i32, energies (P,T,iters) f64, slice i the bits of the single-value call with lmd = values[i]).
+    Normalisation, prototypes, unary term and kNN graph run once per task, the updates on a grid of (task, value).  Not
+    synchronised."""
+    vals, P = _sweep_values(values, "values")
+    _check_lshot_norm(norm_type)
+    K, visual = _sweep_n_class(table_q, n_class)
+    if visual and cols is not None:
+        raise ValueError("LAPLACIAN_SHOT on visual features permutes no columns: cols must be None")
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "LAPLACIAN_SHOT")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    c, dim = _sweep_call("tclip_laplacian_shot", dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), D, visual, P)
+    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
+    preds_iter, energies = c.empty(P, T, max(iters, 1), Q, dtype=torch.int32), c.empty(P, T, max(iters, 1), dtype=torch.float64)
+    c.launch("tclip_laplacian_shot_sweep_tasks",
+             lambda ws, n, st: (dim, ctypes.byref(src), _ptr(y_s), ctypes.c_int32(int(knn)), vals, ctypes.c_int32(P),
+                                ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies),
+                                ws, n, st))
+    return unary, nbr, preds_iter, energies
+
+
+def sweep_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, temp, lr, values, loss_weights=(1.0, 1.0, 1.0),
+                          entropies=("Shannon", "Alpha", "Alpha"), n_batches=1, n_class=None):
+    """run_alpha_tim_tasks (n_class=None) / run_alpha_tim_visual_tasks (n_class given) for every alpha_value of `values` in one
+    call (tclip_alpha_tim_sweep_tasks) -> (weights (P,T,K,D), logits_q (P,T,Q,K), preds (P,T,Q) i32, criterions
+    (P,n_batches,iters)), slice i the bits of the single-value call with alpha_value = values[i].  The Adam loop runs over
+    P * T solves in one set of launches per step; solve (i, t) reads the rows of task t in place.  Not synchronised."""
+    vals, P = _sweep_values(values, "values")
+    _check_entropies(entropies)
+    K, visual = _sweep_n_class(table_q, n_class)
+    if visual and cols is not None:
+        raise ValueError("ALPHA_TIM on visual features permutes no columns: cols must be None")
+    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "ALPHA_TIM")
+    dev, D = table_q.device, table_q.shape[1]
+    (T, Q), S = q_idx.shape, s_idx.shape[1]
+    if T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+    prm = _capi.TimParams(float(lr), float(temp), 0.0, (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
+                          (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
+    c, dim = _sweep_call("tclip_alpha_tim", dev, _capi.Problem(n_batches, T // n_batches, Q, K, S, iters, 1, 0, 0), D, visual, P)
+    weights, logits_q = c.empty(P, T, K, D), c.empty(P, T, Q, K)
+    preds, crit = c.empty(P, T, Q, dtype=torch.int32), c.empty(P, n_batches, iters)
+    c.launch("tclip_alpha_tim_sweep_tasks",
+             lambda ws, n, st: (dim, ctypes.byref(prm), ctypes.byref(src), _ptr(y_s), vals, ctypes.c_int32(P), _ptr(weights),
+                                _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
+    return weights, logits_q, preds, crit
+
+
 MATCHING = ("host", "device")
 
 
