@@ -50,9 +50,10 @@ def reference_init(x_q, text, T):
     return u
 
 
-def reference_step(method, query, u, w=None, v=None, T=30.0, lambd=0, eps=1e-15):
+def reference_step(method, query, u, w=None, v=None, T=30.0, lambd=0, eps=1e-15, log=torch.log):
     """One iteration of the reference's loop from u (and the previous w / v), torch CPU: returns (u, w, v).  w=None: the w_init
-    of SOFT_KMEANS / EM_GAUSSIAN first.  HARD_KMEANS returns u one-hot."""
+    of SOFT_KMEANS / EM_GAUSSIAN first.  HARD_KMEANS returns u one-hot.  `log`: the logarithm of EM_GAUSSIAN's v_update
+    (helpers/restated.restated_log() is the reference host's on every host); float64 inputs run the step in float64."""
     if method != "hard_kmeans" and w is None:
         num = (query.unsqueeze(2) * u.unsqueeze(3)).sum(1)
         den = u.sum(1).clamp(min=eps)
@@ -73,9 +74,9 @@ def reference_step(method, query, u, w=None, v=None, T=30.0, lambd=0, eps=1e-15)
         u.scatter_(2, labels.unsqueeze(-1), 1.0)
     elif method == "em_gaussian":
         if v is None:
-            v = torch.zeros(u.shape[0], u.shape[2])
+            v = torch.zeros(u.shape[0], u.shape[2], dtype=u.dtype)
         u = (T * (-1 / 2 * logits) + lambd * v.unsqueeze(1) / query.size(1)).softmax(2)
-        v = torch.log(u.sum(1) / u.size(1) + eps) + 1
+        v = log(u.sum(1) / u.size(1) + eps) + 1
     else:
         u = (T * (-1 / 2 * logits)).softmax(2)
     return u, w, v

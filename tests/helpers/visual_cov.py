@@ -49,9 +49,9 @@ def step(query, u, v, w, s, lambd, log=torch.log):
 
 
 def run(query, u0, iters, lambd, log=torch.log):
-    """The whole loop from u0: (u, v, w, s, preds)."""
+    """The whole loop from u0: (u, v, w, s, preds); in float64 when its inputs are."""
     u = u0.clone()
-    v = torch.zeros(u0.shape[0], u0.shape[2])
+    v = torch.zeros(u0.shape[0], u0.shape[2], dtype=u0.dtype)
     w, s = init(query, u)
     for _ in range(iters):
         u, v, w, s = step(query, u, v, w, s, lambd, log)

@@ -48,8 +48,8 @@ def random_tasks(N, K, D, shots, seed, n_query=75, scale=1.0):
     return x_s, y_s, x_q
 
 
-def one_hot(y, K):
-    return torch.zeros(y.shape + (K,)).scatter_(-1, y.unsqueeze(-1), 1.0)
+def one_hot(y, K, dtype=torch.float32):
+    return torch.zeros(y.shape + (K,), dtype=dtype).scatter_(-1, y.unsqueeze(-1), 1.0)
 
 
 def support_sums(support, y_s, K):
@@ -58,20 +58,21 @@ def support_sums(support, y_s, K):
     return (h.unsqueeze(-1) * support.unsqueeze(2)).sum(1), h.sum(1)
 
 
-def paddle_step(support, query, y_s, K, lambd, w=None, v=None, eps=1e-15):
+def paddle_step(support, query, y_s, K, lambd, w=None, v=None, eps=1e-15, log=torch.log):
     """One iteration of PADDLE's loop (u_update, v_update, w_update) from w and v, torch CPU; w=None: init_w first, v=None: zeros.
-    Returns (u, v, w)."""
-    h = one_hot(y_s, K)
+    Returns (u, v, w).  `log`: the logarithm of the v_update (helpers/restated.restated_log() is the reference host's on every
+    host); float64 rows run the step in float64."""
+    h = one_hot(y_s, K, query.dtype)
     if w is None:
         counts = h.sum(1).unsqueeze(-1)
         w = (h.unsqueeze(-1) * support.unsqueeze(2)).sum(1).div_(counts)
     if v is None:
-        v = torch.zeros(query.shape[0], K)
+        v = torch.zeros(query.shape[0], K, dtype=query.dtype)
     diff = w.unsqueeze(1) - query.unsqueeze(2)
     logits = -1 / 2 * diff.square_().sum(dim=-1)
     del diff
     u = (logits + lambd * v.unsqueeze(1) / query.size(1)).softmax(2)
-    v = torch.log(u.sum(1) / u.size(1) + eps) + 1
+    v = log(u.sum(1) / u.size(1) + eps) + 1
     num = (query.unsqueeze(2) * u.unsqueeze(3)).sum(1)
     den = u.sum(1)
     num.add_((support.unsqueeze(2) * h.unsqueeze(3)).sum(1))
@@ -92,7 +93,7 @@ def _get_logits(w, samples):
 
 def bdcspn_pass(support, query, y_s, K, temp, norm_type):
     """BD-CSPN's run_task from raw rows: normalisation, prototype rectification task by task, prediction.
-    Returns (rectified prototypes (N,K,D), u (N,Q,K), preds (N,Q))."""
+    Returns (rectified prototypes (N,K,D), u (N,Q,K), preds (N,Q)); in float64 when the rows are."""
     mean = support.mean(1).unsqueeze(1)
     if norm_type == "CL2N":
         support = support - mean
@@ -103,8 +104,8 @@ def bdcspn_pass(support, query, y_s, K, temp, norm_type):
         support = support / support.norm(p=2, dim=2, keepdim=True)
         query = query / query.norm(p=2, dim=2, keepdim=True)
     n_task, _, D = query.shape
-    prototypes = torch.zeros(n_task, K, D)
-    h = one_hot(y_s, K)
+    prototypes = torch.zeros(n_task, K, D, dtype=query.dtype)
+    h = one_hot(y_s, K, query.dtype)
     counts = h.sum(1).unsqueeze(-1)
     init = (h.unsqueeze(-1) * support.unsqueeze(2)).sum(1).div_(counts)
     for j in range(n_task):

@@ -113,6 +113,24 @@ def test_bdcspn_in_place_equals_dense_visual_features(D, K, S, Q):
             assert same(a, b), (name, norm_type)
 
 
+@pytest.mark.parametrize("Q", [17, 257])
+@pytest.mark.parametrize("D,K,S", [(40, 24, 49), (520, 10, 21)])
+def test_bdcspn_in_place_equals_dense_visual_features_off_75_queries(D, K, S, Q):
+    """a last query group of k_vis_dist with a single working wavefront (17 query rows) and the second level of k_vis_mstats's
+    cascade over the S + Q augmented rows (257), on one-chunk and two-chunk rows"""
+    from tclip_amd import engine
+    table_q, q_idx, table_s, s_idx, y_s, _, x_q, x_s = _inputs(D, K, S, Q, False, (D * 1009 + K * 13 + S) * 7 + Q)
+    assert x_q.shape == (T, Q, D)
+    for norm_type in ("UN", "L2N", "CL2N"):
+        dense = engine.run_bdcspn_visual(x_q, x_s, y_s.to(DEV), n_class=K, temp=15.0, norm_type=norm_type)
+        tasks = engine.run_bdcspn_visual_tasks(table_q, q_idx.to(DEV), table_s, s_idx, y_s, n_class=K, temp=15.0, norm_type=norm_type)
+        assert tasks[1].shape == (T, Q, K)
+        for name, a, b in zip(("prototypes", "u", "preds"), tasks, dense):
+            assert same(a, b), (name, norm_type)
+    if S >= K:
+        assert bool(torch.isfinite(dense[0]).all())
+
+
 LSHOT_OUT = ("unary", "neighbours", "preds_iter", "energies")
 
 

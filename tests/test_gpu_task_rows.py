@@ -192,6 +192,30 @@ def test_paddle_in_place_equals_dense_visual_features(K, D, s_kind):
         assert bool(torch.isfinite(dense[2]).all())
 
 
+@pytest.mark.parametrize("Q", [17, 257])
+@pytest.mark.parametrize("K,D", [(24, 40), (10, 520)])
+def test_paddle_in_place_equals_dense_visual_features_off_75_queries(K, D, Q):
+    """the query rows are gathered once into the workspace: one query group of k_vis_dist with a single working wavefront (17)
+    and the second level of k_vis_mstats's cascade (257), with k_vis_mstats and k_vis_mstats_one (K = 24) and rows of two chunks
+    (D = 520)"""
+    from tclip_amd import engine
+    T, S, rows = 2, 2 * K + 1, 300
+    gen = torch.Generator().manual_seed((K * 1009 + D) * 13 + Q)
+    table_s = (torch.randn(rows, D, generator=gen) * (2.0 / D ** 0.5)).to(DEV)
+    table_q = (torch.randn(rows, D, generator=gen) * (2.0 / D ** 0.5)).to(DEV)
+    s_idx, q_idx = _shuffled_repeated(T, S, rows, gen), torch.randint(0, rows, (T, Q), generator=gen)
+    y_s = _labels(T, S, K, gen)
+    x_s, x_q = engine.gather_task_rows(table_s, s_idx), engine.gather_task_rows(table_q, q_idx)
+    dense = engine.run_paddle_visual(x_q, x_s, y_s.to(DEV), n_class=K, iters=3, lambd=7.5)
+    tasks = engine.run_paddle_visual_tasks(table_q, q_idx.to(DEV), table_s, s_idx, y_s, n_class=K, iters=3, lambd=7.5)
+    for name, a, b in zip("uvw", tasks, dense):
+        assert a.shape == b.shape and same(a, b), name
+    assert tasks[0].shape == (T, Q, K) and torch.equal(tasks[3], dense[3])
+    assert bool(torch.isfinite(dense[2]).all())
+    u = dense[0]
+    assert bool(((u > 1e-6) & (u < 1 - 1e-6)).any())
+
+
 def test_paddle_tasks_reject_bad_input():
     from tclip_amd import engine
     K, S, rows = 5, 10, 30
