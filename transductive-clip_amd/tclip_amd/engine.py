@@ -3,7 +3,13 @@
 PyTorch is plumbing here (device memory through its caching allocator, the current HIP stream);
 every number is produced by libtclip.so.  One call handles n_batches independent reference
 batches (the MM stop test couples the tasks of one batch, so the batch is the
-unit of parity and of multi-GPU sharding)."""
+unit of parity and of multi-GPU sharding).
+
+The few-shot methods follow the host loops of the library: one runner per method (`_paddle`, `_bdcspn`, `_laplacian_shot`,
+`_alpha_tim`, `_tim_gd`, `_em_dirichlet`) holds the method's Problem, outputs and C argument tuple once, and is fed by a `_Rows`
+that says where the task rows come from - dense tensors or feature tables.  The public run_* / sweep_* functions check their
+arguments, build the `_Rows` and make one runner call."""
+import collections
 import ctypes
 
 import torch
@@ -71,26 +77,93 @@ def _support(x_q, x_s, y_s):
     return x_s, y_s
 
 
+def _check_n_class(n_class):
+    n_class = int(n_class)
+    if not 2 <= n_class <= 1024:
+        raise ValueError("n_class must be in 2..1024")
+    return n_class
+
+
+def _support_visual(x_q, x_s, y_s, n_class):
+    """_support for D-wide rows: the width of x_s is checked against D, the labels against n_class (on the device: one
+    reduction, its result read back, so that no kernel ever sees a label outside 0..n_class-1)."""
+    x_s, y_s = _support(x_q, x_s, y_s.to(x_q.device))
+    n_class = _check_n_class(n_class)
+    if y_s.numel() and not bool(((y_s >= 0) & (y_s < n_class)).all()):
+        raise ValueError(f"y_s holds a label outside 0..{n_class - 1}")
+    return x_s, y_s, n_class
+
+
+# ---- where the task rows of a few-shot call come from ------------------------------------------------------------------------
+# dev, the task shape (T, Q, S, D: S = 0 without a support set, D the row width), y_s (T,S) int64 on dev or None, `args`: the
+# leading C arguments that name the rows, `run` / `ws_query`: the suffixes of the entry and of its workspace query, `keep`: every
+# prepared tensor and the struct `args` points into - whoever holds the _Rows keeps them alive until the launch has happened.
+_Rows = collections.namedtuple("_Rows", "dev T Q S D y_s args run ws_query keep")
+
+
+def _dense_rows(x_q, x_s=None, y_s=None):
+    """The rows of dense tensors: x_q (T,Q,D) as `_query`, x_s (T,S,D) and y_s as `_support` / `_support_visual` return them."""
+    T, Q, D = x_q.shape
+    return _Rows(x_q.device, T, Q, x_s.shape[1] if x_s is not None else 0, D, y_s, (_ptr(x_q), _ptr(x_s)), "_run",
+                 "_workspace_bytes", (x_q, x_s))
+
+
+def _table_rows(table_q, q_idx, table_s, s_idx, y_s, cols):
+    """The rows read in place from the feature tables (struct tclip_task_source): checked tensors on one device, table_s None
+    without a support set (S = 0), cols None without a column permutation."""
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    src = _capi.TaskSource(ptr(table_q), ptr(q_idx), ptr(table_s), ptr(s_idx), ptr(cols))
+    T, Q = q_idx.shape
+    return _Rows(table_q.device, T, Q, s_idx.shape[1] if table_s is not None else 0, table_q.shape[1], y_s, (ctypes.byref(src),),
+                 "_run_tasks", "_tasks_workspace_bytes", (src, table_q, q_idx, table_s, s_idx, cols))
+
+
+def _rows_call(stem, rows, problem, visual, values=None, infix="_visual"):
+    """The call of a few-shot method on `rows` -> (call, entry, dim, P).  A single-value call: the entry and the workspace query
+    are stem [+ infix on visual features] + the suffixes of `rows`, dim = (D,) on visual features and () on probability ones,
+    P = ().  With `values` (the array of `_sweep_values`): stem + _sweep_tasks, dim = (D or 0,) always, P = (n_values,), the
+    leading dimension of the outputs that depend on the value."""
+    if values is None:
+        dim = (ctypes.c_int32(rows.D),) if visual else ()
+        stem += infix if visual else ""
+        return _Call(rows.dev, problem, stem + rows.ws_query, *dim), stem + rows.run, dim, ()
+    dim = (ctypes.c_int32(rows.D if visual else 0),)
+    call = _Call(rows.dev, problem, stem + "_sweep_tasks_workspace_bytes", *dim, ctypes.c_int32(len(values)))
+    return call, stem + "_sweep_tasks", dim, (len(values),)
+
+
+def _swept(values, ctype=None, scalar=None):
+    """what stands in a method's C tuple where its tunable parameter goes: (values, n_values) of a sweep, or the scalar as a
+    `ctype` (nothing for ALPHA_TIM, whose alpha_value travels in its struct)"""
+    if values is not None:
+        return values, ctypes.c_int32(len(values))
+    return (ctype(float(scalar)),) if ctype is not None else ()
+
+
+def _em_dirichlet(rows, K, n_batches, iters, iter_mm, lambd, hard):
+    """EM-Dirichlet on `rows`, zero-shot (S = 0) or few-shot: tclip_em_dirichlet_run / tclip_em_dirichlet_run_tasks"""
+    T, Q, dev = rows.T, rows.Q, rows.dev
+    c = _Call(dev, _capi.Problem(n_batches, T // n_batches, Q, K, rows.S, iters, iter_mm, int(lambd), int(bool(hard))),
+              "tclip_workspace_bytes")
+    u, v, alpha, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
+    crit = torch.zeros(n_batches, max(iters, 1), device=dev)[:, :iters].contiguous()
+    mm = torch.zeros(n_batches, max(iters, 1), dtype=torch.int32, device=dev)[:, :iters].contiguous()
+    c.launch("tclip_em_dirichlet" + rows.run, lambda ws, n, st: (*rows.args, _ptr(rows.y_s), _ptr(u), _ptr(v), _ptr(alpha),
+                                                                 _ptr(preds), _ptr(crit), _ptr(mm), ws, n, st))
+    return EMDirichletResult(u=u, v=v, alpha=alpha, preds=preds, criterions=crit, mm_iters=mm)
+
+
 def run_em_dirichlet(x_q, x_s=None, y_s=None, *, n_batches=1, iters, iter_mm=1000, lambd, hard=False):
     """x_q (T,Q,K) f32 cuda with T = n_batches * tasks_per_batch; x_s (T,S,K), y_s (T,S) for few-shot.
 
     Returns EMDirichletResult of cuda tensors; nothing is synchronised."""
     x_q = _query(x_q)
-    T, Q, K = x_q.shape
+    T, _, K = x_q.shape
     if T % n_batches:
         raise ValueError("number of tasks must be a multiple of n_batches")
-    S = 0
     if x_s is not None:
         x_s, y_s = _support(x_q, x_s, y_s.to(x_q.device))
-        S = x_s.shape[1]
-    c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, S, iters, iter_mm, int(lambd), int(bool(hard))),
-              "tclip_workspace_bytes")
-    u, v, alpha, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
-    crit = torch.zeros(n_batches, max(iters, 1), device=x_q.device)[:, :iters].contiguous()
-    mm = torch.zeros(n_batches, max(iters, 1), dtype=torch.int32, device=x_q.device)[:, :iters].contiguous()
-    c.launch("tclip_em_dirichlet_run", lambda ws, n, st: (_ptr(x_q), _ptr(x_s), _ptr(y_s), _ptr(u), _ptr(v), _ptr(alpha),
-                                                          _ptr(preds), _ptr(crit), _ptr(mm), ws, n, st))
-    return EMDirichletResult(u=u, v=v, alpha=alpha, preds=preds, criterions=crit, mm_iters=mm)
+    return _em_dirichlet(_dense_rows(x_q, x_s, y_s), K, n_batches, iters, iter_mm, lambd, hard)
 
 
 def _check_on_device(idx, n_rows, cols, n_class, name):
@@ -128,14 +201,14 @@ def run_em_dirichlet_tasks(table_q, q_idx, table_s=None, s_idx=None, y_s=None, c
     table_q (rows,K) f32 cuda, q_idx (T,Q) rows of it; few-shot: table_s, s_idx (T,S), y_s (T,S) the re-indexed support
     labels; cols (T,K) the per-task column permutation of Tasks_Generator_few_shot.get_task or None.  No (T,S,K) /
     (T,Q,K) tensor is built; the results are those of run_em_dirichlet on the materialised tensors, bit for bit."""
+    # the checks of `_task_tables` in this entry's own order and words (it has no label check, and its support set may be absent)
     _require_cuda(table_q, "table_q")
     table_q = table_q.contiguous().float()
     dev, K = table_q.device, table_q.shape[1]
     q_idx = _index_tensor(q_idx, table_q.shape[0], dev, "q_idx")
-    T, Q = q_idx.shape
+    T, _ = q_idx.shape
     if T % n_batches:
         raise ValueError("number of tasks must be a multiple of n_batches")
-    S = 0
     if table_s is not None:
         _require_cuda(table_s, "table_s")
         table_s = table_s.contiguous().float()
@@ -152,15 +225,7 @@ def run_em_dirichlet_tasks(table_q, q_idx, table_s=None, s_idx=None, y_s=None, c
         cols = cols.to(dev).contiguous()
         if on_device:
             _check_on_device(None, 1, cols, K, "cols")
-    c = _Call(dev, _capi.Problem(n_batches, T // n_batches, Q, K, S, iters, iter_mm, int(lambd), int(bool(hard))), "tclip_workspace_bytes")
-    u, v, alpha, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, K), c.empty(T, Q, dtype=torch.int32)
-    crit = torch.zeros(n_batches, max(iters, 1), device=dev)[:, :iters].contiguous()
-    mm = torch.zeros(n_batches, max(iters, 1), dtype=torch.int32, device=dev)[:, :iters].contiguous()
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-    src = _capi.TaskSource(ptr(table_q), ptr(q_idx), ptr(table_s), ptr(s_idx), ptr(cols))
-    c.launch("tclip_em_dirichlet_run_tasks", lambda ws, n, st: (ctypes.byref(src), _ptr(y_s), _ptr(u), _ptr(v), _ptr(alpha),
-                                                                _ptr(preds), _ptr(crit), _ptr(mm), ws, n, st))
-    return EMDirichletResult(u=u, v=v, alpha=alpha, preds=preds, criterions=crit, mm_iters=mm)
+    return _em_dirichlet(_table_rows(table_q, q_idx, table_s, s_idx, y_s, cols), K, n_batches, iters, iter_mm, lambd, hard)
 
 
 def _cols_tensor(cols, T, W, dev):
@@ -262,30 +327,10 @@ def run_hard_kmeans(x_q, *, iters, n_batches=1):
     return _run_hard("tclip_hard_kmeans_run", x_q, iters, n_batches)
 
 
-def _run_paddle(x_q, x_s, y_s, K, iters, lambd, visual):
-    """PADDLE on rows of D elements: D = K and tclip_paddle_run for probability features, tclip_paddle_visual_run with D as its
-    first argument for visual ones."""
-    T, Q, D = x_q.shape
-    stem, dim = ("tclip_paddle_visual", (ctypes.c_int32(D),)) if visual else ("tclip_paddle", ())
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), stem + "_workspace_bytes", *dim)
-    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
-    c.launch(stem + "_run", lambda ws, n, st: (*dim, _ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_float(float(lambd)), _ptr(u),
-                                               _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
-    return u, v, w, preds
-
-
-def run_paddle(x_q, x_s, y_s, *, iters, lambd):
-    """PADDLE: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda ->
-    (u (T,Q,K), v (T,K), w (T,K,K), preds (T,Q) i32), cuda, not synchronised."""
-    x_q = _query(x_q)
-    x_s, y_s = _support(x_q, x_s, y_s)
-    return _run_paddle(x_q, x_s, y_s, x_q.shape[2], iters, lambd, visual=False)
-
-
 def _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, method):
-    """What the entries fed from the feature tables share: the tables as contiguous f32 (rows,D) tensors of one width on one
-    device, the index tensors and cols range-checked (IndexError) and on that device, the labels checked against K.
-    -> (table_q, q_idx, table_s, s_idx, y_s, cols, struct tclip_task_source)"""
+    """What the few-shot entries fed from the feature tables share: the tables as contiguous f32 (rows,D) tensors of one width on
+    one device, the index tensors and cols range-checked (IndexError) and on that device, the labels checked against K.
+    -> their `_Rows`"""
     _require_cuda(table_q, "table_q")
     _require_cuda(table_s, "table_s")
     if table_q.dim() != 2 or table_s.dim() != 2 or q_idx.dim() != 2 or s_idx.dim() != 2:
@@ -307,22 +352,59 @@ def _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, method):
         raise ValueError(f"y_s holds a label outside 0..{K - 1}")
     if cols is not None:
         cols = _cols_tensor(cols, T, D, dev)
-    src = _capi.TaskSource(table_q.data_ptr(), q_idx.data_ptr(), table_s.data_ptr(), s_idx.data_ptr(),
-                           cols.data_ptr() if cols is not None else None)
-    return table_q, q_idx, table_s, s_idx, y_s, cols, src
+    return _table_rows(table_q, q_idx, table_s, s_idx, y_s, cols)
 
 
-def _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, lambd, visual):
-    """PADDLE from the feature tables on rows of D elements (tclip_paddle_run_tasks / tclip_paddle_visual_run_tasks)"""
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "PADDLE")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    stem, dim = ("tclip_paddle_visual", (ctypes.c_int32(D),)) if visual else ("tclip_paddle", ())
-    c = _Call(dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
-    u, v, w, preds = c.empty(T, Q, K), c.empty(T, K), c.empty(T, K, D), c.empty(T, Q, dtype=torch.int32)
-    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_float(float(lambd)), _ptr(u),
-                                                     _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
+# ---- value sweeps: the four tunable few-shot methods for a list of values on the same tasks (tclip_*_sweep_tasks) ----------
+def _sweep_values(values, name):
+    """the list of values as a C double array; ValueError for an empty list or a value that is not a finite number - before
+    anything touches the device"""
+    import math
+    try:
+        vals = [float(v) for v in values]
+    except TypeError:
+        raise ValueError(f"{name} must be a non-empty list of finite numbers")
+    if not vals or not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{name} must be a non-empty list of finite numbers")
+    return (ctypes.c_double * len(vals))(*vals)
+
+
+def _sweep_n_class(table_q, n_class, cols, method):
+    """(K, visual): n_class=None is the probability form (K = the tables' width), a number the visual one, which has no cols"""
+    if n_class is None:
+        return (table_q.shape[1] if table_q.dim() == 2 else 0), False
+    n_class = _check_n_class(n_class)
+    if cols is not None:
+        raise ValueError(f"{method} on visual features permutes no columns: cols must be None")
+    return n_class, True
+
+
+# ---- PADDLE --------------------------------------------------------------------------------------------------------------------
+def _paddle(rows, K, visual, iters, lambd, values=None):
+    """PADDLE on rows of D elements: tclip_paddle[_visual]_run[_tasks] with lambd, tclip_paddle_sweep_tasks with `values`"""
+    T, Q, D = rows.T, rows.Q, rows.D
+    c, entry, dim, P = _rows_call("tclip_paddle", rows, _capi.Problem(1, T, Q, K, rows.S, iters, 1, 0, 0), visual, values)
+    u, v, w, preds = c.empty(*P, T, Q, K), c.empty(*P, T, K), c.empty(*P, T, K, D), c.empty(*P, T, Q, dtype=torch.int32)
+    c.launch(entry, lambda ws, n, st: (*dim, *rows.args, _ptr(rows.y_s), *_swept(values, ctypes.c_float, lambd), _ptr(u),
+                                       _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
     return u, v, w, preds
+
+
+def run_paddle(x_q, x_s, y_s, *, iters, lambd):
+    """PADDLE: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda ->
+    (u (T,Q,K), v (T,K), w (T,K,K), preds (T,Q) i32), cuda, not synchronised."""
+    x_q = _query(x_q)
+    x_s, y_s = _support(x_q, x_s, y_s)
+    return _paddle(_dense_rows(x_q, x_s, y_s), x_q.shape[2], False, iters, lambd)
+
+
+def run_paddle_visual(x_q, x_s, y_s, *, n_class, iters, lambd):
+    """PADDLE on visual features: x_q (T,Q,D), x_s (T,S,D) raw embeddings f32 cuda, y_s (T,S) int64 cuda with labels in
+    0..n_class-1 -> (u (T,Q,K), v (T,K), w (T,K,D), preds (T,Q) i32), cuda, not synchronised.  K = n_class cannot be read off a
+    tensor shape here.  No text features: the reference's text-prompt u is dead (paddle.py:183-203)."""
+    x_q = _query(x_q)
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    return _paddle(_dense_rows(x_q, x_s, y_s), K, True, iters, lambd)
 
 
 def run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, lambd):
@@ -331,7 +413,8 @@ def run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, l
     of Tasks_Generator_few_shot.get_task or None -> (u (T,Q,K), v (T,K), w (T,K,K), preds (T,Q) i32), cuda, not synchronised.
     The support rows are read in place: no (T,S,K) tensor is built; the results are those of run_paddle on the materialised
     tensors, bit for bit."""
-    return _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], iters, lambd, visual=False)
+    K = table_q.shape[1]
+    return _paddle(_task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "PADDLE"), K, False, iters, lambd)
 
 
 def run_paddle_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, lambd):
@@ -339,36 +422,52 @@ def run_paddle_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, ite
     embeddings f32 cuda with any D in 1..1024, q_idx (T,Q), s_idx (T,S), y_s (T,S) int64 labels in 0..n_class-1 as they are (no
     re-indexing and no column permutation on visual features) -> (u (T,Q,K), v (T,K), w (T,K,D), preds (T,Q) i32), cuda, not
     synchronised; the bits of run_paddle_visual on the materialised tensors."""
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    return _run_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, iters, lambd, visual=True)
+    K = _check_n_class(n_class)
+    return _paddle(_task_tables(table_q, q_idx, table_s, s_idx, y_s, None, K, "PADDLE"), K, True, iters, lambd)
 
 
+def sweep_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, values, n_class=None):
+    """run_paddle_tasks (n_class=None) / run_paddle_visual_tasks (n_class given; cols must be None) for every lambd of `values`
+    in one call (tclip_paddle_sweep_tasks) -> (u (P,T,Q,K), v (P,T,K), w (P,T,K,D), preds (P,T,Q) i32): slice i holds the
+    bits of the single-value call with lambd = values[i].  The support class sums are taken once.  Not synchronised."""
+    values = _sweep_values(values, "values")
+    K, visual = _sweep_n_class(table_q, n_class, cols, "PADDLE")
+    return _paddle(_task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "PADDLE"), K, visual, iters, None, values)
+
+
+# ---- ALPHA_TIM and TIM_GD ------------------------------------------------------------------------------------------------------
 ENTROPIES = {"Shannon": 0, "Alpha": 1}
-
-
-def _run_alpha_tim(x_q, x_s, y_s, K, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, visual):
-    """ALPHA_TIM on rows of D elements: D = K and tclip_alpha_tim_run for probability features, tclip_alpha_tim_visual_run with D
-    as its first argument for visual ones."""
-    T, Q, D = x_q.shape
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    prm = _capi.TimParams(float(lr), float(temp), float(alpha_value), (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
-                          (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
-    stem, dim = ("tclip_alpha_tim_visual", (ctypes.c_int32(D),)) if visual else ("tclip_alpha_tim", ())
-    c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, x_s.shape[1], iters, 1, 0, 0),
-              stem + "_workspace_bytes", *dim)
-    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(n_batches, iters)
-    c.launch(stem + "_run", lambda ws, n, st: (*dim, ctypes.byref(prm), _ptr(x_q), _ptr(x_s), _ptr(y_s), _ptr(weights),
-                                               _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
-    return weights, logits_q, preds, crit
 
 
 def _check_entropies(entropies):
     for e in entropies:
         if e not in ENTROPIES:
             raise ValueError("Entropies must be in ['Shannon', 'Alpha']")        # tim.py:286, 295, 305
+
+
+def _tim_params(lr, temp, alpha_value, loss_weights, entropies):
+    return _capi.TimParams(float(lr), float(temp), float(alpha_value), (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
+                           (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
+
+
+def _check_n_batches(rows, n_batches):
+    if rows.T % n_batches:
+        raise ValueError("the number of tasks must be a multiple of n_batches")
+
+
+def _alpha_tim(rows, K, visual, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, values=None):
+    """ALPHA_TIM on rows of D elements: tclip_alpha_tim[_visual]_run[_tasks] with alpha_value, tclip_alpha_tim_sweep_tasks with
+    `values` (the struct's alpha_value is not read there)"""
+    _check_n_batches(rows, n_batches)
+    T, Q, D = rows.T, rows.Q, rows.D
+    prm = _tim_params(lr, temp, alpha_value if values is None else 0.0, loss_weights, entropies)
+    c, entry, dim, P = _rows_call("tclip_alpha_tim", rows, _capi.Problem(n_batches, T // n_batches, Q, K, rows.S, iters, 1, 0, 0),
+                                  visual, values)
+    weights, logits_q = c.empty(*P, T, K, D), c.empty(*P, T, Q, K)
+    preds, crit = c.empty(*P, T, Q, dtype=torch.int32), c.empty(*P, n_batches, iters)
+    c.launch(entry, lambda ws, n, st: (*dim, ctypes.byref(prm), *rows.args, _ptr(rows.y_s), *_swept(values), _ptr(weights),
+                                       _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
+    return weights, logits_q, preds, crit
 
 
 def run_alpha_tim(x_q, x_s, y_s, *, iters, temp, lr, alpha_value, loss_weights=(1.0, 1.0, 1.0),
@@ -378,7 +477,7 @@ def run_alpha_tim(x_q, x_s, y_s, *, iters, temp, lr, alpha_value, loss_weights=(
     _check_entropies(entropies)
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
-    return _run_alpha_tim(x_q, x_s, y_s, x_q.shape[2], iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, visual=False)
+    return _alpha_tim(_dense_rows(x_q, x_s, y_s), x_q.shape[2], False, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches)
 
 
 def run_alpha_tim_visual(x_q, x_s, y_s, *, n_class, iters, temp, lr, alpha_value, loss_weights=(1.0, 1.0, 1.0),
@@ -391,7 +490,56 @@ def run_alpha_tim_visual(x_q, x_s, y_s, *, n_class, iters, temp, lr, alpha_value
     if x_s.dim() != 3 or x_s.shape[1] < 1:
         raise ValueError("ALPHA_TIM is a few-shot method: x_s must be (T,S,D) with n_support = S positive")
     x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    return _run_alpha_tim(x_q, x_s, y_s, K, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches, visual=True)
+    return _alpha_tim(_dense_rows(x_q, x_s, y_s), K, True, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches)
+
+
+def run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, temp, lr, alpha_value,
+                        loss_weights=(1.0, 1.0, 1.0), entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
+    """ALPHA_TIM fed from the task-batch loop's feature tables (tclip_alpha_tim_run_tasks): table_q, table_s (rows,K) f32 cuda,
+    q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column permutation
+    of Tasks_Generator_few_shot.get_task or None -> what run_alpha_tim returns on the materialised tensors, bit for bit; neither
+    (T,S,K) nor (T,Q,K) is built: the table rows are read in place in every Adam step.  Not synchronised."""
+    K = table_q.shape[1]
+    _check_entropies(entropies)
+    rows = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "ALPHA_TIM")
+    return _alpha_tim(rows, K, False, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches)
+
+
+def run_alpha_tim_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, temp, lr, alpha_value,
+                               loss_weights=(1.0, 1.0, 1.0), entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
+    """ALPHA_TIM on visual features fed from the feature tables (tclip_alpha_tim_visual_run_tasks): tables (rows,D) with any D
+    in 1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> the bits of run_alpha_tim_visual
+    on the materialised tensors.  Not synchronised."""
+    K = _check_n_class(n_class)
+    _check_entropies(entropies)
+    rows = _task_tables(table_q, q_idx, table_s, s_idx, y_s, None, K, "ALPHA_TIM")
+    return _alpha_tim(rows, K, True, iters, temp, lr, alpha_value, loss_weights, entropies, n_batches)
+
+
+def sweep_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, temp, lr, values, loss_weights=(1.0, 1.0, 1.0),
+                          entropies=("Shannon", "Alpha", "Alpha"), n_batches=1, n_class=None):
+    """run_alpha_tim_tasks (n_class=None) / run_alpha_tim_visual_tasks (n_class given) for every alpha_value of `values` in one
+    call (tclip_alpha_tim_sweep_tasks) -> (weights (P,T,K,D), logits_q (P,T,Q,K), preds (P,T,Q) i32, criterions
+    (P,n_batches,iters)), slice i the bits of the single-value call with alpha_value = values[i].  The Adam loop runs over
+    P * T solves in one set of launches per step; solve (i, t) reads the rows of task t in place.  Not synchronised."""
+    values = _sweep_values(values, "values")
+    _check_entropies(entropies)
+    K, visual = _sweep_n_class(table_q, n_class, cols, "ALPHA_TIM")
+    rows = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "ALPHA_TIM")
+    return _alpha_tim(rows, K, visual, iters, temp, lr, None, loss_weights, entropies, n_batches, values)
+
+
+def _tim_gd(rows, K, iters, temp, lr, loss_weights, n_batches):
+    """TIM_GD on rows of D elements, D always passed: tclip_tim_gd_run[_tasks]"""
+    _check_n_batches(rows, n_batches)
+    T, Q, D = rows.T, rows.Q, rows.D
+    lw = (ctypes.c_float * 3)(*[float(w) for w in loss_weights])
+    c, entry, dim, _ = _rows_call("tclip_tim_gd", rows, _capi.Problem(n_batches, T // n_batches, Q, K, rows.S, iters, 1, 0, 0), True,
+                                  infix="")
+    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(iters, T)
+    c.launch(entry, lambda ws, n, st: (*dim, ctypes.c_double(float(lr)), ctypes.c_float(float(temp)), lw, *rows.args, _ptr(rows.y_s),
+                                       _ptr(weights), _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
+    return weights, logits_q, preds, crit
 
 
 def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0), n_batches=1):
@@ -403,59 +551,7 @@ def run_tim_gd(x_q, x_s, y_s, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.
     if x_s.dim() != 3 or x_s.shape[1] < 1:
         raise ValueError("TIM_GD is a few-shot method: x_s must be (T,S,D) with n_support = S positive")
     x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    T, Q, D = x_q.shape
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    dim = ctypes.c_int32(D)
-    lw = (ctypes.c_float * 3)(*[float(w) for w in loss_weights])
-    c = _Call(x_q.device, _capi.Problem(n_batches, T // n_batches, Q, K, x_s.shape[1], iters, 1, 0, 0),
-              "tclip_tim_gd_workspace_bytes", dim)
-    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(iters, T)
-    c.launch("tclip_tim_gd_run", lambda ws, n, st: (dim, ctypes.c_double(float(lr)), ctypes.c_float(float(temp)), lw, _ptr(x_q),
-                                                    _ptr(x_s), _ptr(y_s), _ptr(weights), _ptr(logits_q), _ptr(preds), _ptr(crit),
-                                                    ws, n, st))
-    return weights, logits_q, preds, crit
-
-
-def _run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, temp, lr, alpha_value, loss_weights, entropies,
-                         n_batches, visual):
-    """ALPHA_TIM from the feature tables on rows of D elements (tclip_alpha_tim_run_tasks / tclip_alpha_tim_visual_run_tasks)"""
-    _check_entropies(entropies)
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "ALPHA_TIM")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    prm = _capi.TimParams(float(lr), float(temp), float(alpha_value), (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
-                          (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
-    stem, dim = ("tclip_alpha_tim_visual", (ctypes.c_int32(D),)) if visual else ("tclip_alpha_tim", ())
-    c = _Call(dev, _capi.Problem(n_batches, T // n_batches, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
-    weights, logits_q, preds, crit = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32), c.empty(n_batches, iters)
-    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(prm), ctypes.byref(src), _ptr(y_s), _ptr(weights),
-                                                     _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
-    return weights, logits_q, preds, crit
-
-
-def run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, temp, lr, alpha_value,
-                        loss_weights=(1.0, 1.0, 1.0), entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
-    """ALPHA_TIM fed from the task-batch loop's feature tables (tclip_alpha_tim_run_tasks): table_q, table_s (rows,K) f32 cuda,
-    q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column permutation
-    of Tasks_Generator_few_shot.get_task or None -> what run_alpha_tim returns on the materialised tensors, bit for bit; neither
-    (T,S,K) nor (T,Q,K) is built: the table rows are read in place in every Adam step.  Not synchronised."""
-    return _run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], iters, temp, lr, alpha_value,
-                                loss_weights, entropies, n_batches, visual=False)
-
-
-def run_alpha_tim_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, temp, lr, alpha_value,
-                               loss_weights=(1.0, 1.0, 1.0), entropies=("Shannon", "Alpha", "Alpha"), n_batches=1):
-    """ALPHA_TIM on visual features fed from the feature tables (tclip_alpha_tim_visual_run_tasks): tables (rows,D) with any D
-    in 1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> the bits of run_alpha_tim_visual
-    on the materialised tensors.  Not synchronised."""
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    return _run_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, iters, temp, lr, alpha_value, loss_weights,
-                                entropies, n_batches, visual=True)
+    return _tim_gd(_dense_rows(x_q, x_s, y_s), K, iters, temp, lr, loss_weights, n_batches)
 
 
 def run_tim_gd_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, n_class, iters, temp, lr, loss_weights=(1.0, 0.3, 1.0),
@@ -464,43 +560,32 @@ def run_tim_gd_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, n_class,
     1..1024, q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) int64 labels in 0..n_class-1 (re-indexed on probability
     features), cols (T,D) the per-task column permutation on probability features (D = n_class) or None -> what run_tim_gd
     returns on the materialised tensors, bit for bit; the table rows are read in place in every Adam step.  Not synchronised."""
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    if cols is not None and table_q.dim() == 2 and table_q.shape[1] != n_class:
+    K = _check_n_class(n_class)
+    if cols is not None and table_q.dim() == 2 and table_q.shape[1] != K:
         raise ValueError("TIM_GD permutes columns on probability features only: cols needs tables of n_class columns")
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, n_class, "TIM_GD")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    dim = ctypes.c_int32(D)
-    lw = (ctypes.c_float * 3)(*[float(w) for w in loss_weights])
-    c = _Call(dev, _capi.Problem(n_batches, T // n_batches, Q, n_class, S, iters, 1, 0, 0), "tclip_tim_gd_tasks_workspace_bytes", dim)
-    weights, logits_q, preds, crit = c.empty(T, n_class, D), c.empty(T, Q, n_class), c.empty(T, Q, dtype=torch.int32), c.empty(iters, T)
-    c.launch("tclip_tim_gd_run_tasks", lambda ws, n, st: (dim, ctypes.c_double(float(lr)), ctypes.c_float(float(temp)), lw,
-                                                          ctypes.byref(src), _ptr(y_s), _ptr(weights), _ptr(logits_q), _ptr(preds),
-                                                          _ptr(crit), ws, n, st))
-    return weights, logits_q, preds, crit
+    return _tim_gd(_task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "TIM_GD"), K, iters, temp, lr, loss_weights, n_batches)
 
 
-def _run_laplacian_shot(x_q, x_s, y_s, K, iters, knn, lmd, norm_type, visual):
-    """LAPLACIAN_SHOT on rows of D elements: D = K and tclip_laplacian_shot_run for probability features,
-    tclip_laplacian_shot_visual_run with D as its first argument for visual ones."""
-    T, Q, D = x_q.shape
-    stem, dim = ("tclip_laplacian_shot_visual", (ctypes.c_int32(D),)) if visual else ("tclip_laplacian_shot", ())
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], iters, 1, 0, 0), stem + "_workspace_bytes", *dim)
-    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
-    preds_iter, energies = c.empty(T, max(iters, 1), Q, dtype=torch.int32), c.empty(T, max(iters, 1), dtype=torch.float64)
-    c.launch(stem + "_run", lambda ws, n, st: (*dim, _ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_int32(int(knn)),
-                                               ctypes.c_double(float(lmd)), ctypes.c_int32(NORM_TYPES[norm_type]),
-                                               _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies), ws, n, st))
-    return unary, nbr, preds_iter, energies
+# ---- LAPLACIAN_SHOT ------------------------------------------------------------------------------------------------------------
+NORM_TYPES = {"UN": 0, "L2N": 1, "CL2N": 2}
 
 
 def _check_lshot_norm(norm_type):
     if norm_type not in ("UN", "L2N"):
         raise ValueError("norm_type must be 'UN' or 'L2N' (the reference's CL2N needs a train mean it never passes)")
+
+
+def _laplacian_shot(rows, K, visual, iters, knn, lmd, norm_type, values=None):
+    """LAPLACIAN_SHOT on rows of D elements: tclip_laplacian_shot[_visual]_run[_tasks] with lmd, tclip_laplacian_shot_sweep_tasks
+    with `values`; the unary term and the neighbours, which no lmd enters, have no leading P"""
+    T, Q = rows.T, rows.Q
+    c, entry, dim, P = _rows_call("tclip_laplacian_shot", rows, _capi.Problem(1, T, Q, K, rows.S, iters, 1, 0, 0), visual, values)
+    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
+    preds_iter, energies = c.empty(*P, T, max(iters, 1), Q, dtype=torch.int32), c.empty(*P, T, max(iters, 1), dtype=torch.float64)
+    c.launch(entry, lambda ws, n, st: (*dim, *rows.args, _ptr(rows.y_s), ctypes.c_int32(int(knn)),
+                                       *_swept(values, ctypes.c_double, lmd), ctypes.c_int32(NORM_TYPES[norm_type]),
+                                       _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies), ws, n, st))
+    return unary, nbr, preds_iter, energies
 
 
 def run_laplacian_shot(x_q, x_s, y_s, *, iters, knn, lmd, norm_type="L2N"):
@@ -509,7 +594,7 @@ def run_laplacian_shot(x_q, x_s, y_s, *, iters, knn, lmd, norm_type="L2N"):
     _check_lshot_norm(norm_type)
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
-    return _run_laplacian_shot(x_q, x_s, y_s, x_q.shape[2], iters, knn, lmd, norm_type, visual=False)
+    return _laplacian_shot(_dense_rows(x_q, x_s, y_s), x_q.shape[2], False, iters, knn, lmd, norm_type)
 
 
 def run_laplacian_shot_visual(x_q, x_s, y_s, *, n_class, iters, knn, lmd, norm_type="L2N"):
@@ -519,24 +604,7 @@ def run_laplacian_shot_visual(x_q, x_s, y_s, *, n_class, iters, knn, lmd, norm_t
     _check_lshot_norm(norm_type)
     x_q = _query(x_q)
     x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    return _run_laplacian_shot(x_q, x_s, y_s, K, iters, knn, lmd, norm_type, visual=True)
-
-
-def _run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, iters, knn, lmd, norm_type, visual):
-    """LAPLACIAN_SHOT from the feature tables on rows of D elements (tclip_laplacian_shot_run_tasks /
-    tclip_laplacian_shot_visual_run_tasks)"""
-    _check_lshot_norm(norm_type)
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "LAPLACIAN_SHOT")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    stem, dim = ("tclip_laplacian_shot_visual", (ctypes.c_int32(D),)) if visual else ("tclip_laplacian_shot", ())
-    c = _Call(dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
-    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
-    preds_iter, energies = c.empty(T, max(iters, 1), Q, dtype=torch.int32), c.empty(T, max(iters, 1), dtype=torch.float64)
-    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_int32(int(knn)),
-                                                     ctypes.c_double(float(lmd)), ctypes.c_int32(NORM_TYPES[norm_type]),
-                                                     _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies), ws, n, st))
-    return unary, nbr, preds_iter, energies
+    return _laplacian_shot(_dense_rows(x_q, x_s, y_s), K, True, iters, knn, lmd, norm_type)
 
 
 def run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, knn, lmd, norm_type="L2N"):
@@ -544,18 +612,33 @@ def run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, 
     f32 cuda, q_idx (T,Q) / s_idx (T,S) rows of them, y_s (T,S) the re-indexed support labels, cols (T,K) the per-task column
     permutation of Tasks_Generator_few_shot.get_task or None -> what run_laplacian_shot returns on the materialised tensors,
     bit for bit; neither (T,S,K) nor (T,Q,K) is built.  Not synchronised."""
-    return _run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], iters, knn, lmd, norm_type,
-                                     visual=False)
+    K = table_q.shape[1]
+    _check_lshot_norm(norm_type)
+    rows = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "LAPLACIAN_SHOT")
+    return _laplacian_shot(rows, K, False, iters, knn, lmd, norm_type)
 
 
 def run_laplacian_shot_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, iters, knn, lmd, norm_type="L2N"):
     """LAPLACIAN_SHOT on visual features fed from the feature tables (tclip_laplacian_shot_visual_run_tasks): tables (rows,D)
     with any D in 1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> the bits of
     run_laplacian_shot_visual on the materialised tensors.  Not synchronised."""
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    return _run_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, iters, knn, lmd, norm_type, visual=True)
+    K = _check_n_class(n_class)
+    _check_lshot_norm(norm_type)
+    rows = _task_tables(table_q, q_idx, table_s, s_idx, y_s, None, K, "LAPLACIAN_SHOT")
+    return _laplacian_shot(rows, K, True, iters, knn, lmd, norm_type)
+
+
+def sweep_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, knn, values, norm_type="L2N", n_class=None):
+    """run_laplacian_shot_tasks (n_class=None) / run_laplacian_shot_visual_tasks (n_class given) for every lmd of `values` in one
+    call (tclip_laplacian_shot_sweep_tasks) -> (unary (T,Q,K) and neighbours (T,Q,knn-1) i32, which no lmd enters, once;
+    preds_iter (P,T,iters,Q) i32, energies (P,T,iters) f64, slice i the bits of the single-value call with lmd = values[i]).
+    Normalisation, prototypes, unary term and kNN graph run once per task, the updates on a grid of (task, value).  Not
+    synchronised."""
+    values = _sweep_values(values, "values")
+    _check_lshot_norm(norm_type)
+    K, visual = _sweep_n_class(table_q, n_class, cols, "LAPLACIAN_SHOT")
+    rows = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "LAPLACIAN_SHOT")
+    return _laplacian_shot(rows, K, visual, iters, knn, None, norm_type, values)
 
 
 def argmax_rows(x):
@@ -571,46 +654,38 @@ def argmax_rows(x):
     return labels
 
 
-NORM_TYPES = {"UN": 0, "L2N": 1, "CL2N": 2}
+# ---- BD-CSPN -------------------------------------------------------------------------------------------------------------------
+def _check_bdcspn_norm(norm_type):
+    if norm_type not in NORM_TYPES:
+        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
 
 
-def _run_bdcspn(x_q, x_s, y_s, K, temp, norm_type, visual):
-    """BD-CSPN on rows of D elements: D = K and tclip_bdcspn_run for probability features, tclip_bdcspn_visual_run with D as its
-    first argument for visual ones."""
-    T, Q, D = x_q.shape
-    stem, dim = ("tclip_bdcspn_visual", (ctypes.c_int32(D),)) if visual else ("tclip_bdcspn", ())
-    c = _Call(x_q.device, _capi.Problem(1, T, Q, K, x_s.shape[1], 1, 1, 0, 0), stem + "_workspace_bytes", *dim)
-    prototypes, u, preds = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
-    c.launch(stem + "_run", lambda ws, n, st: (*dim, _ptr(x_q), _ptr(x_s), _ptr(y_s), ctypes.c_float(float(temp)),
-                                               ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u), _ptr(preds),
-                                               ws, n, st))
+def _bdcspn(rows, K, visual, temp, norm_type, values=None):
+    """BD-CSPN on rows of D elements: tclip_bdcspn[_visual]_run[_tasks] with temp, tclip_bdcspn_sweep_tasks with `values`"""
+    T, Q, D = rows.T, rows.Q, rows.D
+    c, entry, dim, P = _rows_call("tclip_bdcspn", rows, _capi.Problem(1, T, Q, K, rows.S, 1, 1, 0, 0), visual, values)
+    prototypes, u, preds = c.empty(*P, T, K, D), c.empty(*P, T, Q, K), c.empty(*P, T, Q, dtype=torch.int32)
+    c.launch(entry, lambda ws, n, st: (*dim, *rows.args, _ptr(rows.y_s), *_swept(values, ctypes.c_float, temp),
+                                       ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u), _ptr(preds), ws, n, st))
     return prototypes, u, preds
 
 
 def run_bdcspn(x_q, x_s, y_s, *, temp, norm_type="L2N"):
     """BD-CSPN: x_q (T,Q,K), x_s (T,S,K) f32 cuda, y_s (T,S) int64 cuda ->
     (prototypes (T,K,K), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised."""
-    if norm_type not in NORM_TYPES:
-        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
+    _check_bdcspn_norm(norm_type)
     x_q = _query(x_q)
     x_s, y_s = _support(x_q, x_s, y_s)
-    return _run_bdcspn(x_q, x_s, y_s, x_q.shape[2], temp, norm_type, visual=False)
+    return _bdcspn(_dense_rows(x_q, x_s, y_s), x_q.shape[2], False, temp, norm_type)
 
 
-def _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, K, temp, norm_type, visual):
-    """BD-CSPN from the feature tables on rows of D elements (tclip_bdcspn_run_tasks / tclip_bdcspn_visual_run_tasks)"""
-    if norm_type not in NORM_TYPES:
-        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "BDCSPN")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    stem, dim = ("tclip_bdcspn_visual", (ctypes.c_int32(D),)) if visual else ("tclip_bdcspn", ())
-    c = _Call(dev, _capi.Problem(1, T, Q, K, S, 1, 1, 0, 0), stem + "_tasks_workspace_bytes", *dim)
-    prototypes, u, preds = c.empty(T, K, D), c.empty(T, Q, K), c.empty(T, Q, dtype=torch.int32)
-    c.launch(stem + "_run_tasks", lambda ws, n, st: (*dim, ctypes.byref(src), _ptr(y_s), ctypes.c_float(float(temp)),
-                                                     ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u), _ptr(preds),
-                                                     ws, n, st))
-    return prototypes, u, preds
+def run_bdcspn_visual(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
+    """BD-CSPN on visual features: x_q (T,Q,D), x_s (T,S,D) f32 cuda, y_s (T,S) int64 cuda with labels in 0..n_class-1 ->
+    (rectified prototypes (T,K,D), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised."""
+    _check_bdcspn_norm(norm_type)
+    x_q = _query(x_q)
+    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
+    return _bdcspn(_dense_rows(x_q, x_s, y_s), K, True, temp, norm_type)
 
 
 def run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, temp, norm_type="L2N"):
@@ -619,136 +694,28 @@ def run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, temp, no
     of Tasks_Generator_few_shot.get_task or None -> (prototypes (T,K,K), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised:
     the bits of run_bdcspn on the materialised tensors.  Neither (T,S,K) nor (T,Q,K) is built, and the workspace is smaller than
     the dense one by the normalised support rows (they share the logits' region)."""
-    return _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols, table_q.shape[1], temp, norm_type, visual=False)
+    K = table_q.shape[1]
+    _check_bdcspn_norm(norm_type)
+    return _bdcspn(_task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "BDCSPN"), K, False, temp, norm_type)
 
 
 def run_bdcspn_visual_tasks(table_q, q_idx, table_s, s_idx, y_s, *, n_class, temp, norm_type="L2N"):
     """BD-CSPN on visual features fed from the feature tables (tclip_bdcspn_visual_run_tasks): tables (rows,D) with any D in
     1..1024, y_s (T,S) int64 labels in 0..n_class-1 as they are, no column permutation -> (rectified prototypes (T,K,D),
     u (T,Q,K), preds (T,Q) i32): the bits of run_bdcspn_visual on the materialised tensors.  Not synchronised."""
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    return _run_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, None, n_class, temp, norm_type, visual=True)
-
-
-# ---- value sweeps: the four tunable few-shot methods for a list of values on the same tasks (tclip_*_sweep_tasks) ----------
-def _sweep_values(values, name):
-    """the list of values as a C double array; ValueError for an empty list or a value that is not a finite number - before
-    anything touches the device"""
-    import math
-    try:
-        vals = [float(v) for v in values]
-    except TypeError:
-        raise ValueError(f"{name} must be a non-empty list of finite numbers")
-    if not vals or not all(math.isfinite(v) for v in vals):
-        raise ValueError(f"{name} must be a non-empty list of finite numbers")
-    return (ctypes.c_double * len(vals))(*vals), len(vals)
-
-
-def _sweep_n_class(table_q, n_class):
-    """(K, visual): n_class=None is the probability form (K = the tables' width), a number the visual one"""
-    if n_class is None:
-        return (table_q.shape[1] if table_q.dim() == 2 else 0), False
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    return n_class, True
-
-
-def _sweep_call(stem, dev, problem, D, visual, P):
-    dim = ctypes.c_int32(D if visual else 0)
-    return _Call(dev, problem, stem + "_sweep_tasks_workspace_bytes", dim, ctypes.c_int32(P)), dim
-
-
-def sweep_paddle_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, values, n_class=None):
-    """run_paddle_tasks (n_class=None) / run_paddle_visual_tasks (n_class given; cols must be None) for every lambd of `values`
-    in one call (tclip_paddle_sweep_tasks) -> (u (P,T,Q,K), v (P,T,K), w (P,T,K,D), preds (P,T,Q) i32): slice i holds the
-    bits of the single-value call with lambd = values[i].  The support class sums are taken once.  Not synchronised."""
-    vals, P = _sweep_values(values, "values")
-    K, visual = _sweep_n_class(table_q, n_class)
-    if visual and cols is not None:
-        raise ValueError("PADDLE on visual features permutes no columns: cols must be None")
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "PADDLE")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    c, dim = _sweep_call("tclip_paddle", dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), D, visual, P)
-    u, v, w, preds = c.empty(P, T, Q, K), c.empty(P, T, K), c.empty(P, T, K, D), c.empty(P, T, Q, dtype=torch.int32)
-    c.launch("tclip_paddle_sweep_tasks", lambda ws, n, st: (dim, ctypes.byref(src), _ptr(y_s), vals, ctypes.c_int32(P), _ptr(u),
-                                                            _ptr(v), _ptr(w), _ptr(preds), ws, n, st))
-    return u, v, w, preds
+    K = _check_n_class(n_class)
+    _check_bdcspn_norm(norm_type)
+    return _bdcspn(_task_tables(table_q, q_idx, table_s, s_idx, y_s, None, K, "BDCSPN"), K, True, temp, norm_type)
 
 
 def sweep_bdcspn_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, values, norm_type="L2N", n_class=None):
     """run_bdcspn_tasks (n_class=None) / run_bdcspn_visual_tasks (n_class given) for every temp of `values` in one call
     (tclip_bdcspn_sweep_tasks) -> (prototypes (P,T,K,D), u (P,T,Q,K), preds (P,T,Q) i32), slice i the bits of the single-value
     call with temp = values[i].  Everything up to the augmented set runs once.  Not synchronised."""
-    vals, P = _sweep_values(values, "values")
-    if norm_type not in NORM_TYPES:
-        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
-    K, visual = _sweep_n_class(table_q, n_class)
-    if visual and cols is not None:
-        raise ValueError("BDCSPN on visual features permutes no columns: cols must be None")
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "BDCSPN")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    c, dim = _sweep_call("tclip_bdcspn", dev, _capi.Problem(1, T, Q, K, S, 1, 1, 0, 0), D, visual, P)
-    prototypes, u, preds = c.empty(P, T, K, D), c.empty(P, T, Q, K), c.empty(P, T, Q, dtype=torch.int32)
-    c.launch("tclip_bdcspn_sweep_tasks", lambda ws, n, st: (dim, ctypes.byref(src), _ptr(y_s), vals, ctypes.c_int32(P),
-                                                            ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(prototypes), _ptr(u),
-                                                            _ptr(preds), ws, n, st))
-    return prototypes, u, preds
-
-
-def sweep_laplacian_shot_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, knn, values, norm_type="L2N", n_class=None):
-    """run_laplacian_shot_tasks (n_class=None) / run_laplacian_shot_visual_tasks (n_class given) for every lmd of `values` in one
-    call (tclip_laplacian_shot_sweep_tasks) -> (unary (T,Q,K) and neighbours (T,Q,knn-1) i32, which no lmd enters, once;
-    preds_iter (P,T,iters,Q) i32, energies (P,T,iters) f64, slice i the bits of the single-value call with lmd = values[i]).
-    Normalisation, prototypes, unary term and kNN graph run once per task, the updates on a grid of (task, value).  Not
-    synchronised."""
-    vals, P = _sweep_values(values, "values")
-    _check_lshot_norm(norm_type)
-    K, visual = _sweep_n_class(table_q, n_class)
-    if visual and cols is not None:
-        raise ValueError("LAPLACIAN_SHOT on visual features permutes no columns: cols must be None")
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "LAPLACIAN_SHOT")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    c, dim = _sweep_call("tclip_laplacian_shot", dev, _capi.Problem(1, T, Q, K, S, iters, 1, 0, 0), D, visual, P)
-    unary, nbr = c.empty(T, Q, K), c.empty(T, Q, max(int(knn) - 1, 1), dtype=torch.int32)
-    preds_iter, energies = c.empty(P, T, max(iters, 1), Q, dtype=torch.int32), c.empty(P, T, max(iters, 1), dtype=torch.float64)
-    c.launch("tclip_laplacian_shot_sweep_tasks",
-             lambda ws, n, st: (dim, ctypes.byref(src), _ptr(y_s), ctypes.c_int32(int(knn)), vals, ctypes.c_int32(P),
-                                ctypes.c_int32(NORM_TYPES[norm_type]), _ptr(unary), _ptr(nbr), _ptr(preds_iter), _ptr(energies),
-                                ws, n, st))
-    return unary, nbr, preds_iter, energies
-
-
-def sweep_alpha_tim_tasks(table_q, q_idx, table_s, s_idx, y_s, cols=None, *, iters, temp, lr, values, loss_weights=(1.0, 1.0, 1.0),
-                          entropies=("Shannon", "Alpha", "Alpha"), n_batches=1, n_class=None):
-    """run_alpha_tim_tasks (n_class=None) / run_alpha_tim_visual_tasks (n_class given) for every alpha_value of `values` in one
-    call (tclip_alpha_tim_sweep_tasks) -> (weights (P,T,K,D), logits_q (P,T,Q,K), preds (P,T,Q) i32, criterions
-    (P,n_batches,iters)), slice i the bits of the single-value call with alpha_value = values[i].  The Adam loop runs over
-    P * T solves in one set of launches per step; solve (i, t) reads the rows of task t in place.  Not synchronised."""
-    vals, P = _sweep_values(values, "values")
-    _check_entropies(entropies)
-    K, visual = _sweep_n_class(table_q, n_class)
-    if visual and cols is not None:
-        raise ValueError("ALPHA_TIM on visual features permutes no columns: cols must be None")
-    table_q, q_idx, table_s, s_idx, y_s, cols, src = _task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "ALPHA_TIM")
-    dev, D = table_q.device, table_q.shape[1]
-    (T, Q), S = q_idx.shape, s_idx.shape[1]
-    if T % n_batches:
-        raise ValueError("the number of tasks must be a multiple of n_batches")
-    prm = _capi.TimParams(float(lr), float(temp), 0.0, (ctypes.c_float * 3)(*[float(w) for w in loss_weights]),
-                          (ctypes.c_int32 * 3)(*[ENTROPIES[e] for e in entropies]))
-    c, dim = _sweep_call("tclip_alpha_tim", dev, _capi.Problem(n_batches, T // n_batches, Q, K, S, iters, 1, 0, 0), D, visual, P)
-    weights, logits_q = c.empty(P, T, K, D), c.empty(P, T, Q, K)
-    preds, crit = c.empty(P, T, Q, dtype=torch.int32), c.empty(P, n_batches, iters)
-    c.launch("tclip_alpha_tim_sweep_tasks",
-             lambda ws, n, st: (dim, ctypes.byref(prm), ctypes.byref(src), _ptr(y_s), vals, ctypes.c_int32(P), _ptr(weights),
-                                _ptr(logits_q), _ptr(preds), _ptr(crit), ws, n, st))
-    return weights, logits_q, preds, crit
+    values = _sweep_values(values, "values")
+    _check_bdcspn_norm(norm_type)
+    K, visual = _sweep_n_class(table_q, n_class, cols, "BDCSPN")
+    return _bdcspn(_task_tables(table_q, q_idx, table_s, s_idx, y_s, cols, K, "BDCSPN"), K, visual, None, norm_type, values)
 
 
 MATCHING = ("host", "device")
@@ -873,37 +840,6 @@ def run_em_gaussian_cov_visual(x_q, u0, *, iters, lambd):
     c.launch("tclip_em_gaussian_cov_visual_run", lambda ws, n, st: (ctypes.c_int32(D), _ptr(x_q), _ptr(u0), _ptr(u), _ptr(v), _ptr(w),
                                                                     _ptr(s), _ptr(preds), ws, n, st))
     return u, v, w, s, preds
-
-
-def _support_visual(x_q, x_s, y_s, n_class):
-    """_support for D-wide rows: the width of x_s is checked against D, the labels against n_class (on the device: one
-    reduction, its result read back, so that no kernel ever sees a label outside 0..n_class-1)."""
-    x_s, y_s = _support(x_q, x_s, y_s.to(x_q.device))
-    n_class = int(n_class)
-    if not 2 <= n_class <= 1024:
-        raise ValueError("n_class must be in 2..1024")
-    if y_s.numel() and not bool(((y_s >= 0) & (y_s < n_class)).all()):
-        raise ValueError(f"y_s holds a label outside 0..{n_class - 1}")
-    return x_s, y_s, n_class
-
-
-def run_paddle_visual(x_q, x_s, y_s, *, n_class, iters, lambd):
-    """PADDLE on visual features: x_q (T,Q,D), x_s (T,S,D) raw embeddings f32 cuda, y_s (T,S) int64 cuda with labels in
-    0..n_class-1 -> (u (T,Q,K), v (T,K), w (T,K,D), preds (T,Q) i32), cuda, not synchronised.  K = n_class cannot be read off a
-    tensor shape here.  No text features: the reference's text-prompt u is dead (paddle.py:183-203)."""
-    x_q = _query(x_q)
-    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    return _run_paddle(x_q, x_s, y_s, K, iters, lambd, visual=True)
-
-
-def run_bdcspn_visual(x_q, x_s, y_s, *, n_class, temp, norm_type="L2N"):
-    """BD-CSPN on visual features: x_q (T,Q,D), x_s (T,S,D) f32 cuda, y_s (T,S) int64 cuda with labels in 0..n_class-1 ->
-    (rectified prototypes (T,K,D), u (T,Q,K), preds (T,Q) i32), cuda, not synchronised."""
-    if norm_type not in NORM_TYPES:
-        raise ValueError(f"norm_type must be one of {sorted(NORM_TYPES)}")
-    x_q = _query(x_q)
-    x_s, y_s, K = _support_visual(x_q, x_s, y_s, n_class)
-    return _run_bdcspn(x_q, x_s, y_s, K, temp, norm_type, visual=True)
 
 
 def _match(lib, T, Q, K, preds, n_clusters, ids, rows, y_q, graph_matching, cmax, dev):
