@@ -1,0 +1,96 @@
+"""What the two task-batch loops (src/eval_zero_shot.py, src/eval_few_shot.py) share: the constructor, the method table
+look-up, the saved-feature files, the result rows, the per-batch samplers and the tail that gathers a run's results onto
+rank 0."""
+import contextlib
+import os
+
+import numpy as np
+import torch
+
+from src.utils import Logger, compute_confidence_interval
+from tclip_amd import features, reporting, sharding
+
+
+def _as_tensor(x):
+    return x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+
+
+@contextlib.contextmanager
+def arg_set_to(args, attr, value):
+    """args[attr] is `value` inside the block and what it was before afterwards, whatever the block raises"""
+    saved = args[attr]
+    args[attr] = value
+    try:
+        yield
+    finally:
+        args[attr] = saved
+
+
+class EvaluatorBase:
+    _METHODS = {}       # name_method -> class: the subclass's table
+
+    def __init__(self, device, args, log_file):
+        self.device = device
+        self.args = args
+        self.log_file = log_file
+        self.logger = Logger(type(self).__module__, self.log_file)
+
+    def get_method_builder(self, model, device, args, log_file):
+        try:
+            cls = self._METHODS[args.name_method]
+        except KeyError:
+            raise ValueError(f"method {args.name_method!r} is not part of the EM-Dirichlet engine")
+        return cls(model=model, device=device, log_file=log_file, args=args)
+
+    def report_results(self, mean_accuracies, mean_times):
+        """eval_zero_shot.py:189-232, eval_few_shot.py:272-338 (validation sweep row, or the test-mode row)."""
+        return reporting.report_results(self.args, mean_accuracies, mean_times, self.logger,
+                                        root=getattr(self.args, 'results_root', '.'))
+
+    def load_split(self, split):
+        """data/<dataset>/saved_features/<split>_{softmax_<backbone>_T<T>,visual_<backbone>}.plk under args.results_root
+        (default: the working directory, as in the reference), as the reference's dictionary"""
+        path = reporting.saved_feature_path(self.args, split, getattr(self.args, 'results_root', '.'))
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path} not found: this package runs the reference's evaluation from saved "
+                                    "feature files; extract them with the reference (CLIP is out of scope here)")
+        feats, labels = features.load_features(path)
+        return {'concat_features': feats, 'concat_labels': labels}
+
+    def _draw_batches(self, make_sampler, labels, draws):
+        """One (n_batches, batch_size, n) index tensor per class of `draws`, drawn batch by batch exactly as the reference
+        does: a fresh sampler per batch, the classes of `draws` iterated in their order.  The label -> index lists
+        (`m_ind_*`) are a function of the labels alone and consume no random numbers: built for the first batch from `labels`,
+        shared by the others (the reference rebuilds them per batch, sampler_zero_shot.py:31-36)."""
+        a = self.args
+        out, lists = [[] for _ in draws], None
+        for _ in range(int(a.number_tasks / a.batch_size)):
+            sampler = make_sampler()
+            if lists is None:
+                sampler.create_list_classes(*labels)
+                lists = {k: v for k, v in vars(sampler).items() if k.startswith('m_ind_')}
+            else:
+                vars(sampler).update(lists)
+            for drawn, draw in zip(out, draws):
+                drawn.append(torch.stack(list(draw(sampler)), 0))
+        return [torch.stack(drawn, 0) for drawn in out]
+
+    def _gathered(self, parts, n_batches, N, Q, method, timestamps):
+        """The one collective of a run and what it leaves behind: the per-task predictions, accuracies and per-batch records
+        of every rank onto rank 0 (`parts`: this rank's, None when it had no batch; `timestamps`: one time per batch it ran).
+        Sets last_method (`method`: the object that actually ran on this rank) and, on rank 0, last_task_accuracies,
+        last_task_predictions, last_batch_criterions and last_batch_mm_iters.  Returns (mean over the batches of their mean
+        accuracies, mean time), or (None, None) off rank 0."""
+        if parts is None:      # more ranks than batches: this rank only takes part in the gather
+            parts = sharding.method_parts(self.args, None, None, 0, N, Q, torch.device(self.device))
+        got = sharding.gather_packed(parts, n_batches)
+        self.last_method = method
+        if got is None:
+            return None, None
+        acc = got['acc'].numpy()
+        results_task = [compute_confidence_interval(acc[b])[0] for b in range(n_batches)]
+        self.last_task_accuracies = acc
+        self.last_task_predictions = got['preds'].view(n_batches, N, Q).numpy()      # class per query, every batch of the run
+        self.last_batch_criterions = got['criterions'].numpy() if 'criterions' in got else None     # (n_batches, iter)
+        self.last_batch_mm_iters = got['mm_iters'].numpy() if 'mm_iters' in got else None
+        return np.asarray(results_task).mean(), (float(np.mean(timestamps)) if timestamps else 0.0)

@@ -2,11 +2,12 @@
 batched engine; see src/eval_zero_shot.py for the structure.  Per batch the reference draws all
 query index sets first, then all support index sets (eval_few_shot.py:233-241); the same order is
 kept so that a seeded run sees the reference's tasks."""
-import os
+import types
 
 import numpy as np
 import torch
 
+from src._evaluator import EvaluatorBase, _as_tensor, arg_set_to
 from src.methods.few_shot.em_dirichlet import EM_DIRICHLET
 from src.methods.few_shot.hard_em_dirichlet import HARD_EM_DIRICHLET
 from src.methods.few_shot.paddle import PADDLE
@@ -15,11 +16,8 @@ from src.methods.few_shot.tim import ALPHA_TIM, TIM_GD
 from src.methods.few_shot.laplacian_shot import LAPLACIAN_SHOT
 from src.sampler_few_shot import CategoriesSampler_few_shot, SamplerQuery_few_shot, SamplerSupport_few_shot
 from src.task_generator_few_shot import label_permutation, relabel
-from src.utils import Logger, compute_confidence_interval
-from tclip_amd import engine, features, reporting, sharding
-
-def _as_tensor(x):
-    return x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+from src.utils import compute_confidence_interval
+from tclip_amd import engine, reporting, sharding
 
 
 def relabel_batch(x_s, x_q, y_s, y_q, use_softmax_feature):
@@ -86,22 +84,18 @@ _METHODS = {'EM_DIRICHLET': EM_DIRICHLET, 'HARD_EM_DIRICHLET': HARD_EM_DIRICHLET
             'TIM-GD': TIM_GD, 'TIM_GD': TIM_GD}      # tim.yaml's name_method is 'TIM-GD'
 
 
-class Evaluator_few_shot:
-    def __init__(self, device, args, log_file):
-        self.device = device
-        self.args = args
-        self.log_file = log_file
-        self.logger = Logger(__name__, self.log_file)
+class Evaluator_few_shot(EvaluatorBase):
+    _METHODS = _METHODS
+    # the validation-tuned parameter of a method (reference: eval_few_shot.py:130-187).  TIM-GD has no branch in the reference's
+    # set_value_opt_param: nothing of it is tuned
+    _TUNED = reporting.VAL_PARAM
 
     def run_full_evaluation(self, model, preprocess):
         """eval_few_shot.py:42-74 from saved feature files (see Evaluator_zero_shot.run_full_evaluation): the
         support table is the train split, the query table the `used_test_set` split."""
         if getattr(self.args, 'sweep_values', None) is not None:
             return self.run_full_sweep(model)
-        dic_s, dic_q = self.extract_and_load_features(model, None, None)
-        mean_accuracies, mean_times = self.evaluate_tasks(
-            model, dic_s['concat_features'].to('cpu'), dic_s['concat_labels'].long().to('cpu'),
-            dic_q['concat_features'].to('cpu'), dic_q['concat_labels'].long().to('cpu'))
+        mean_accuracies, mean_times = self.evaluate_tasks(model, *self._saved_tables(model))
         if mean_accuracies is not None:
             self.report_results(mean_accuracies, mean_times)
         return mean_accuracies, mean_times
@@ -114,48 +108,21 @@ class Evaluator_few_shot:
         a = self.args
         values = checked_sweep_values(a, a.sweep_values)
         if tables is None:
-            dic_s, dic_q = self.extract_and_load_features(model, None, None)
-            tables = (dic_s['concat_features'].to('cpu'), dic_s['concat_labels'].long().to('cpu'),
-                      dic_q['concat_features'].to('cpu'), dic_q['concat_labels'].long().to('cpu'))
+            tables = self._saved_tables(model)
         accs, mean_time = self.evaluate_sweep(model, *tables, values=values)
-        attr = self._TUNED[a.name_method]
-        saved = a[attr]
-        try:
-            for v, acc in zip(values, accs):
-                a[attr] = v
+        for v, acc in zip(values, accs):
+            with arg_set_to(a, self._TUNED[a.name_method], v):
                 self.report_results(acc, mean_time)
-        finally:
-            a[attr] = saved
         return accs, mean_time
 
     def extract_and_load_features(self, model, dataset, data_loaders):
-        """eval_few_shot.py:91-128, loading only."""
-        root = getattr(self.args, 'results_root', '.')
-        out = []
-        for split in ('train', self.args.used_test_set):
-            path = reporting.saved_feature_path(self.args, split, root)
-            if not os.path.exists(path):
-                raise FileNotFoundError(f"{path} not found: this package runs the reference's evaluation from saved "
-                                        "feature files; extract them with the reference (CLIP is out of scope here)")
-            feats, labels = features.load_features(path)
-            out.append({'concat_features': feats, 'concat_labels': labels})
-        return out[0], out[1]
+        """eval_few_shot.py:91-128, loading only: the train split, then the `used_test_set` split (EvaluatorBase.load_split)."""
+        return self.load_split('train'), self.load_split(self.args.used_test_set)
 
-    def report_results(self, mean_accuracies, mean_times):
-        """eval_few_shot.py:272-338 (validation sweep row, or the test-mode row)."""
-        return reporting.report_results(self.args, mean_accuracies, mean_times, self.logger,
-                                        root=getattr(self.args, 'results_root', '.'))
-
-    def get_method_builder(self, model, device, args, log_file):
-        try:
-            cls = _METHODS[args.name_method]
-        except KeyError:
-            raise ValueError(f"method {args.name_method!r} is not part of the EM-Dirichlet engine")
-        return cls(model=model, device=device, log_file=log_file, args=args)
-
-    # ---- validation-tuned parameter (reference: eval_few_shot.py:130-187)
-    # TIM-GD has no branch in the reference's set_value_opt_param: nothing of it is tuned
-    _TUNED = {'LAPLACIAN_SHOT': 'lmd', 'ALPHA_TIM': 'alpha_value', 'PADDLE': 'lambd', 'BDCSPN': 'temp'}
+    def _saved_tables(self, model):
+        dic_s, dic_q = self.extract_and_load_features(model, None, None)
+        return (dic_s['concat_features'].to('cpu'), dic_s['concat_labels'].long().to('cpu'),
+                dic_q['concat_features'].to('cpu'), dic_q['concat_labels'].long().to('cpu'))
 
     def set_value_opt_param(self, opt_param):
         if self.args.name_method in self._TUNED:
@@ -167,10 +134,7 @@ class Evaluator_few_shot:
         caltech101's, eval_few_shot.py:161-166), rows `param<TAB>acc`, the LAST best row wins.  A missing or
         unreadable file is an error, as in the reference."""
         a = self.args
-        word = '_softmax' if a.use_softmax_feature else '_visual'
-        dataset = 'caltech101' if a.dataset == 'imagenet' else a.dataset
-        name_file = os.path.join(getattr(a, 'results_root', '.'), 'results_few_shot', 'val', str(dataset),
-                                 '{}_s{}.txt'.format(a.name_method + word, a.shots))
+        name_file = reporting.validation_file(a, getattr(a, 'results_root', '.'), 'caltech101' if a.dataset == 'imagenet' else None)
         try:
             params, accs = [], []
             with open(name_file, 'r') as f:
@@ -190,19 +154,42 @@ class Evaluator_few_shot:
         return opt_param
 
     def sample_indices(self, all_labels_support, all_labels_query):
+        """(support, query) index tensors (n_batches, batch_size, n); per batch the reference draws all query index sets first,
+        then all support index sets"""
         a = self.args
-        q_all, s_all, lists = [], [], None
-        for _ in range(int(a.number_tasks / a.batch_size)):
-            sampler = CategoriesSampler_few_shot(a.batch_size, a.k_eff, a.n_class, a.shots, a.n_query,
-                                                 force_query_size=True)
-            if lists is None:             # label -> index lists: no random numbers involved, built once (see eval_zero_shot.py)
-                sampler.create_list_classes(all_labels_support, all_labels_query)
-                lists = (sampler.m_ind_support, sampler.m_ind_query)
-            else:
-                sampler.m_ind_support, sampler.m_ind_query = lists
-            q_all.append(torch.stack(list(SamplerQuery_few_shot(sampler)), 0))
-            s_all.append(torch.stack(list(SamplerSupport_few_shot(sampler)), 0))
-        return torch.stack(s_all, 0), torch.stack(q_all, 0)
+        q_idx, s_idx = self._draw_batches(lambda: CategoriesSampler_few_shot(a.batch_size, a.k_eff, a.n_class, a.shots, a.n_query,
+                                                                             force_query_size=True),
+                                          (all_labels_support, all_labels_query), (SamplerQuery_few_shot, SamplerSupport_few_shot))
+        return s_idx, q_idx
+
+    def _tasks(self, all_features_support, all_labels_support, all_features_query, all_labels_query, indices):
+        """What evaluate_tasks and evaluate_sweep prepare alike: the labels on the host, the (support, query) index tensors -
+        `indices`, or drawn here - and their shape, the feature width W and the class count K: one number on softmax features,
+        the embedding length D and args.n_class on visual features (use_softmax_feature: False; the labels are not re-indexed
+        there).  tables() puts the (support, query) feature tables on the device: called by whoever runs a method on them, so
+        that a sweep which falls back to ordinary runs holds no copy of its own."""
+        a, dev = self.args, torch.device(self.device)
+        feats_s, feats_q = _as_tensor(all_features_support), _as_tensor(all_features_query)
+        t = types.SimpleNamespace(tables=lambda: (feats_s.float().to(dev), feats_q.float().to(dev)),
+                                  lab_s=_as_tensor(all_labels_support).long().cpu(), lab_q=_as_tensor(all_labels_query).long().cpu())
+        t.s_idx, t.q_idx = self.sample_indices(t.lab_s.numpy(), t.lab_q.numpy()) if indices is None else indices
+        t.n_batches, t.N, t.S = t.s_idx.shape
+        t.Q = t.q_idx.shape[2]
+        t.W = feats_q.shape[1]
+        t.K = t.W if a.use_softmax_feature else int(a.n_class)
+        return t
+
+    def _block(self, t, ids=slice(None), relabelled=True):
+        """The tasks of the batches `ids` of `t`: (si (T,S), qi (T,Q), y_s, y_q, rel).  rel = (cols, y_s, y_q): the label
+        re-indexing / column permutation of Tasks_Generator_few_shot.get_task WITHOUT touching the features - softmax features
+        only (visual features keep labels and columns: cols None); rel is None when a support set misses a class, or when not
+        `relabelled`: the tensors are then materialised and relabelled as the reference does."""
+        si, qi = t.s_idx[ids].reshape(-1, t.S), t.q_idx[ids].reshape(-1, t.Q)
+        y_s, y_q = t.lab_s[si.reshape(-1)].view(-1, t.S), t.lab_q[qi.reshape(-1)].view(-1, t.Q)
+        rel = None
+        if relabelled:
+            rel = relabel_indices(y_s, y_q, t.K) if self.args.use_softmax_feature else (None, y_s, y_q)
+        return si, qi, y_s, y_q, rel
 
     def evaluate_sweep(self, model, all_features_support, all_labels_support, all_features_query, all_labels_query, values,
                        indices=None):
@@ -218,46 +205,30 @@ class Evaluator_few_shot:
         attr = self._TUNED[a.name_method]
         self.logger.info("=> Runnning a sweep of {} over {} with method {} on {} dataset".format(
             attr, values, a.name_method, a.used_test_set))
-        lab_s = _as_tensor(all_labels_support).long().cpu()
-        lab_q = _as_tensor(all_labels_query).long().cpu()
-        s_idx, q_idx = self.sample_indices(lab_s.numpy(), lab_q.numpy()) if indices is None else indices
-        n_batches, N, S = s_idx.shape
-        Q = q_idx.shape[2]
-        si, qi = s_idx.reshape(-1, S), q_idx.reshape(-1, Q)
-        y_s, y_q = lab_s[si.reshape(-1)].view(-1, S), lab_q[qi.reshape(-1)].view(-1, Q)
-        W = _as_tensor(all_features_query).shape[1]
-        K = W if a.use_softmax_feature else int(a.n_class)
-        rel = relabel_indices(y_s, y_q, K) if a.use_softmax_feature else (None, y_s, y_q)
-        saved = a[attr]
-        try:
-            if rel is None:
-                accs, times = [], []
-                for v in values:
-                    a[attr] = v
-                    acc, t = self.evaluate_tasks(model, all_features_support, all_labels_support, all_features_query,
-                                                 all_labels_query, indices=(s_idx, q_idx))
+        t = self._tasks(all_features_support, all_labels_support, all_features_query, all_labels_query, indices)
+        si, qi, _, _, rel = self._block(t)
+        accs, times, methods = [], [], []
+        for v in values:
+            with arg_set_to(a, attr, v):
+                if rel is None:
+                    acc, time = self.evaluate_tasks(model, all_features_support, all_labels_support, all_features_query,
+                                                    all_labels_query, indices=(t.s_idx, t.q_idx))
                     accs.append(acc)
-                    times.append(t)
-                return np.asarray(accs), float(np.mean(times))
-            methods = []
-            for v in values:                       # one object per value, built as a run with that value builds it
-                a[attr] = v
-                methods.append(self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file))
-        finally:
-            a[attr] = saved
-        dev = torch.device(self.device)
-        tab_s = _as_tensor(all_features_support).float().to(dev)
-        tab_q = _as_tensor(all_features_query).float().to(dev)
-        cols, y_s, y_q = rel
-        type(methods[0]).run_tables_sweep(methods, table_s=tab_s, s_idx=si, table_q=tab_q, q_idx=qi, cols=cols, y_s=y_s.to(dev),
-                                          y_q=y_q.to(dev), n_batches=n_batches)
-        accs, times = [], []
-        for m in methods:
-            logs = m.get_logs()
-            acc = torch.from_numpy(logs['acc'][:, -1].copy()).view(n_batches, N).float().numpy()      # as sharding.method_parts
-            accs.append(np.asarray([compute_confidence_interval(acc[b])[0] for b in range(n_batches)]).mean())
-            times.append(float(logs['timestamps']))
-        self.last_methods = methods
+                    times.append(time)
+                else:                              # one object per value, built as a run with that value builds it
+                    methods.append(self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file))
+        if rel is not None:
+            cols, y_s, y_q = rel
+            dev = torch.device(self.device)
+            tab_s, tab_q = t.tables()
+            type(methods[0]).run_tables_sweep(methods, table_s=tab_s, s_idx=si, table_q=tab_q, q_idx=qi, cols=cols,
+                                              y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=t.n_batches)
+            for m in methods:
+                logs = m.get_logs()
+                acc = sharding.task_accuracies(logs, t.n_batches, t.N).numpy()
+                accs.append(np.asarray([compute_confidence_interval(acc[b])[0] for b in range(t.n_batches)]).mean())
+                times.append(float(logs['timestamps']))
+            self.last_methods = methods
         return np.asarray(accs), float(np.mean(times))
 
     def evaluate_tasks(self, model, all_features_support, all_labels_support, all_features_query, all_labels_query,
@@ -266,19 +237,10 @@ class Evaluator_few_shot:
         a = self.args
         self.logger.info("=> Runnning evaluation with method {} on {} dataset".format(
             a.name_method, getattr(a, 'used_test_set', 'test')))
+        t = self._tasks(all_features_support, all_labels_support, all_features_query, all_labels_query, indices)
+        tab_s, tab_q = t.tables()
         dev = torch.device(self.device)
-        tab_s = _as_tensor(all_features_support).float().to(dev)
-        tab_q = _as_tensor(all_features_query).float().to(dev)
-        lab_s = _as_tensor(all_labels_support).long().cpu()
-        lab_q = _as_tensor(all_labels_query).long().cpu()
-        s_idx, q_idx = self.sample_indices(lab_s.numpy(), lab_q.numpy()) if indices is None else indices
-        n_batches, N, S = s_idx.shape
-        Q = q_idx.shape[2]
-        mine = sharding.my_batches(n_batches)
-        # the feature width and the class count: one number on softmax features, the embedding length D and args.n_class on
-        # visual features (use_softmax_feature: False; PADDLE, BDCSPN and TIM-GD run there, the labels are not re-indexed)
-        W = tab_q.shape[1]
-        K = W if a.use_softmax_feature else int(a.n_class)
+        mine = sharding.my_batches(t.n_batches)
         # The parameter tuned on the validation split, when the test split is evaluated.  The reference builds the
         # method of a batch FIRST and reads the sweep file afterwards (eval_few_shot.py:250-254), and every method
         # copies its parameter in __init__ (paddle.py:26, bdcspn.py:18, tim.py:198, laplacian_shot.py:32): its batch 0
@@ -292,7 +254,6 @@ class Evaluator_few_shot:
                 first_method = self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file)
             self.set_method_opt_param()
         method = self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file)
-        timestamps, parts = [], None
         runs = [(first_method, mine[:1]), (method, mine[1:])] if first_method is not None else [(method, mine)]
         # batches_per_call (absent or 0: all batches of a run in one engine call): consecutive groups of at most that many
         # batches, each with a method object of its own, as the reference builds one per batch - what bounds the (T,S,W)
@@ -306,62 +267,34 @@ class Evaluator_few_shot:
             step = per_call if per_call > 0 else max(len(ids), 1)
             for g0 in range(0, len(ids), step):
                 groups.append((m if g0 == 0 else None, ids[g0:g0 + step]))
-        materialise = bool(getattr(a, 'materialise_tasks', False))
+        timestamps, parts = [], None
         ran = None                        # the last method object that actually executed on this rank
         for m, ids in groups:
             if m is None:
                 m = self.get_method_builder(model=model, device=self.device, args=a, log_file=self.log_file)
             ran = m
-            si, qi = s_idx[ids].reshape(-1, S), q_idx[ids].reshape(-1, Q)
-            y_s, y_q = lab_s[si.reshape(-1)].view(-1, S), lab_q[qi.reshape(-1)].view(-1, Q)
-            # label re-indexing / column permutation of Tasks_Generator_few_shot.get_task WITHOUT touching the features: softmax
-            # features only (visual features keep labels and columns); None when a support set misses a class, and the tensors
-            # are then materialised as the reference does
-            cols, rel = None, None
-            if not materialise:
-                rel = relabel_indices(y_s, y_q, K) if a.use_softmax_feature else (None, y_s, y_q)
-            # The EM-Dirichlet classes and PADDLE read the task rows from the tables through the index tensors (label flip and
-            # column permutation inside the kernels): x_s (T,S,K) - 1.6 GB per 100 tasks at K = 1000, 4 shots - is never built
-            # in_place_support (absent or False: the route above and below as it always was): BDCSPN and LAPLACIAN_SHOT, whose
-            # first kernels normalise the task rows into their workspace, read them from the tables too
-            in_place = m.reads_rows_in_place(a.use_softmax_feature)
-            if not in_place and getattr(a, 'in_place_support', False) and hasattr(m, 'can_read_rows_in_place'):
-                in_place = m.can_read_rows_in_place(a.use_softmax_feature)
-            # in_place_loop (absent or False: as above): TIM-GD and ALPHA_TIM, which read their task rows in both GEMMs of EVERY
-            # Adam step, read them from the tables too - a switch of its own, since they pay the indirection per step
-            if not in_place and getattr(a, 'in_place_loop', False) and hasattr(m, 'can_read_rows_in_place_per_step'):
-                in_place = m.can_read_rows_in_place_per_step(a.use_softmax_feature)
-            if rel is not None:
-                cols, y_s, y_q = rel
-            if rel is not None and in_place:
-                m.run_tables(table_s=tab_s, s_idx=si, table_q=tab_q, q_idx=qi, cols=cols, y_s=y_s.to(dev), y_q=y_q.to(dev),
-                             n_batches=len(ids))
+            # the route (FewShotMixin.rows_in_place has the table).  materialise_tasks: no rel, the reference's route
+            si, qi, y_s, y_q, rel = self._block(t, ids, relabelled=not getattr(a, 'materialise_tasks', False))
+            in_place = rel is not None and m.rows_in_place(a)
+            if rel is None:
+                x_s = engine.gather_rows(tab_s, si.reshape(-1)).view(len(ids) * t.N, t.S, t.W)
+                x_q = engine.gather_rows(tab_q, qi.reshape(-1)).view(len(ids) * t.N, t.Q, t.W)
+                x_s, x_q, y_s, y_q = relabel_batch(x_s, x_q, y_s, y_q, a.use_softmax_feature)
             else:
-                if rel is not None:
-                    # the fused task builder: `table[idx][..., cols]` in one device pass, the re-indexed labels from the same call
-                    x_s = engine.gather_task_rows(tab_s, si, cols)
-                    x_q = engine.gather_task_rows(tab_q, qi, cols)
-                else:
-                    x_s = engine.gather_rows(tab_s, si.reshape(-1)).view(len(ids) * N, S, W)
-                    x_q = engine.gather_rows(tab_q, qi.reshape(-1)).view(len(ids) * N, Q, W)
-                    x_s, x_q, y_s, y_q = relabel_batch(x_s, x_q, y_s, y_q, a.use_softmax_feature)
+                cols, y_s, y_q = rel
+                if not in_place:      # the fused task builder: `table[idx][..., cols]` in one device pass
+                    x_s, x_q = engine.gather_task_rows(tab_s, si, cols), engine.gather_task_rows(tab_q, qi, cols)
+            labels = dict(y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
+            if in_place:
+                # the class reads the task rows from the tables through the index tensors (label flip and column permutation
+                # inside the kernels): x_s (T,S,K) - 1.6 GB per 100 tasks at K = 1000, 4 shots - is never built
+                m.run_tables(table_s=tab_s, s_idx=si, table_q=tab_q, q_idx=qi, cols=cols, **labels)
+            else:
                 # BDCSPN normalises the features in run_task, before run_method (few_shot/bdcspn.py:165-166): run_batch does both
-                m.run_batch(support=x_s, query=x_q, y_s=y_s.to(dev), y_q=y_q.to(dev), n_batches=len(ids))
+                m.run_batch(support=x_s, query=x_q, **labels)
             logs = m.get_logs()
-            parts = sharding.concat_parts(parts, sharding.method_parts(a, m, logs, len(ids), N, Q, dev))
+            parts = sharding.concat_parts(parts, sharding.method_parts(a, m, logs, len(ids), t.N, t.Q, dev))
             timestamps += [float(logs['timestamps'])] * len(ids)
-        if parts is None:      # more ranks than batches: this rank only takes part in the gather
-            parts = sharding.method_parts(a, None, None, 0, N, Q, dev)
-        got = sharding.gather_packed(parts, n_batches)
         # a rank whose only batch is batch 0 of a tuned run executes `first_method` alone: `method` never ran there and
         # carries no records (mm_iters None); a rank without a batch keeps the freshly built object
-        self.last_method = ran if ran is not None else method
-        if got is None:
-            return None, None
-        acc = got['acc'].numpy()
-        results_task = [compute_confidence_interval(acc[b])[0] for b in range(n_batches)]
-        self.last_task_accuracies = acc
-        self.last_task_predictions = got['preds'].view(n_batches, N, Q).numpy()
-        self.last_batch_criterions = got['criterions'].numpy() if 'criterions' in got else None
-        self.last_batch_mm_iters = got['mm_iters'].numpy() if 'mm_iters' in got else None
-        return np.asarray(results_task).mean(), (float(np.mean(timestamps)) if timestamps else 0.0)
+        return self._gathered(parts, t.n_batches, t.N, t.Q, ran if ran is not None else method, timestamps)

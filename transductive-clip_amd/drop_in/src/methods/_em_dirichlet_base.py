@@ -227,8 +227,34 @@ class FewShotMixin:
     def can_read_rows_in_place_per_step(cls, use_softmax_feature):
         return ("softmax" if use_softmax_feature else "visual") in cls.IN_PLACE_LOOP
 
+    @classmethod
+    def rows_in_place(cls, args):
+        """Whether the task-batch loop (Evaluator_few_shot.evaluate_tasks) hands this class the feature tables and the index
+        tensors (run_tables) instead of task tensors (run_batch).  The whole route of a group of batches:
+
+          materialise_tasks                              gather_rows + relabel_batch -> run_batch    (the reference's route)
+          softmax features, a support set misses a class gather_rows + relabel_batch -> run_batch    (relabel_indices: None)
+          otherwise, rows_in_place(args)                 run_tables                                  (no task tensor is built)
+          otherwise                                      gather_task_rows, the fused builder -> run_batch
+
+        and rows_in_place, by class and feature kind (visual: use_softmax_feature False):
+
+          EM_DIRICHLET, HARD_EM_DIRICHLET   softmax            always    (IN_PLACE_FEATURES; visual features are refused)
+          PADDLE                            softmax, visual    always    (IN_PLACE_FEATURES)
+          BDCSPN                            softmax, visual    with in_place_support    (IN_PLACE_SUPPORT)
+          LAPLACIAN_SHOT                    softmax            with in_place_support    (IN_PLACE_SUPPORT; visual: refused)
+          TIM_GD                            softmax, visual    with in_place_loop       (IN_PLACE_LOOP: the rows are read per step)
+          ALPHA_TIM                         softmax            with in_place_loop       (IN_PLACE_LOOP; visual: refused)
+
+        A switch that does not belong to the class changes nothing.  evaluate_sweep always reads the rows in place."""
+        soft = args.use_softmax_feature
+        return (cls.reads_rows_in_place(soft)
+                or bool(getattr(args, "in_place_support", False)) and cls.can_read_rows_in_place(soft)
+                or bool(getattr(args, "in_place_loop", False)) and cls.can_read_rows_in_place_per_step(soft))
+
     # ---- a sweep of the class's validation-tuned parameter over the same tasks (Evaluator_few_shot.evaluate_sweep) ----------
-    # The four tunable classes name the attribute (SWEEP_ATTR) and split their `_run` into `_banner` and `_finish`, so that
+    # The four tunable classes take the attribute's name from reporting.VAL_PARAM (SWEEP_ATTR) and split their `_run` into
+    # `_banner` and `_finish`, so that
     # the reference's bookkeeping of one run can follow an engine call that served several objects.
     SWEEP_ATTR = None
 

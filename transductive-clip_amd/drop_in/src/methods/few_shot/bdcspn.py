@@ -11,12 +11,13 @@ import torch
 
 from src.methods._em_dirichlet_base import FewShotMixin, MethodBase
 from tclip_amd import engine
+from tclip_amd.reporting import VAL_PARAM
 
 
 class BDCSPN(FewShotMixin, MethodBase):
     LOGGER_NAME = __name__
     IN_PLACE_SUPPORT = ("softmax", "visual")
-    SWEEP_ATTR = "temp"
+    SWEEP_ATTR = VAL_PARAM["BDCSPN"]
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)

@@ -11,12 +11,13 @@ import numpy as np
 
 from src.methods._em_dirichlet_base import FewShotMixin, MethodBase
 from tclip_amd import engine
+from tclip_amd.reporting import VAL_PARAM
 
 
 class LAPLACIAN_SHOT(FewShotMixin, MethodBase):
     LOGGER_NAME = __name__
     IN_PLACE_SUPPORT = ("softmax",)          # run_method refuses visual features, and so does run_tables
-    SWEEP_ATTR = "lmd"
+    SWEEP_ATTR = VAL_PARAM["LAPLACIAN_SHOT"]
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)

@@ -8,6 +8,7 @@ args.num_classes_test, as in the reference; the reference's text-prompt u (:186-
 the first u_update before anything reads it, so no text features are asked for."""
 from src.methods._em_dirichlet_base import EMDirichletBase, FewShotMixin
 from tclip_amd import engine
+from tclip_amd.reporting import VAL_PARAM
 
 
 class BASE(FewShotMixin, EMDirichletBase):
@@ -18,7 +19,7 @@ class PADDLE(BASE):
     BANNER = "PADDLE"
     ARG_DEFAULTS = {"iter_mm": 0}          # paddle.yaml has no iter_mm
     IN_PLACE_FEATURES = ("softmax", "visual")
-    SWEEP_ATTR = "lambd"
+    SWEEP_ATTR = VAL_PARAM["PADDLE"]
 
     def __init__(self, model, device, log_file, args):
         super().__init__(model=model, device=device, log_file=log_file, args=args)

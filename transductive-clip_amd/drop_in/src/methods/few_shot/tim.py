@@ -9,6 +9,7 @@ row sets from the feature tables in place in every Adam step (tclip_tim_gd_run_t
 without the (T,S,D) and (T,Q,D) tensors."""
 from src.methods._em_dirichlet_base import EMDirichletBase, FewShotMixin
 from tclip_amd import engine
+from tclip_amd.reporting import VAL_PARAM
 
 
 # tim.yaml and alpha_tim.yaml have no iter_mm; k_eff only feeds the unused EM-Dirichlet lambd of the shared base
@@ -61,7 +62,7 @@ class ALPHA_TIM(BASE):
     BANNER = "ALPHA_TIM"
     ARG_DEFAULTS = _ARG_DEFAULTS
     IN_PLACE_LOOP = ("softmax",)
-    SWEEP_ATTR = "alpha_value"
+    SWEEP_ATTR = VAL_PARAM["ALPHA_TIM"]
     _VISUAL = "ALPHA_TIM here takes probability features (use_softmax_feature: True, feature dimension = n_class)"
 
     def __init__(self, model, device, log_file, args):

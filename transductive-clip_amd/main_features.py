@@ -158,8 +158,7 @@ def main(argv=None, keep_process_group=False):
         ev = Evaluator_few_shot(device=device, args=args, log_file=None)
         if sweep is not None:
             accs, t = ev.run_full_sweep(None, (feats_s, labels_s, feats_q, labels_q))
-            path = os.path.join(ns.results_root, "results_few_shot", "val", str(args.dataset), "{}_s{}.txt".format(
-                args.name_method + ("_softmax" if args.use_softmax_feature else "_visual"), args.shots))
+            path = reporting.validation_file(args, ns.results_root)
             for v, acc in zip(sweep, accs):
                 print(f"{reporting.VAL_PARAM[args.name_method]} = {v}: mean accuracy {100 * float(acc):.2f} %")
             print(f"mean time/task statistic {t:.3e} s  -> {path}")

@@ -16,48 +16,45 @@ def saved_feature_path(args, split, root="."):
     return os.path.join(root, "data", str(args.dataset), "saved_features", name)
 
 
+def _result_file(args, root, split, dataset, few):
+    """results_few_shot/<split>/<dataset>/<METHOD>_<softmax|visual>_s<shots>.txt; zero-shot runs (not `few`):
+    results_zero_shot/... and ..._<shots>shot.txt"""
+    name = (("{}_s{}.txt" if few else "{}_{}shot.txt")
+            .format(args.name_method + ("_softmax" if args.use_softmax_feature else "_visual"), args.shots))
+    return os.path.join(root, "results_few_shot" if few else "results_zero_shot", str(split), str(dataset), name)
+
+
+def validation_file(args, root=".", dataset=None):
+    """The sweep file of a tunable few-shot method, always in the few-shot layout: validation runs append their
+    `val_param<TAB>acc` rows to it, test runs read their parameter from it.  `dataset`: another dataset's file (imagenet
+    borrows caltech101's, eval_few_shot.py:161-166)."""
+    return _result_file(args, root, "val", args.dataset if dataset is None else dataset, True)
+
+
+def _append_row(name_file, header, row):
+    os.makedirs(os.path.dirname(name_file), exist_ok=True)
+    new = not os.path.isfile(name_file)
+    with open(name_file, "w" if new else "a") as f:
+        f.write((header if new else "") + row + "\t\n")
+    return name_file
+
+
 def report_results(args, mean_accuracies, mean_times, logger=None, root="."):
     """Appends one row to results_{zero,few}_shot/<used_test_set>/<dataset>/<METHOD>_<softmax|visual>_...txt
     exactly as the reference's Evaluator_*.report_results does when `save_results` is set; returns
     the file path (or None when nothing is written)."""
     few = int(getattr(args, "shots", 0)) > 0
-    word = "_softmax" if args.use_softmax_feature else "_visual"
     info = logger.info if logger is not None else (lambda *_: None)
     info("----- Final results -----")
     info("{}-shot mean test accuracy over {} tasks: {}".format(args.shots, args.number_tasks, mean_accuracies))
-    kind = "results_few_shot" if few else "results_zero_shot"
-    path = os.path.join(root, "{}/{}/{}".format(kind, args.used_test_set, args.dataset))
     if few and args.used_test_set == "val":                 # eval_few_shot.py:282-302: written whatever save_results says
         if args.name_method not in VAL_PARAM:
             raise AttributeError("method {} has no validation parameter".format(args.name_method))  # reference: self.val_param unset
-        val_param = args[VAL_PARAM[args.name_method]]
-        name_file = os.path.join(path, "{}_s{}.txt".format(args.name_method + word, args.shots))
-        os.makedirs(path, exist_ok=True)
-        new = not os.path.isfile(name_file)
-        with open(name_file, "w" if new else "a") as f:
-            if new:
-                f.write("val_param\tacc\n")
-            f.write(str(val_param) + "\t")
-            f.write(str(round(100 * float(mean_accuracies), 2)) + "\t")
-            f.write("\n")
-        return name_file
+        return _append_row(validation_file(args, root), "val_param\tacc\n",
+                           "{}\t{}".format(args[VAL_PARAM[args.name_method]], round(100 * float(mean_accuracies), 2)))
     info("{}-shot mean time over {} tasks: {}".format(args.shots, args.number_tasks, mean_times))
     if not getattr(args, "save_results", False) or (few and args.used_test_set != "test"):
         return None
-    if few:
-        var = "{}\t{}\t{}".format(args.shots, args.n_query, args.k_eff)
-        names = "shots\tn_query\tk_eff\tacc\n"
-        name_file = os.path.join(path, "{}_s{}.txt".format(args.name_method + word, args.shots))
-    else:
-        var = "{}\t{}\t{}".format(args.shots, args.n_query, args.number_tasks)
-        names = "shots\tn_query\tn_task\tacc\n"
-        name_file = os.path.join(path, "{}_{}shot.txt".format(args.name_method + word, args.shots))
-    os.makedirs(path, exist_ok=True)
-    new = not os.path.isfile(name_file)
-    with open(name_file, "w" if new else "a") as f:
-        if new:
-            f.write(names + "\t" + "\n")
-        f.write(var + "\t")
-        f.write(str(round(100 * float(mean_accuracies), 1)) + "\t")
-        f.write("\n")
-    return name_file
+    names, last = ("shots\tn_query\tk_eff\tacc\n", args.k_eff) if few else ("shots\tn_query\tn_task\tacc\n", args.number_tasks)
+    return _append_row(_result_file(args, root, args.used_test_set, args.dataset, few), names + "\t\n",
+                       "{}\t{}\t{}\t{}".format(args.shots, args.n_query, last, round(100 * float(mean_accuracies), 1)))

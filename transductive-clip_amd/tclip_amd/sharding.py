@@ -30,6 +30,11 @@ _PER_BATCH_RECORDS = {'EM_DIRICHLET': ('criterions', 'mm_iters'), 'HARD_EM_DIRIC
 _PER_TASK_CRITERIONS = ('TIM-GD', 'TIM_GD')
 
 
+def task_accuracies(logs, n_local, N):
+    """(n_local, N) f32: every task's accuracy after the last recorded step of a method's logs"""
+    return torch.from_numpy(logs['acc'][:, -1].copy()).view(n_local, N).float()
+
+
 def method_parts(args, method, logs, n_local, N, Q, dev):
     """This rank's results of one method run over `n_local` batches of N tasks, as the parts gather_packed moves
     (SURVEY.md section 8e): `preds` (N*Q) int32 - the class assigned to every query, after the cluster-to-class
@@ -52,7 +57,7 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
         if p is None:
             p = method.preds
         parts = {'preds': p.reshape(n_local, N * Q).to(torch.int32),
-                 'acc': torch.from_numpy(logs['acc'][:, -1].copy()).view(n_local, N).float()}
+                 'acc': task_accuracies(logs, n_local, N)}
         if 'criterions' in records:
             parts['criterions'] = torch.as_tensor(method.criterions_per_batch, dtype=torch.float32).view(n_local, iters)
         if 'mm_iters' in records:
