@@ -120,6 +120,33 @@ int tclip_em_dirichlet_run_tasks(const tclip_problem* p, const tclip_task_source
                                  float* u, float* v, float* alpha, int32_t* preds, float* criterions,
                                  int32_t* mm_iters, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same two loops, each batch stopped once its argmax assignment stands still (opt-in; the plain entries run every
+ * iteration).  After outer iteration `it` (0-based) of batch b
+ *     changes[b, it] = number of (task, query) pairs of the batch whose preds differ from those after iteration it - 1,
+ *     changes[b, 0]  = N * Q (no iteration precedes it),
+ * and the batch is stable after the first `it` with changes[b, it-patience+1 .. it] all 0.  Then outer_iters[b] = it + 1
+ * (at least patience + 1) and nothing of batch b is written any more: u, v, alpha and preds keep their values, and
+ * criterions[b, j], mm_iters[b, j] and changes[b, j] are 0 for j >= outer_iters[b] (the entry zero-fills the three arrays).  A
+ * batch that never qualifies has outer_iters[b] = iters.  The decision is taken on the device (no host synchronisation).
+ * Contract: with s = outer_iters[b], the slices u, v, alpha, preds, criterions[b, :s], mm_iters[b, :s] of batch b are bit for
+ * bit what the plain entry returns for that batch alone with iters = s - zero-shot and few-shot, soft and hard, dense rows
+ * and table rows, whatever other batches share the call and however it is split over stream groups.
+ *   patience    >= 1
+ *   outer_iters device [B]        i32 out
+ *   changes     device [B, iters] i32 out
+ * Checks are those of the plain entries; patience < 1, a null outer_iters or changes are TCLIP_ERR_ARG before any launch (the
+ * error text names the argument).  Workspace: tclip_em_dirichlet_until_stable_workspace_bytes(p) bytes (0 on bad input),
+ * 256-byte aligned; it is tclip_workspace_bytes(p) plus, per stream group, the previous predictions and two words per batch. */
+size_t tclip_em_dirichlet_until_stable_workspace_bytes(const tclip_problem* p);
+int tclip_em_dirichlet_run_until_stable(const tclip_problem* p, const float* x_q, const float* x_s, const int64_t* y_s,
+                                        int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
+                                        int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+int tclip_em_dirichlet_run_tasks_until_stable(const tclip_problem* p, const tclip_task_source* src, const int64_t* y_s,
+                                              int32_t patience, float* u, float* v, float* alpha, int32_t* preds,
+                                              float* criterions, int32_t* mm_iters, int32_t* outer_iters, int32_t* changes,
+                                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Range check of DEVICE-resident index tensors before tclip_em_dirichlet_run_tasks / tclip_gather_rows - what torch's own
  * `all_features_query[indices, :]` (src/eval_zero_shot.py:160-163, src/eval_few_shot.py:233-241) does by raising IndexError:
  *   idx  device [n_idx]  i64, every value must lie in [0, n_rows)         (NULL with n_idx == 0: nothing to check)

@@ -19,6 +19,8 @@
 //   k_logits          (alpha-1) . log z contraction for rows that changed          (:37-38)
 //   k_softmax         u = softmax_k(logit + lambd*v/Q), argmax, one-hot if hard    (:142-143)
 //   k_criterion(+_mean) per-task relative change of alpha; alpha_old <- alpha      (:236-239)
+//   k_assign_changes  the until-stable entries only: predictions changed since the last iteration, per batch; a batch whose
+//                     predictions stand still is marked done and skipped by every kernel above from then on
 //
 // The other methods behind the same boundary reuse k_cluster_sizes, k_mstats*,
 // k_softmax and add:
@@ -254,11 +256,14 @@ __global__ void k_support_stats(RowSrc src, const int64_t* __restrict__ ys, int 
 // ------------------------------------------------------------------------------------------
 // cs[t,k] = sum_q u[t,q,k] (torch outer-sum order), live mask, v = log(cs/Q + eps) + 1.
 // Also invalidates the dead-row cache of rows that are alive.
+// `done` (optional, the until-stable driver): a row of a batch b with done[b] set is left as it is; rows_per_batch = N * K.
 __global__ void k_cluster_sizes(const float* __restrict__ u, int T, int Q, int K, int zero_shot,
                                 float* __restrict__ cs, uint8_t* __restrict__ live, float* __restrict__ v,
-                                int32_t* __restrict__ cache_len) {
+                                int32_t* __restrict__ cache_len, const int32_t* __restrict__ done = nullptr,
+                                int rows_per_batch = 0) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)T * K) return;
+    if (done && done[i / rows_per_batch]) return;
     const int t = i / K, k = i % K;
     const float* ut = u + (size_t)t * Q * K;
     const float c = dsum_outer(Q, k, K, [&](int q) { return ut[(size_t)q * K + k]; });
@@ -397,13 +402,15 @@ __global__ __launch_bounds__(64) void k_mstats_rows(const float* __restrict__ u,
 // Row lists for one outer iteration.  live_rows: rows whose alpha will change (k_mm_live iterates
 // them, and their E-step terms must be recomputed); dead_rows: dead rows whose cached stop-test
 // terms are incomplete (k_mm_live<.., true> iterates them).  Order inside the lists is irrelevant to the results.
+// `done` (optional, the until-stable driver): no row of a batch b with done[b] set is listed; rows_per_batch = N * K.
 __device__ __forceinline__ int lanes_below_mask(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
 
 __global__ void k_build_rows(const uint8_t* __restrict__ live, const int32_t* __restrict__ cache_len, int n_rows,
                              int n_checks, int32_t* __restrict__ dead_rows, int32_t* __restrict__ live_rows,
-                             int32_t* __restrict__ n_dead, int32_t* __restrict__ n_live) {
+                             int32_t* __restrict__ n_dead, int32_t* __restrict__ n_live,
+                             const int32_t* __restrict__ done = nullptr, int rows_per_batch = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in = i < n_rows;
+    const bool in = i < n_rows && !(done && done[i / rows_per_batch]);
     const bool alive = in && live[i];
     const bool need = in && !alive && n_checks > 0 && cache_len[i] < n_checks;
     // one atomic per wavefront and list: the 64 consecutive rows of a wavefront (same task, neighbouring classes) stay
@@ -1996,12 +2003,15 @@ __global__ __launch_bounds__(256) void k_cov_logits_rows(const float* __restrict
 // One 16-lane group per (task, query) row.  Also argmax (first maximum; pick_min: first minimum,
 // hard_kmeans.py:193) and the hard one-hot.  u may be logit0 itself (each entry is read before it
 // is written, by the same thread).
+// `done` (optional, the until-stable driver): a row of a batch b with done[b] set keeps its u and preds; rows_per_batch = N * Q.
 __global__ __launch_bounds__(256) void k_softmax(const float* logit0, const float* __restrict__ v, int TQ,
                                                  int Q, int K, float lambd, int hard, int pick_min, float* u,
-                                                 int32_t* __restrict__ preds) {
+                                                 int32_t* __restrict__ preds, const int32_t* __restrict__ done = nullptr,
+                                                 int rows_per_batch = 0) {
     const int lane = threadIdx.x & 15;
     const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     if (r >= TQ) return;
+    if (done && done[r / rows_per_batch]) return;       // the whole 16-lane group of a row leaves together
     const int t = r / Q;
     const float* x = logit0 + (size_t)r * K;
     const float* vt = v ? v + (size_t)t * K : nullptr;
@@ -2069,10 +2079,13 @@ __global__ __launch_bounds__(256) void k_softmax(const float* logit0, const floa
 // 10^6 elements, oracle/mathcheck.cpp::mc_norm8).  One wavefront per task; lane j (and its seven copies 8 i + j) owns
 // accumulator j.  The chain of n/8 dependent FMAs per accumulator is inherent; everything else is kept off it (main loop
 // below).  (A variant with four tasks per wavefront and DPP operands had a quarter of the wavefronts and was slower.)
+// `done` (optional, the until-stable driver): a task of a batch b with done[b] set keeps its alpha_old and ratio; rows_per_batch = N.
 __global__ __launch_bounds__(64) void k_criterion(const float* __restrict__ alpha, float* __restrict__ alpha_old, int K, int T,
-                                                  float* __restrict__ ratio) {
+                                                  float* __restrict__ ratio, const int32_t* __restrict__ done = nullptr,
+                                                  int rows_per_batch = 0) {
     const int t = blockIdx.x, lane = threadIdx.x, j = lane & 7;
     if (t >= T) return;
+    if (done && done[t / rows_per_batch]) return;
     const size_t n = (size_t)K * K, base = (size_t)t * n, nv = n & ~(size_t)7;
     float acc_d = 0.0f, acc_o = 0.0f;                         // meaningful in lanes 0..7
     auto step = [&](float o, float c, int groups) {           // `groups` whole groups of eight elements, in order
@@ -2167,12 +2180,55 @@ __global__ __launch_bounds__(64) void k_criterion(const float* __restrict__ alph
     }
 }
 
-__global__ void k_criterion_mean(const float* __restrict__ ratio, int N, int force_zero, float* __restrict__ out, int stride) {
+__global__ void k_criterion_mean(const float* __restrict__ ratio, int N, int force_zero, float* __restrict__ out, int stride,
+                                 const int32_t* __restrict__ done = nullptr) {
     const int b = blockIdx.x;
     if (threadIdx.x != 0) return;
+    if (done && done[b]) return;
     const float* r = ratio + (size_t)b * N;
     const float s = dsum_inner_serial(N, [&](int i) { return r[i]; });
     out[(size_t)b * stride] = force_zero ? 0.0f : s / (float)N;
+}
+
+// ------------------------------------------------------------------------------------------
+// The until-stable driver's decision, one block per batch, after k_softmax of outer iteration `it`:
+//   changes[b, it] = number of (task, query) pairs of the batch whose prediction differs from the one after iteration it - 1
+//                    (prev_preds starts at -1, so iteration 0 counts all n = N * Q of them);  prev_preds <- preds;
+//   quiet[b]       = length of the run of change-free iterations that ends here;
+//   quiet[b] reaches `patience`: done[b] <- 1, outer_iters[b] <- it + 1.  From then on every kernel of the loop leaves the
+//   batch alone (this one too: its changes stay as the entry zero-filled them).
+// A batch still running in the last iteration gets outer_iters[b] = it + 1 = iters.
+__global__ __launch_bounds__(256) void k_assign_changes(const int32_t* __restrict__ preds, int32_t* __restrict__ prev_preds, int n,
+                                                        int it, int is_last, int patience, int32_t* __restrict__ changes,
+                                                        int stride, int32_t* __restrict__ quiet, int32_t* __restrict__ done,
+                                                        int32_t* __restrict__ outer_iters) {
+    const int b = blockIdx.x;
+    if (done[b]) return;
+    const size_t base = (size_t)b * n;
+    int diff = 0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int32_t now = preds[base + i];
+        diff += now != prev_preds[base + i] ? 1 : 0;
+        prev_preds[base + i] = now;
+    }
+    __shared__ int sh[256];
+    sh[threadIdx.x] = diff;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        changes[(size_t)b * stride + it] = sh[0];
+        const int run = sh[0] == 0 ? quiet[b] + 1 : 0;
+        quiet[b] = run;
+        if (run >= patience) {
+            done[b] = 1;
+            outer_iters[b] = it + 1;
+        } else if (is_last) {
+            outer_iters[b] = it + 1;
+        }
+    }
 }
 
 // PADDLE prototype initialisation (few_shot/paddle.py:127-140): class means of the support set.
@@ -3592,11 +3648,28 @@ const char* tclip_last_error(void) { return g_err; }
 
 namespace tclip {
 
+// The until-stable entries' part of a group of batches (tclip_em_dirichlet_run_until_stable): the outputs of the group's
+// batches and its state in the group's workspace slice, behind the plain layout.
+struct StableStop {
+    int patience;
+    int32_t* outer_iters;   // [B]
+    int32_t* changes;       // [B, iters]
+    int32_t* prev_preds;    // [T, Q] the predictions after the previous outer iteration, -1 before the first
+    int32_t* quiet;         // [B] change-free outer iterations in a row
+    int32_t* done;          // [B] the batch is stable: nothing of it is written any more
+};
+static size_t stable_state_bytes(const tclip_problem& p) {
+    const size_t B = p.n_batches, T = B * p.tasks_per_batch;
+    return align_up(T * p.n_query * 4) + 2 * align_up(B * 4);
+}
+
 // Enqueues the whole loop for `p.n_batches` consecutive batches on stream `st`.  `crit_stride` is
 // the row stride (= iters of the full problem) of criterions / mm_iters.
+// `stable` (optional): a batch stops once its predictions have stood still for stable->patience outer iterations
+// (k_assign_changes); every later launch finds its done flag and skips it.  Null: the plain entries' launches, unchanged.
 static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const RowSrc& s_src, const int64_t* y_s, float* u,
                            float* v, float* alpha, int32_t* preds, float* criterions, int32_t* mm_iters,
-                           char* ws, hipStream_t st) {
+                           char* ws, hipStream_t st, const StableStop* stable = nullptr) {
     const bool zs = p.n_support == 0;
     const Layout L = make_layout(p);
     const int B = p.n_batches, N = p.tasks_per_batch, Q = p.n_query, K = p.n_class, S = p.n_support;
@@ -3627,6 +3700,12 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
     double* dpart = (double*)(ws + L.dpart);
     const int n_chunks = n_chunks_of(p.iter_mm);
     const int n_checks = zs ? L.n_checks : 0;   // few-shot has no dead rows: nothing to cache
+    const int32_t* done = stable ? stable->done : nullptr;
+    if (stable) {
+        TCLIP_HIP(hipMemsetAsync(stable->prev_preds, 0xff, (size_t)T * Q * 4, st));
+        TCLIP_HIP(hipMemsetAsync(stable->quiet, 0, (size_t)B * 4, st));
+        TCLIP_HIP(hipMemsetAsync(stable->done, 0, (size_t)B * 4, st));
+    }
 
     // ---- initialisation (em_dirichlet.py:195-211)
     TCLIP_HIP(hipMemsetAsync(flags, 0, 256, st));
@@ -3665,16 +3744,19 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
     for (int it = 0; it < p.iters; it++) {
         // ---- M-step statistics
         hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, zs ? 1 : 0,
-                           cs, live, v, cache_len);
+                           cs, live, v, cache_len, done, N * K);
         // zero-shot: every class alive in the first outer iteration, a few per cent afterwards - the tile kernel over all classes,
         // then over the lists of the live ones; few-shot: every class alive throughout
         launch_mstats(st, (const float*)u, (const float*)logz, (const float*)cs, (const uint8_t*)live, (const float*)sup, (const float*)cnt, T, Q, K, y, 0,
                       !zs || it == 0, (zs && it > 0) ? (int16_t*)(ws + L.cls) : nullptr, (zs && it > 0) ? (int32_t*)(ws + L.n_live) : nullptr);
         TCLIP_HIP(hipMemsetAsync(counts, 0, 256, st));
         TCLIP_HIP(hipMemsetAsync(dead_counts, 0, ((size_t)n_chunks + 3) * 4, st));
-        TCLIP_HIP(hipMemsetAsync(stop, 0, (size_t)B * 4, st));
+        if (done)       // a stable batch starts every outer iteration with its MM stop flag set: its MM launches are no-ops
+            TCLIP_HIP(hipMemcpyAsync(stop, done, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+        else
+            TCLIP_HIP(hipMemsetAsync(stop, 0, (size_t)B * 4, st));
         hipLaunchKernelGGL(k_build_rows, dim3((TK + 255) / 256), dim3(256), 0, st, (const uint8_t*)live,
-                           (const int32_t*)cache_len, TK, n_checks, dead_list[0], live_rows, dead_counts, counts + 1);
+                           (const int32_t*)cache_len, TK, n_checks, dead_list[0], live_rows, dead_counts, counts + 1, done, N * K);
         // ---- MM fixed point in chunks aligned with the stop-test checkpoints
         for (int c = 0; c < n_chunks; c++) {
             MMArgs a;
@@ -3742,11 +3824,16 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
                                      (const int32_t*)live_rows, (const int32_t*)(counts + 1), Q, K, logit0, (const int32_t*)nullptr);
         }
         hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
-                           T * Q, Q, K, (float)p.lambd, p.hard, 0, u, preds);
+                           T * Q, Q, K, (float)p.lambd, p.hard, 0, u, preds, done, N * Q);
         // ---- convergence record
-        hipLaunchKernelGGL(k_criterion, dim3(T), dim3(64), 0, st, (const float*)alpha, alpha_old, K, T, ratio);
+        hipLaunchKernelGGL(k_criterion, dim3(T), dim3(64), 0, st, (const float*)alpha, alpha_old, K, T, ratio, done, N);
         hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)ratio, N, (!zs && p.hard) ? 1 : 0,
-                           criterions + it, p.iters);
+                           criterions + it, p.iters, done);
+        // ---- the batch's predictions against the previous iteration's; last, so that this iteration's record is complete
+        if (stable)
+            hipLaunchKernelGGL(k_assign_changes, dim3(B), dim3(256), 0, st, (const int32_t*)preds, stable->prev_preds, N * Q, it,
+                               it == p.iters - 1 ? 1 : 0, stable->patience, stable->changes, p.iters, stable->quiet,
+                               stable->done, stable->outer_iters);
     }
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
@@ -3862,18 +3949,42 @@ size_t tclip_workspace_bytes(const tclip_problem* p) {
     return total;
 }
 
+size_t tclip_em_dirichlet_until_stable_workspace_bytes(const tclip_problem* p) {
+    if (check_problem(p) != TCLIP_OK) return 0;
+    size_t total = 0;
+    for (int g = 0; g < n_groups_of(*p); g++) {
+        int b0;
+        const tclip_problem q = group_problem(*p, g, &b0);
+        total += make_layout(q).total + stable_state_bytes(q);
+    }
+    return total;
+}
+
 }  // extern "C"
 
 namespace tclip {
 
 // Splits the call's batches into stream groups and enqueues each group (see StreamPool).
+// `stable` (optional, the until-stable entries): patience and the outputs outer_iters [n_batches], changes [n_batches, iters] of
+// the whole call; each group's state follows the group's plain layout in its workspace slice.
 static int run_em_dirichlet(const tclip_problem& p, const RowSrc& q_src, const RowSrc& s_src, const int64_t* y_s, float* u,
                             float* v, float* alpha, int32_t* preds, float* criterions, int32_t* mm_iters,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+                            void* workspace, size_t workspace_bytes, void* stream, const StableStop* stable = nullptr) {
     const bool zs = p.n_support == 0;
-    if (workspace_bytes < tclip_workspace_bytes(&p)) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_workspace_bytes()");
+    if (stable) {
+        if (workspace_bytes < tclip_em_dirichlet_until_stable_workspace_bytes(&p))
+            return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_em_dirichlet_until_stable_workspace_bytes()");
+    } else if (workspace_bytes < tclip_workspace_bytes(&p)) {
+        return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_workspace_bytes()");
+    }
     if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     hipStream_t caller = (hipStream_t)stream;
+    if (stable && p.iters > 0) {   // what a stopped batch never writes reads 0; ordered before every group's work (the fork event follows)
+        TCLIP_HIP(hipMemsetAsync(criterions, 0, (size_t)p.n_batches * p.iters * 4, caller));
+        TCLIP_HIP(hipMemsetAsync(mm_iters, 0, (size_t)p.n_batches * p.iters * 4, caller));
+        TCLIP_HIP(hipMemsetAsync(stable->changes, 0, (size_t)p.n_batches * p.iters * 4, caller));
+        TCLIP_HIP(hipMemsetAsync(stable->outer_iters, 0, (size_t)p.n_batches * 4, caller));
+    }
     const int G = n_groups_of(p);
     if (G > 1) {
         if (int rc = pool_init(G)) return rc;
@@ -3883,7 +3994,8 @@ static int run_em_dirichlet(const tclip_problem& p, const RowSrc& q_src, const R
     size_t ws_off[kMaxGroups + 1] = {0};
     for (int g = 0; g < G; g++) {
         int b0;
-        ws_off[g + 1] = ws_off[g] + make_layout(group_problem(p, g, &b0)).total;
+        const tclip_problem q = group_problem(p, g, &b0);
+        ws_off[g + 1] = ws_off[g] + make_layout(q).total + (stable ? stable_state_bytes(q) : 0);
     }
     // the rows of the tasks from t0 on: a dense tensor moves its base, an indexed source its index (and column) rows
     auto from_task = [&](const RowSrc& src, size_t t0, size_t rows_per_task) {
@@ -3900,10 +4012,20 @@ static int run_em_dirichlet(const tclip_problem& p, const RowSrc& q_src, const R
         if (g != 0) TCLIP_HIP(hipStreamWaitEvent(st, g_pool.fork, 0));
         tclip_problem qs = q;
         qs.iters = p.iters;
+        StableStop group;
+        if (stable) {
+            char* state = (char*)workspace + ws_off[g] + make_layout(q).total;
+            group.patience = stable->patience;
+            group.outer_iters = stable->outer_iters + b0;
+            group.changes = stable->changes + (size_t)b0 * p.iters;
+            group.prev_preds = (int32_t*)state;
+            group.quiet = (int32_t*)(state + align_up((size_t)q.n_batches * N * Q * 4));
+            group.done = (int32_t*)(state + align_up((size_t)q.n_batches * N * Q * 4) + align_up((size_t)q.n_batches * 4));
+        }
         if (int rc = enqueue_batches(qs, from_task(q_src, t0, Q), from_task(s_src, t0, S), zs ? nullptr : y_s + t0 * S,
                                      u + t0 * Q * K, v + t0 * K, alpha + t0 * K * K, preds + t0 * Q,
                                      criterions + (size_t)b0 * p.iters, mm_iters + (size_t)b0 * p.iters,
-                                     (char*)workspace + ws_off[g], st)) {
+                                     (char*)workspace + ws_off[g], st, stable ? &group : nullptr)) {
             // kernels already enqueued on the internal streams still use the caller's buffers: let them finish
             // before the error reaches a caller who may free them (the caller's own stream is ordered anyway)
             for (int h = 1; h < G; h++) (void)hipStreamSynchronize(g_pool.s[h]);
@@ -3943,6 +4065,46 @@ int tclip_em_dirichlet_run_tasks(const tclip_problem* pp, const tclip_task_sourc
         return fail(TCLIP_ERR_ARG, "table_s, s_idx and y_s must be given exactly when n_support > 0");
     return run_em_dirichlet(*pp, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s,
                             u, v, alpha, preds, criterions, mm_iters, workspace, workspace_bytes, stream);
+}
+
+// The checks the two until-stable entries add to those of the plain ones
+static int check_stable(int32_t patience, const int32_t* outer_iters, const int32_t* changes) {
+    if (patience < 1) return fail(TCLIP_ERR_ARG, "patience must be >= 1");
+    if (!outer_iters) return fail(TCLIP_ERR_ARG, "outer_iters is null");
+    if (!changes) return fail(TCLIP_ERR_ARG, "changes is null");
+    return TCLIP_OK;
+}
+
+int tclip_em_dirichlet_run_until_stable(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s,
+                                        int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
+                                        int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const bool zs = pp->n_support == 0;
+    if (int rc = check_stable(patience, outer_iters, changes)) return rc;
+    if (!x_q || !u || !v || !alpha || !preds || !criterions || !mm_iters || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (zs != (x_s == nullptr) || zs != (y_s == nullptr))
+        return fail(TCLIP_ERR_ARG, "x_s and y_s must be given exactly when n_support > 0");
+    const StableStop stable{patience, outer_iters, changes, nullptr, nullptr, nullptr};
+    return run_em_dirichlet(*pp, dense_rows(x_q), dense_rows(x_s), y_s, u, v, alpha, preds, criterions, mm_iters, workspace,
+                            workspace_bytes, stream, &stable);
+}
+
+int tclip_em_dirichlet_run_tasks_until_stable(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s,
+                                              int32_t patience, float* u, float* v, float* alpha, int32_t* preds,
+                                              float* criterions, int32_t* mm_iters, int32_t* outer_iters, int32_t* changes,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_problem(pp)) return rc;
+    const bool zs = pp->n_support == 0;
+    if (int rc = check_stable(patience, outer_iters, changes)) return rc;
+    if (!src || !src->table_q || !src->q_idx || !u || !v || !alpha || !preds || !criterions || !mm_iters || !workspace)
+        return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (zs != (src->table_s == nullptr) || zs != (src->s_idx == nullptr) || zs != (y_s == nullptr))
+        return fail(TCLIP_ERR_ARG, "table_s, s_idx and y_s must be given exactly when n_support > 0");
+    const StableStop stable{patience, outer_iters, changes, nullptr, nullptr, nullptr};
+    return run_em_dirichlet(*pp, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s,
+                            u, v, alpha, preds, criterions, mm_iters, workspace, workspace_bytes, stream, &stable);
 }
 
 int tclip_argmax_rows(const float* x, int64_t n_rows, int32_t n_class, int32_t* labels, void* stream) {

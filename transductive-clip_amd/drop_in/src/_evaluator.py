@@ -26,6 +26,34 @@ def arg_set_to(args, attr, value):
         args[attr] = saved
 
 
+@contextlib.contextmanager
+def arg_hidden(args, attr):
+    """args has no `attr` inside the block and what it had before afterwards, whatever the block raises"""
+    missing = object()
+    saved = args.pop(attr, missing) if isinstance(args, dict) else missing
+    try:
+        yield
+    finally:
+        if saved is not missing:
+            args[attr] = saved
+
+
+_STOP_PATIENCE_METHODS = ('EM_DIRICHLET', 'HARD_EM_DIRICHLET')
+
+
+def check_stop_patience(args):
+    """args.stop_patience (not a default: absent unless given) belongs to the EM-Dirichlet classes: ValueError for any other
+    method, before anything touches the device.  Returns the option's value or None."""
+    try:
+        patience = getattr(args, 'stop_patience', None)
+    except KeyError:
+        patience = None
+    if patience is not None and getattr(args, 'name_method', None) not in _STOP_PATIENCE_METHODS:
+        raise ValueError("stop_patience stops a batch of EM_DIRICHLET / HARD_EM_DIRICHLET once its assignments are stable: "
+                         f"method {getattr(args, 'name_method', None)!r} has no such stop")
+    return patience
+
+
 class EvaluatorBase:
     _METHODS = {}       # name_method -> class: the subclass's table
 
@@ -79,7 +107,8 @@ class EvaluatorBase:
         """The one collective of a run and what it leaves behind: the per-task predictions, accuracies and per-batch records
         of every rank onto rank 0 (`parts`: this rank's, None when it had no batch; `timestamps`: one time per batch it ran).
         Sets last_method (`method`: the object that actually ran on this rank) and, on rank 0, last_task_accuracies,
-        last_task_predictions, last_batch_criterions and last_batch_mm_iters.  Returns (mean over the batches of their mean
+        last_task_predictions, last_batch_criterions and last_batch_mm_iters (with args.stop_patience also
+        last_batch_outer_iters).  Returns (mean over the batches of their mean
         accuracies, mean time), or (None, None) off rank 0."""
         if parts is None:      # more ranks than batches: this rank only takes part in the gather
             parts = sharding.method_parts(self.args, None, None, 0, N, Q, torch.device(self.device))
@@ -93,4 +122,6 @@ class EvaluatorBase:
         self.last_task_predictions = got['preds'].view(n_batches, N, Q).numpy()      # class per query, every batch of the run
         self.last_batch_criterions = got['criterions'].numpy() if 'criterions' in got else None     # (n_batches, iter)
         self.last_batch_mm_iters = got['mm_iters'].numpy() if 'mm_iters' in got else None
+        if 'outer_iters' in got:       # args.stop_patience: the outer iterations every batch ran, (n_batches,)
+            self.last_batch_outer_iters = got['outer_iters'].numpy().reshape(n_batches)
         return np.asarray(results_task).mean(), (float(np.mean(timestamps)) if timestamps else 0.0)

@@ -151,6 +151,14 @@ class EMDirichletBase(MethodBase):
         self.iter_mm = args.iter_mm
         self.mm_iters = None
 
+    def _stop_patience(self):
+        """args.stop_patience (main_features.py --opts stop_patience 2): a batch stops once its predictions have stood still
+        for that many outer iterations in a row (tclip_amd.until_stable).  Optional like device_matching: None when absent."""
+        try:
+            return getattr(self.args, "stop_patience", None)
+        except KeyError:
+            return None
+
     # -- the loop ---------------------------------------------------------------------------
     def _run_engine(self, query, support=None, y_s=None, n_batches=1, tables=None):
         """`tables` = dict(table_q, q_idx[, table_s, s_idx, cols]): the task rows are read from the feature tables through the
@@ -159,11 +167,16 @@ class EMDirichletBase(MethodBase):
             raise ValueError(_SIMPLEX_ERROR)
         n_task = tables["q_idx"].shape[0] if tables is not None else query.shape[0]
         kw = dict(n_batches=n_batches, iters=self.iter, iter_mm=self.iter_mm, lambd=self.lambd, hard=self.HARD)
+        runner = engine
+        patience = self._stop_patience()
+        if patience is not None:
+            from tclip_amd import until_stable as runner
+            kw["patience"] = runner.check_patience(patience)
         if tables is not None:
-            call = lambda: engine.run_em_dirichlet_tasks(tables["table_q"], tables["q_idx"], tables.get("table_s"),      # noqa: E731
+            call = lambda: runner.run_em_dirichlet_tasks(tables["table_q"], tables["q_idx"], tables.get("table_s"),      # noqa: E731
                                                          tables.get("s_idx"), y_s, tables.get("cols"), **kw)
         else:
-            call = lambda: engine.run_em_dirichlet(query, support, y_s, **kw)      # noqa: E731
+            call = lambda: runner.run_em_dirichlet(query, support, y_s, **kw)      # noqa: E731
         res, total = self._execute(" ==> Executing {} with LAMBDA = {} and T = {}".format(self.BANNER, self.lambd, self.args.T),
                                    call, name="EM-Dirichlet")
         self.u, self.v, self.alpha, self.preds = res.u, res.v, res.alpha, res.preds
@@ -172,6 +185,9 @@ class EMDirichletBase(MethodBase):
         self.timestamps += self.spread_time("cumulative", total, self.iter, n_task)
         self.criterions = list(crit.mean(0)) if n_batches > 1 else list(crit[0])
         self.criterions_per_batch = crit
+        if patience is not None:       # the logs keep their shapes: a stopped batch's records are 0 from its outer_iters on
+            self.outer_iters = res.outer_iters.cpu().numpy()                    # (n_batches,)
+            self.assignment_changes = res.changes.cpu().numpy()                 # (n_batches, iter)
         return res
 
 

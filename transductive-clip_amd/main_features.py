@@ -40,6 +40,10 @@ costs in time is measured in DESIGN.md 8j.
 run: the tasks are drawn once, every value of the method's tuned parameter is solved on them in one engine call, and one
 `val_param<TAB>acc` row per value is appended to the validation file, in the order given - the file that one run per value with
 the same seed writes.  Each element keeps the type it is written with (`5` and `5.0` are different rows).
+`stop_patience 2` (EM_DIRICHLET and HARD_EM_DIRICHLET; not a default: absent unless given) stops a batch once no prediction of
+it has changed for that many outer iterations in a row: the batch returns exactly what a run with `iter` set to the iterations
+it ran returns, and spends no further MM launches.  The logs keep their shapes (a stopped batch's criterions are 0 from its stop
+on); the evaluator keeps the iterations every batch ran in `last_batch_outer_iters`.  Any other method refuses the option.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse
@@ -122,6 +126,9 @@ def main(argv=None, keep_process_group=False):
         if int(args.shots) < 1:
             raise ValueError("sweep_values tunes a few-shot method: shots must be positive")
         sweep = checked_sweep_values(args, sweep, distributed=True if dist_on else None)
+    from src._evaluator import check_stop_patience
+    if sweep is None:                          # refused here, before the device is touched; a sweep ignores the option
+        check_stop_patience(args)
     local_rank = int(os.environ.get("LOCAL_RANK", args.device))
     if args.seed is not None:                  # main.py:42-46
         random.seed(args.seed)

@@ -29,6 +29,12 @@ _SIGNATURES = {
     "tclip_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
     "tclip_em_dirichlet_run": (ctypes.c_int, [ctypes.POINTER(Problem)] + [_P] * 10 + [ctypes.c_size_t, _P]),
     "tclip_em_dirichlet_run_tasks": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource)] + [_P] * 8 + [ctypes.c_size_t, _P]),
+    # the plain entries' arguments with patience after y_s and outer_iters, changes after mm_iters
+    "tclip_em_dirichlet_until_stable_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem)]),
+    "tclip_em_dirichlet_run_until_stable": (ctypes.c_int, [ctypes.POINTER(Problem)] + [_P] * 3 + [ctypes.c_int32] + [_P] * 9
+                                            + [ctypes.c_size_t, _P]),
+    "tclip_em_dirichlet_run_tasks_until_stable": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_int32]
+                                                  + [_P] * 9 + [ctypes.c_size_t, _P]),
     "tclip_prototype_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
     "tclip_cluster_prototypes": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 6 + [ctypes.c_size_t, _P]),
     "tclip_match_clusters_host": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 5 + [ctypes.c_int32, _P, _P]),

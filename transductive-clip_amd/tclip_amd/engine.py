@@ -201,6 +201,12 @@ def run_em_dirichlet_tasks(table_q, q_idx, table_s=None, s_idx=None, y_s=None, c
     table_q (rows,K) f32 cuda, q_idx (T,Q) rows of it; few-shot: table_s, s_idx (T,S), y_s (T,S) the re-indexed support
     labels; cols (T,K) the per-task column permutation of Tasks_Generator_few_shot.get_task or None.  No (T,S,K) /
     (T,Q,K) tensor is built; the results are those of run_em_dirichlet on the materialised tensors, bit for bit."""
+    rows, K = _em_dirichlet_table_rows(table_q, q_idx, table_s, s_idx, y_s, cols, n_batches)
+    return _em_dirichlet(rows, K, n_batches, iters, iter_mm, lambd, hard)
+
+
+def _em_dirichlet_table_rows(table_q, q_idx, table_s, s_idx, y_s, cols, n_batches):
+    """The argument checks of run_em_dirichlet_tasks (tclip_amd.until_stable shares them) -> (the `_Rows` of the tables, K)"""
     # the checks of `_task_tables` in this entry's own order and words (it has no label check, and its support set may be absent)
     _require_cuda(table_q, "table_q")
     table_q = table_q.contiguous().float()
@@ -225,7 +231,7 @@ def run_em_dirichlet_tasks(table_q, q_idx, table_s=None, s_idx=None, y_s=None, c
         cols = cols.to(dev).contiguous()
         if on_device:
             _check_on_device(None, 1, cols, K, "cols")
-    return _em_dirichlet(_table_rows(table_q, q_idx, table_s, s_idx, y_s, cols), K, n_batches, iters, iter_mm, lambd, hard)
+    return _table_rows(table_q, q_idx, table_s, s_idx, y_s, cols), K
 
 
 def _cols_tensor(cols, T, W, dev):

@@ -30,6 +30,14 @@ _PER_BATCH_RECORDS = {'EM_DIRICHLET': ('criterions', 'mm_iters'), 'HARD_EM_DIRIC
 _PER_TASK_CRITERIONS = ('TIM-GD', 'TIM_GD')
 
 
+def _option(args, name):
+    """an optional switch of args (absent unless given): args may be a namespace or a dict with attribute access"""
+    try:
+        return getattr(args, name, None)
+    except KeyError:
+        return None
+
+
 def task_accuracies(logs, n_local, N):
     """(n_local, N) f32: every task's accuracy after the last recorded step of a method's logs"""
     return torch.from_numpy(logs['acc'][:, -1].copy()).view(n_local, N).float()
@@ -40,8 +48,11 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
     (SURVEY.md section 8e): `preds` (N*Q) int32 - the class assigned to every query, after the cluster-to-class
     matching for the zero-shot clustering methods, `acc` (N) f32, and for the EM-Dirichlet classes / ALPHA_TIM the
     per-batch `criterions` (iter) f32 and `mm_iters` (iter) int32; for TIM-GD the per-task `criterions` (iter, N) f32.
+    With args.stop_patience set, the EM-Dirichlet classes add `outer_iters` (1) int32: the outer iterations the batch ran.
     method=None: a rank without a batch (zero rows of the same widths)."""
     records = _PER_BATCH_RECORDS.get(getattr(args, 'name_method', None), ())
+    if 'mm_iters' in records and _option(args, 'stop_patience') is not None:
+        records = records + ('outer_iters',)
     iters = int(getattr(args, 'iter', 0))
     per_task = getattr(args, 'name_method', None) in _PER_TASK_CRITERIONS
     if method is None:
@@ -50,6 +61,8 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
             parts['criterions'] = torch.zeros(0, iters)
         if 'mm_iters' in records:
             parts['mm_iters'] = torch.zeros(0, iters, dtype=torch.int32)
+        if 'outer_iters' in records:
+            parts['outer_iters'] = torch.zeros(0, 1, dtype=torch.int32)
         if per_task:
             parts['criterions'] = torch.zeros(0, iters, N)
     else:
@@ -62,6 +75,8 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
             parts['criterions'] = torch.as_tensor(method.criterions_per_batch, dtype=torch.float32).view(n_local, iters)
         if 'mm_iters' in records:
             parts['mm_iters'] = torch.as_tensor(method.mm_iters, dtype=torch.int32).view(n_local, iters)
+        if 'outer_iters' in records:
+            parts['outer_iters'] = torch.as_tensor(method.outer_iters, dtype=torch.int32).view(n_local, 1)
         if per_task:        # (iter, n_local * N) -> one (iter, N) block per batch
             crit = torch.as_tensor(method.criterions_per_task, dtype=torch.float32)
             parts['criterions'] = crit.view(iters, n_local, N).permute(1, 0, 2).contiguous()
