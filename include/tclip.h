@@ -47,7 +47,8 @@ extern "C" {
  *    tclip_alpha_tim_visual_run_tasks, tclip_tim_gd_tasks_workspace_bytes, tclip_tim_gd_run_tasks;
  *    tclip_paddle_sweep_tasks_workspace_bytes, tclip_paddle_sweep_tasks, tclip_bdcspn_sweep_tasks_workspace_bytes,
  *    tclip_bdcspn_sweep_tasks, tclip_laplacian_shot_sweep_tasks_workspace_bytes, tclip_laplacian_shot_sweep_tasks,
- *    tclip_alpha_tim_sweep_tasks_workspace_bytes, tclip_alpha_tim_sweep_tasks
+ *    tclip_alpha_tim_sweep_tasks_workspace_bytes, tclip_alpha_tim_sweep_tasks;
+ *    tclip_debug_set_mm_reuse, tclip_profile_last_mm_reuse
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -594,7 +595,7 @@ int tclip_profile_enable(int on);
 int tclip_profile_collect(double* mm_busy_ms, double* mm_launch_ms_sum, int64_t* mm_launches,
                           int64_t* element_updates);
 /* The same four figures of the LAST tclip_profile_collect of this thread per kernel: index 0 = k_mm_live (the first outer
- * iteration and row lengths without a split instantiation), 1 = k_mm_split.  Every argument points to two values. */
+ * iteration, k_mm_reuse's launches included, and row lengths without a split instantiation), 1 = k_mm_split.  Every argument points to two values. */
 int tclip_profile_last_kernels(double* busy_ms, double* launch_ms_sum, int64_t* launches, int64_t* element_updates);
 /* k_mm_split keeps the placement of a wavefront's elements in its three class queues from one MM iteration to the next and
  * sorts anew only when an element has left its class: the wavefront-iterations the kernel ran in the window of the LAST
@@ -628,6 +629,17 @@ int tclip_debug_set_rowset_min_rows(int32_t rows);
  * the first iteration on, 100 + n from outer iteration n on, negative restores the default rule (n = 1).  Process-wide;
  * results do not depend on it. */
 int tclip_debug_set_mm_split(int32_t mode);
+
+/* In the first outer iteration the live rows' MM iterations from 51 on run through k_mm_reuse: digamma and lgamma are
+ * evaluated at fl(a + 1), and an element whose fl(a + 1) the last iteration left unchanged keeps both values (two LDS words
+ * per element) instead of evaluating them again.  Only under tclip_debug_set_mm_split's default rule.  For tests: 0 runs
+ * k_mm_live for the whole first outer iteration, 1 is the default, 2 is the default with the kernel's index queue cut to 64
+ * entries (its overflow path on small problems); anything else is refused (TCLIP_ERR_ARG).  Process-wide; results do not
+ * depend on it. */
+int tclip_debug_set_mm_reuse(int32_t mode);
+/* k_mm_reuse in the window of the LAST tclip_profile_collect of this thread: out[0] = entries whose special functions it
+ * evaluated, out[1] = element-updates it executed (these are also part of tclip_profile_last_kernels' k_mm_live figures). */
+int tclip_profile_last_mm_reuse(uint64_t out[2]);
 
 /* The MM kernels are also compiled with the row length as a constant for the class counts of the reference's datasets that
  * BASELINE.json runs (1000, 397, 100): same layout and operations as the run-time-K kernel of the row length's bucket.  For

@@ -11,7 +11,9 @@
 //                     register-resident, large-argument lgamma work queued block-wide in LDS
 //   k_mm_split        the same for the live rows from the second outer iteration on: every element executes only what its
 //                     value class a+1 < 2.3 / [2.3, 10) / >= 10 needs, through three dense per-wavefront LDS queues
-//                     (both also compiled with the row length as a constant for K = 1000 / 397 / 100, launch_mm)
+//   k_mm_reuse        the same for the live rows in the first outer iteration from MM iteration 51 on: digamma and lgamma of
+//                     a + 1 are kept per element in LDS and evaluated anew only where fl(a + 1) has changed
+//                     (all three also compiled with the row length as a constant for K = 1000 / 397 / 100, launch_mm)
 //   k_mm_live<dead>   the same for the listed dead rows (y = -10, iterate kept in a scratch copy),
 //   k_mm_probe        after chunk 0: limit-cycle detection that spares them the remaining chunks
 //   k_mm_decide x20   batch-global stop test on device, no host round trip          (:157-177)
@@ -460,6 +462,7 @@ struct MMArgs {
     int K, rows_per_batch, chunk, l0, l1, has_check, n_checks;
     int keep_placement;     // k_mm_split: 1 = keep the class queues' placement across the iterations of a launch (the default),
                             // 0 = sort in every iteration as rounds 3-4 did (tclip_debug_set_split_keep_placement: same bits)
+    int reuse_cap;          // k_mm_reuse: entries of the index queue in use (tclip_debug_set_mm_reuse(2): 64, so that small problems overflow it)
 };
 
 // One MM iteration of a row held in registers, in place.  If `measure`, also accumulates this
@@ -1583,6 +1586,320 @@ __global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void 
         }
         if (a.work_counter && lane == 0)
             atomicAdd(a.work_counter, (unsigned long long)K * (unsigned long long)(a.l1 - a.l0 + 1));
+        if (a.has_check) {
+            const double sn = group_sum_f64_g<G>(num), sd = group_sum_f64_g<G>(den);
+            if (lane == 0) {
+                a.rowpart[2 * (size_t)row] = sn;
+                a.rowpart[2 * (size_t)row + 1] = sd;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Reuse MM iteration (live rows, chunks 1.. of the first outer iteration).
+// Both special functions are evaluated at x1 = fl(a + 1) (em_dirichlet.py:154-155).  In the first outer iteration almost every
+// parameter is below 1, so x1 lies in [1, 2) with an ulp far coarser than a's: a moves from one MM iteration to the next while
+// x1 keeps its bit pattern (measured on the CPU oracle from iteration 50 on: 58-60 % of the elements, and not the same
+// elements every time), and digamma(x1) and lgamma(x1) are functions of that bit pattern alone.  Here every element owns
+// one word in each of two LDS planes - element e of lane l: word 64 e + l; plane 0 lgamma(x1), plane 1 digamma(x1) - and an
+// iteration evaluates only the elements whose x1 the LAST iteration changed: phase C compares fl(nb + 1) with fl(a + 1),
+// and a dirty element writes its new x1 over its plane-0 word (whose lgamma it has just consumed) and appends its home
+// index to a queue, small arguments (x1 < 2.3) from the front, large ones from the back.  The next iteration runs
+// k_mm_split's class-A passes over the small queue and its class-B pass over the large one, entry j reading x at q[j] and
+// writing both planes there.  The first iteration of a launch, an iteration after the generic path and one after a queue
+// overflow evaluate every element at its home.  Same functions, same arguments: the same bits as k_mm_live.
+constexpr int kReuseQueue = 768;    // entries of the index queue (16 bits each): with the planes and the log table 9 984 B per
+                                    // wavefront at 16 registers per lane, 16 wavefronts per CU; 400-450 of 1 000 are dirty per iteration
+struct ReuseState {
+    int nS, nL;         // entries queued for this iteration: small from q[0] up, large from q[cap - 1] down
+    bool full;          // this iteration evaluates every element (nothing cached, or the queues overflowed)
+    int evaluated;      // entries evaluated by this wavefront in the launch (instrumentation)
+};
+
+// phase C of the reuse iteration: split_apply_updates with home addresses, plus the dirty test for the next iteration
+template <int E, int G, bool kTiny, bool kMeasure>
+__device__ __forceinline__ void reuse_apply_updates(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, float psi_s,
+                                                    float* my0, const float* my1, uint16_t* q, int cap, ReuseState& rs,
+                                                    double& num, double& den) {
+    constexpr bool measure = kMeasure;
+    constexpr bool kYLocal = !RowY<E, G, kSplitYRegsMaxE>::kInRegs;
+    float yl[kYLocal ? E : 1];
+    if constexpr (kYLocal) yv.fetch_all(yl);
+    auto y_of = [&](int e) { if constexpr (kYLocal) return yl[e]; else return yv.get(e); };
+    const int n_full = full_registers<E, G>(K);
+    const int lane64 = threadIdx.x & 63;
+    float* h0 = my0 + lane64;                                       // this lane's home words: register e at h0[64 e]
+    const float* h1 = my1 + lane64;
+    int cS = 0, cL = 0;
+    // a slot beyond the row keeps a = nb = 0: never dirty
+    auto note = [&](int e, float a, float nb) {
+        const float xo = a + 1.0f, xn = nb + 1.0f;
+        const bool dirty = xn != xo, small = xn < 2.3f;
+        // one ballot per compare (the compare writes the lane mask), the classes by scalar logic; the queue's running base sits in
+        // the store's scalar base and in the capacity test's scalar side, so that the rank is v_mbcnt of the mask alone
+        const unsigned long long mD = __builtin_amdgcn_ballot_w64(dirty), mSm = __builtin_amdgcn_ballot_w64(small);
+        const unsigned long long mS = mD & mSm, mL = mD & ~mSm;
+        const int rank = lanes_below(mS);
+        if (dirty) h0[64 * e] = xn;
+        uint16_t* qs = q + cS;
+        if (dirty && small && rank < cap - cS) qs[rank] = (uint16_t)(64 * e + lane64);   // beyond the capacity: the next iteration is a full one
+        if (__builtin_expect(mL != 0ull, 0)) {
+            const int rankL = lanes_below(mL);
+            if (dirty && !small && rankL < cap - cL) q[cap - 1 - cL - rankL] = (uint16_t)(64 * e + lane64);
+        }
+        cS += __popcll(mS);
+        cL += __popcll(mL);
+    };
+    auto finish = [&](int p, const PkUpdateStage& st) {
+        const int e = 2 * p;
+        const f2 a{beta[e], beta[e + 1]};
+        const f2 nb = pk_mm_update_stage2(st);
+        const bool full = e + 1 < n_full;
+        const bool ok0 = full || elem_of<E, G>(e, lane) < K, ok1 = full || elem_of<E, G>(e + 1, lane) < K;
+        if (measure) {
+            const double d0 = (double)nb.x - (double)a.x, d1 = (double)nb.y - (double)a.y;
+            if (ok0) { num += d0 * d0; den += (double)a.x * (double)a.x; }
+            if (ok1) { num += d1 * d1; den += (double)a.y * (double)a.y; }
+        }
+        if (full) {
+            beta[e] = nb.x;
+            beta[e + 1] = nb.y;
+        } else {
+            beta[e] = ok0 ? nb.x : 0.0f;
+            beta[e + 1] = ok1 ? nb.y : 0.0f;
+        }
+        note(e, a.x, beta[e]);
+        note(e + 1, a.y, beta[e + 1]);
+    };
+    PkUpdateStage pending;
+#pragma unroll
+    for (int p = 0; p < E / 2; p++) {
+        const int e = 2 * p;
+        const f2 a{beta[e], beta[e + 1]};
+        const PkUpdateStage st = pk_mm_update_stage1_given<kTiny>(a, f2{y_of(e), y_of(e + 1)}, psi_s, h1[64 * e], h1[64 * (e + 1)],
+                                                                  h0[64 * e], h0[64 * (e + 1)]);
+        if (p > 0) finish(p - 1, pending);
+        pending = st;
+    }
+    if (E / 2 > 0) finish(E / 2 - 1, pending);
+    if (E & 1) {
+        constexpr int e = E - 1;
+        const float a = beta[e];
+        const float nb = mm_update_algebra(a, y_of(e), psi_s, h1[64 * e], h0[64 * e]);
+        const bool ok = elem_of<E, G>(e, lane) < K;
+        if (measure && ok) {
+            const double df = (double)nb - (double)a;
+            num += df * df;
+            den += (double)a * (double)a;
+        }
+        beta[e] = ok ? nb : 0.0f;
+        note(e, a, beta[e]);
+    }
+    rs.nS = cS;
+    rs.nL = cL;
+    rs.full = cS + cL > cap;
+}
+
+// my0 / my1: the wavefront's two planes of 64 E words; q: its index queue of `cap` entries
+template <int E, int G, int KC = 0>
+__device__ __forceinline__ void mm_iterate_wave_reuse(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, bool active,
+                                                      const LogTabEntry* tab, float* my0, float* my1, uint16_t* q, int cap, bool measure,
+                                                      double& num, double& den, ReuseState& rs) {
+    const int lane64 = threadIdx.x & 63;
+    float s = 16.0f;
+    bool in_domain = true;
+    if (active) {
+        s = row_sum_torch<E, G, KC>(beta, K, lane);
+        in_domain = lane != 0 || (fast_range_f32(s) && s <= 0x1p40f);     // the sum lives in lane 0
+        uint32_t largest = 0u;
+#pragma unroll
+        for (int e = 0; e < E; e++) largest = max(largest, f32_bits(beta[e]));
+        in_domain = in_domain & mm_fast_domain_of_max_bits(largest);
+    }
+    s = __shfl(s, 0, G);                                            // the row's sum in every lane of its group
+    if (__builtin_expect(!__all(in_domain), 0)) {                   // NaN / inf / out of range somewhere in the wavefront
+        if (active) {
+            const float psi_s = digamma_f32(s);
+#pragma unroll
+            for (int e = 0; e < E; e++) {
+                const float nb = mm_update_generic(beta[e], yv.get(e), psi_s);
+                const bool ok = elem_of<E, G>(e, lane) < K;
+                if (measure && ok) {
+                    const double df = (double)nb - (double)beta[e];
+                    num += df * df;
+                    den += (double)beta[e] * (double)beta[e];
+                }
+                beta[e] = ok ? nb : 0.0f;
+            }
+        }
+        rs.full = true;                                             // the generic path leaves nothing in the planes
+        return;
+    }
+    // the tiny-parameter flag and digamma of the row sum: as in mm_iterate_wave_split
+    constexpr int kFirstRagged = first_ragged_register<E, G, KC>();
+    int32_t smallest = 0x7f800000;
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        int32_t bits = (int32_t)f32_bits(beta[e]);
+        if (e >= kFirstRagged) bits = elem_of<E, G>(e, lane) < K ? bits : 0x7f800000;
+        smallest = bits < smallest ? bits : smallest;
+    }
+    const bool tiny = __builtin_amdgcn_ballot_w64(smallest <= (int32_t)0x2d2febffu) != 0ull;      // 0x2d2febff = 1e-11f
+    const float psi_s = digamma_pos_f32(s, tab);
+    if (rs.full) {
+        // every element, register by register at its home: digamma's nine masked recurrence steps and the lgamma of the
+        // argument's side of 2.3, as k_mm_live evaluates them (slots beyond the row hold a = 0 and are evaluated along)
+#pragma unroll
+        for (int e = 0; e < E; e++) my0[64 * e + lane64] = beta[e] + 1.0f;
+        wave_lds_handoff();
+#pragma unroll 1
+        for (int i = lane64; i < 64 * E; i += 64) {
+            const float x = my0[i];
+            const bool small = x < 2.3f;
+            float xr = x, acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                const float m = below10_f32(xr);
+                acc = __builtin_fmaf(-m, rcp_rn_f32(xr), acc);
+                xr += m;
+            }
+            const float psi = digamma_after_rec_ge10<false>(xr, acc, tab);
+            const unsigned long long m_big = __builtin_amdgcn_ballot_w64(!small);
+            float lg = 0.0f;
+            if (m_big != ~0ull) {
+                bool sure;
+                lg = lgamma_sleef_1_23_f64(small ? x : 2.0f, sure);
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(!sure) != 0ull, 0)) lg = sure ? lg : lgamma_sleef_05_23(small ? x : 2.0f);
+            }
+            if (m_big != 0ull) {
+                const float lg_big = lgamma_big_dense(small ? 8.0f : x);
+                lg = small ? lg : lg_big;
+            }
+            my0[i] = lg;
+            my1[i] = psi;
+        }
+        rs.evaluated += __popcll(__builtin_amdgcn_ballot_w64(active && lane == 0)) * K;
+    } else {
+        // the small queue: k_mm_split's class-A passes, entry j at home q[j]
+        const int nS = rs.nS, nL = rs.nL;
+        int jS = 0;
+        for (; jS + 64 < nS; jS += 128) {
+            const int j0 = jS + lane64, j1 = min(j0 + 64, nS - 1);
+            const int i0 = q[j0], i1 = q[j1];
+            const f2 x{my0[i0], my0[i1]};
+            f2 xr = x, acc = pk(0.0f);
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                acc = acc - pk_rcp_rn(xr);
+                xr = xr + pk(1.0f);
+            }
+            const f2 m{below10_f32(xr.x), below10_f32(xr.y)};
+            acc = pk_fma(-m, pk_rcp_rn(xr), acc);
+            xr = xr + m;
+            const f2 psi = pk_digamma_after_rec(xr, acc, tab);
+            const f2 lg = pk_lgamma_sleef_1_23(x);
+            my0[i0] = lg.x;
+            my1[i0] = psi.x;
+            my0[i1] = lg.y;
+            my1[i1] = psi.y;
+        }
+        for (; jS < nS; jS += 64) {
+            const int i = q[min(jS + lane64, nS - 1)];
+            const float x = my0[i];
+            float xr = x, acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                acc = acc - rcp_rn_f32(xr);
+                xr = xr + 1.0f;
+            }
+            const float m = below10_f32(xr);
+            acc = __builtin_fmaf(-m, rcp_rn_f32(xr), acc);
+            xr = xr + m;
+            const float psi = digamma_after_rec_ge10<false>(xr, acc, tab);
+            bool sure;
+            float lg = lgamma_sleef_1_23_f64(x, sure);
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(!sure) != 0ull, 0)) lg = sure ? lg : lgamma_sleef_05_23(x);
+            my0[i] = lg;
+            my1[i] = psi;
+        }
+        // the large queue: k_mm_split's class-B pass (its masked recurrence and general lgamma are right from 10 on as well)
+        for (int jL = 0; jL < nL; jL += 64) {
+            const int i = q[cap - 1 - min(jL + lane64, nL - 1)];
+            const float x = my0[i];
+            float xr = x, acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const float m = below10_f32(xr);
+                acc = __builtin_fmaf(-m, rcp_rn_f32(xr), acc);
+                xr += m;
+            }
+            const float psi = digamma_after_rec_ge10<false>(xr, acc, tab);
+            const float lg = lgamma_big_dense(x);
+            my0[i] = lg;
+            my1[i] = psi;
+        }
+        rs.evaluated += nS + nL;
+    }
+    // phase C
+    wave_lds_handoff();
+    if (__builtin_expect(measure, 0)) {
+        if (tiny) reuse_apply_updates<E, G, true, true>(beta, yv, K, lane, psi_s, my0, my1, q, cap, rs, num, den);
+        else reuse_apply_updates<E, G, false, true>(beta, yv, K, lane, psi_s, my0, my1, q, cap, rs, num, den);
+    } else if (__builtin_expect(tiny, 0)) reuse_apply_updates<E, G, true, false>(beta, yv, K, lane, psi_s, my0, my1, q, cap, rs, num, den);
+    else reuse_apply_updates<E, G, false, false>(beta, yv, K, lane, psi_s, my0, my1, q, cap, rs, num, den);
+    wave_lds_handoff();
+}
+
+template <int E, int G, int KC = 0>
+__global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void k_mm_reuse(MMArgs a) {
+    static_assert(E <= kSplitMaxE, "LDS: two words per element");
+    constexpr int kQ = kReuseQueue < 64 * E ? kReuseQueue : 64 * E;
+    __shared__ LogTabEntry tab[16];
+    __shared__ float plane0[64 * E];
+    __shared__ float plane1[64 * E];
+    __shared__ uint16_t queue[kQ];
+    load_log_table(tab);
+    const int lane = threadIdx.x & (G - 1);
+    const int group = threadIdx.x / G;
+    constexpr int kRows = 64 / G;
+    const int n = *a.n_rows;
+    const int K = KC > 0 ? KC : a.K;
+    const int cap = a.reuse_cap < kQ ? a.reuse_cap : kQ;
+    for (int first = blockIdx.x * kRows; first < n; first += gridDim.x * kRows) {
+        const int i = first + group;
+        int row = i < n ? a.rows[i] : 0;
+        if constexpr (G == 64) row = __builtin_amdgcn_readfirstlane(row);
+        const bool active = i < n && !a.stop[row / a.rows_per_batch];
+        if (!__any(active)) continue;
+        float beta[E];
+        RowY<E, G, kSplitYRegsMaxE> yv;
+        double num = 0.0, den = 0.0;
+        yv.load(a.y + (size_t)row * K, lane, K);
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const int d = elem_of<E, G>(e, lane);
+            beta[e] = (active && d < K) ? a.alpha[(size_t)row * K + d] : 0.0f;
+        }
+        ReuseState rs;
+        rs.nS = rs.nL = 0;
+        rs.full = true;                                             // nothing is cached across launches
+        rs.evaluated = 0;
+        for (int l = a.l0; l <= a.l1; l++)
+            mm_iterate_wave_reuse<E, G, KC>(beta, yv, K, lane, active, tab, plane0, plane1, queue, cap, a.has_check && l == a.l1, num, den, rs);
+        if (a.work_counter && (threadIdx.x & 63) == 0)             // [4]: entries this kernel evaluated
+            atomicAdd(a.work_counter + 4, (unsigned long long)rs.evaluated);
+        if (!active) continue;
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const int d = elem_of<E, G>(e, lane);
+            if (d < K) a.alpha[(size_t)row * K + d] = beta[e];
+        }
+        if (a.work_counter && lane == 0) {                          // [0]: with k_mm_live's (the first outer iteration); [5]: this kernel's own
+            const unsigned long long updates = (unsigned long long)K * (unsigned long long)(a.l1 - a.l0 + 1);
+            atomicAdd(a.work_counter, updates);
+            atomicAdd(a.work_counter + 5, updates);
+        }
         if (a.has_check) {
             const double sn = group_sum_f64_g<G>(num), sd = group_sum_f64_g<G>(den);
             if (lane == 0) {
@@ -2959,11 +3276,13 @@ struct Profile {
     std::vector<hipEvent_t> ev;      // start/stop pairs, reused across collections
     std::vector<uint8_t> kind;       // per pair: 0 = k_mm_live, 1 = k_mm_split
     size_t used = 0;
-    unsigned long long* counter = nullptr;      // [4]: element-updates executed by k_mm_live / k_mm_split; k_mm_split's wavefront-iterations / full placements
+    unsigned long long* counter = nullptr;      // [6]: element-updates executed by k_mm_live / k_mm_split; k_mm_split's wavefront-iterations / full placements;
+                                                // k_mm_reuse's evaluated entries / element-updates
     // per-kernel figures of the last collection (tclip_profile_last_kernels)
     double last_busy[2] = {0, 0}, last_sum[2] = {0, 0};
     int64_t last_launches[2] = {0, 0}, last_updates[2] = {0, 0};
-    int64_t last_split_iterations = 0, last_split_sorts = 0;     // k_mm_split: wavefront-iterations, and how many of them sorted their queues anew
+    uint64_t last_reuse[2] = {0, 0};                              // k_mm_reuse: entries evaluated, element-updates executed (those also under k_mm_live)
+    int64_t last_split_iterations = 0, last_split_sorts = 0;    // k_mm_split: wavefront-iterations, and how many of them sorted their queues anew
 };
 static thread_local bool g_last_mm_was_split = false;     // which kernel the last launch_mm(kMMSplit / kMMLive) started
 thread_local Profile g_prof;
@@ -2972,6 +3291,8 @@ static int g_dead_head = kDeadHead;                 // tclip_debug_set_dead_head
 static int g_rowset_min_rows = -1;                  // tclip_debug_set_rowset_min_rows; negative: the default rule
 static int g_mm_split = -1;                         // tclip_debug_set_mm_split: 0 never, 1 always, negative: from the second outer iteration on
 static int g_split_keep_placement = 1;              // tclip_debug_set_split_keep_placement: 0 = k_mm_split sorts its queues in every iteration
+static int g_mm_reuse = 1;                          // tclip_debug_set_mm_reuse: 0 = k_mm_live for the whole first outer iteration, 1 = k_mm_reuse from its
+                                                    // chunk 1 on, 2 = the same with a 64-entry index queue
 
 static hipEvent_t prof_event() {
     if (g_prof.used == g_prof.ev.size()) {
@@ -3076,7 +3397,7 @@ static int mm_lanes_per_row(int K) {
     if (K >= kG64MinK) return 64;
     return K <= kG16MaxK ? 16 : 32;
 }
-enum MMKind { kMMLive = 0, kMMDead = 1, kMMProbe = 2, kMMSplit = 3, kMMProbeHead = 4 };
+enum MMKind { kMMLive = 0, kMMDead = 1, kMMProbe = 2, kMMSplit = 3, kMMProbeHead = 4, kMMReuse = 5 };
 template <int E, int G, int KC = 0>
 static void launch_mm_EG(int dead, int rows, hipStream_t st, const MMArgs& a) {
     constexpr int kWaves = 4, kRowsPerBlock = (64 / G) * kWaves;
@@ -3089,6 +3410,16 @@ static void launch_mm_EG(int dead, int rows, hipStream_t st, const MMArgs& a) {
             if (sgrid > 256 * 64) sgrid = 256 * 64;
             hipLaunchKernelGGL((k_mm_split<E, G, KC>), dim3(sgrid), dim3(64), 0, st, a);
             g_last_mm_was_split = true;
+            return;
+        }
+        dead = kMMLive;
+    }
+    if (dead == kMMReuse) {                        // live rows, chunks 1.. of the first outer iteration; instantiated where k_mm_split is
+        if constexpr (E <= kSplitMaxE && E >= kSplitMinE) {
+            constexpr int kReuseRows = 64 / G;           // one wavefront per block
+            int rgrid = (rows + kReuseRows - 1) / kReuseRows;
+            if (rgrid > 256 * 64) rgrid = 256 * 64;
+            hipLaunchKernelGGL((k_mm_reuse<E, G, KC>), dim3(rgrid), dim3(64), 0, st, a);
             return;
         }
         dead = kMMLive;
@@ -3141,6 +3472,16 @@ static bool mm_has_split(int K) {
 // 2 x 4 lane masks per row sum in spilled scalar registers).  g_fixed_k_kernels == 0 (tclip_debug_set_fixed_k_kernels, tests)
 // or the 32-lane test hook: the run-time-K kernels for every row length, which must give the same bits.
 static int g_fixed_k_kernels = 1;
+// Lane layouts in which k_mm_reuse replaces k_mm_live.  Same machine, tclip_debug_set_mm_reuse 0 against 1, summed time of the
+// first outer iteration's live-row launches / time per engine call (three stream groups, 1000 MM iterations at most):
+//   16 lanes: K = 65 -34 % / -1.1 %, K = 100 -35 % / -0.5 %, K = 196 -29 % / -1.8 %, K = 256 -14 % / -0.4 %
+//   32 lanes: K = 300 -21 % / -2.4 %, K = 397 hard -20 % / -4.1 %
+//   64 lanes: K = 1000 against the parent's library -5.4 % per call, few-shot K = 1000 -2.1 % (profiles/mm_reuse_ab.txt)
+constexpr bool kReuseG16 = true, kReuseG32 = true, kReuseG64 = true;
+static bool mm_reuse_pays(int K) {
+    const int G = mm_lanes_per_row(K);
+    return G == 64 ? kReuseG64 : (G == 32 ? kReuseG32 : kReuseG16);
+}
 static void launch_mm(int dead, int K, int rows, hipStream_t st, const MMArgs& a) {
     if (g_rowset_min_rows != 0 && g_fixed_k_kernels && dead != kMMProbe && dead != kMMProbeHead) {
         if (K == 1000) return launch_mm_EG<16, 64, 1000>(dead, rows, st, a);
@@ -3765,6 +4106,7 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
             a.next_rows = nullptr; a.next_count = nullptr;
             a.K = K; a.rows_per_batch = N * K; a.chunk = c;
             a.keep_placement = g_split_keep_placement;
+            a.reuse_cap = g_mm_reuse == 2 ? 64 : kReuseQueue;
             a.l0 = c == 0 ? 0 : 50 * c + 1;
             a.l1 = 50 * (c + 1) < p.iter_mm - 1 ? 50 * (c + 1) : p.iter_mm - 1;
             a.has_check = (a.l1 > 0 && a.l1 % 50 == 0) ? 1 : 0;
@@ -3777,7 +4119,9 @@ static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const Ro
             if (e0 && e1) TCLIP_HIP(hipEventRecord(e0, st));
             a.rows = live_rows; a.n_rows = counts + 1;
             g_last_mm_was_split = false;
-            launch_mm(split ? kMMSplit : kMMLive, K, TK, st, a);
+            // chunks 1.. of the first outer iteration under the default rule: k_mm_reuse where it exists and pays
+            const bool reuse = g_mm_split < 0 && g_mm_reuse != 0 && it == 0 && c > 0 && mm_has_split(K) && mm_reuse_pays(K);
+            launch_mm(split ? kMMSplit : (reuse ? kMMReuse : kMMLive), K, TK, st, a);
             if (e0 && e1) {                                     // the instrumentation covers k_mm_live / k_mm_split only
                 TCLIP_HIP(hipEventRecord(e1, st));
                 if (g_prof.kind.size() < g_prof.used / 2) g_prof.kind.resize(g_prof.used / 2);
@@ -4148,6 +4492,12 @@ int tclip_debug_set_mm_split(int32_t mode) {
     return TCLIP_OK;
 }
 
+int tclip_debug_set_mm_reuse(int32_t mode) {
+    if (mode < 0 || mode > 2) return fail(TCLIP_ERR_ARG, "tclip_debug_set_mm_reuse: mode must be 0, 1 or 2");
+    g_mm_reuse = mode;
+    return TCLIP_OK;
+}
+
 int tclip_debug_set_split_keep_placement(int32_t on) {
     g_split_keep_placement = on != 0;
     return TCLIP_OK;
@@ -4166,8 +4516,8 @@ int tclip_debug_set_probe_chunks(int32_t chunks) {
 
 int tclip_profile_enable(int on) {
     if (on && !g_prof.counter) {
-        TCLIP_HIP(hipMalloc((void**)&g_prof.counter, 4 * sizeof(unsigned long long)));
-        TCLIP_HIP(hipMemset(g_prof.counter, 0, 4 * sizeof(unsigned long long)));
+        TCLIP_HIP(hipMalloc((void**)&g_prof.counter, 6 * sizeof(unsigned long long)));
+        TCLIP_HIP(hipMemset(g_prof.counter, 0, 6 * sizeof(unsigned long long)));
     }
     g_prof.on = on != 0;
     return TCLIP_OK;
@@ -4213,7 +4563,7 @@ int tclip_profile_collect(double* mm_busy_ms, double* mm_launch_ms_sum, int64_t*
     if (mm_busy_ms) *mm_busy_ms = busy;
     if (mm_launch_ms_sum) *mm_launch_ms_sum = sum;
     if (mm_launches) *mm_launches = (int64_t)(g_prof.used / 2);
-    unsigned long long c[4] = {0, 0, 0, 0};
+    unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
     if (g_prof.counter) {
         TCLIP_HIP(hipMemcpy(c, g_prof.counter, sizeof c, hipMemcpyDeviceToHost));
         TCLIP_HIP(hipMemset(g_prof.counter, 0, sizeof c));
@@ -4222,6 +4572,8 @@ int tclip_profile_collect(double* mm_busy_ms, double* mm_launch_ms_sum, int64_t*
     g_prof.last_updates[1] = (int64_t)c[1];
     g_prof.last_split_iterations = (int64_t)c[2];
     g_prof.last_split_sorts = (int64_t)c[3];
+    g_prof.last_reuse[0] = c[4];
+    g_prof.last_reuse[1] = c[5];
     if (element_updates) *element_updates = (int64_t)(c[0] + c[1]);
     g_prof.used = 0;
     return TCLIP_OK;
@@ -4239,6 +4591,13 @@ int tclip_profile_last_kernels(double* busy_ms, double* launch_ms_sum, int64_t* 
 int tclip_profile_last_split_sorts(int64_t* wave_iterations, int64_t* sorts) {
     if (wave_iterations) *wave_iterations = g_prof.last_split_iterations;
     if (sorts) *sorts = g_prof.last_split_sorts;
+    return TCLIP_OK;
+}
+
+int tclip_profile_last_mm_reuse(uint64_t out[2]) {
+    if (!out) return fail(TCLIP_ERR_ARG, "null pointer");
+    out[0] = g_prof.last_reuse[0];
+    out[1] = g_prof.last_reuse[1];
     return TCLIP_OK;
 }
 
