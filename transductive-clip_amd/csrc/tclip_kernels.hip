@@ -557,6 +557,74 @@ __device__ __forceinline__ float lgamma_big_dense(float v) {
     return r;
 }
 
+// y of a row as phase C reads it: from the registers of the whole chunk (short rows), or fetched here, all at once, for this
+// phase alone - 16 values per lane that live across the dense passes were 16 values the compiler spilled and re-read one pair
+// at a time, each re-read followed by a wait for EVERYTHING in flight, the next pair's square-root table entries included
+template <int E, int G, int kRegsMaxE>
+struct PhaseCY {
+    static constexpr bool kLocal = !RowY<E, G, kRegsMaxE>::kInRegs;
+    const RowY<E, G, kRegsMaxE>& yv;
+    float yl[kLocal ? E : 1];
+    __device__ __forceinline__ explicit PhaseCY(const RowY<E, G, kRegsMaxE>& yv_) : yv(yv_) {
+        if constexpr (kLocal) yv.fetch_all(yl);
+    }
+    __device__ __forceinline__ float operator()(int e) const {
+        if constexpr (kLocal) return yl[e];
+        else return yv.get(e);
+    }
+};
+
+// Finishes pair p of phase C (the square root's table entries were requested one pair ago), measures it if `measure` (this
+// lane's share of ||b'-b||^2 and ||b||^2 in fp64) and stores it; slots beyond the row keep 0.  Returns the old pair.
+template <int E, int G>
+__device__ __forceinline__ f2 mm_finish_pair(float (&beta)[E], int p, const PkUpdateStage& st, int n_full, int K, int lane,
+                                             bool measure, double& num, double& den) {
+    const int e = 2 * p;
+    const f2 a{beta[e], beta[e + 1]};
+    const f2 nb = pk_mm_update_stage2(st);
+    const bool full = e + 1 < n_full;
+    const bool ok0 = full || elem_of<E, G>(e, lane) < K, ok1 = full || elem_of<E, G>(e + 1, lane) < K;
+    if (measure) {
+        const double d0 = (double)nb.x - (double)a.x, d1 = (double)nb.y - (double)a.y;
+        if (ok0) { num += d0 * d0; den += (double)a.x * (double)a.x; }
+        if (ok1) { num += d1 * d1; den += (double)a.y * (double)a.y; }
+    }
+    if (full) {                                    // uniform branch: nothing to mask
+        beta[e] = nb.x;
+        beta[e + 1] = nb.y;
+    } else {
+        beta[e] = ok0 ? nb.x : 0.0f;
+        beta[e + 1] = ok1 ? nb.y : 0.0f;
+    }
+    return a;
+}
+
+// The same for a single element: the new value `nb` of register e, measured and stored.  Returns the old value.
+template <int E, int G>
+__device__ __forceinline__ float mm_finish_one(float (&beta)[E], int e, float nb, int K, int lane, bool measure, double& num,
+                                               double& den) {
+    const float a = beta[e];
+    const bool ok = elem_of<E, G>(e, lane) < K;
+    if (measure && ok) {
+        const double df = (double)nb - (double)a;
+        num += df * df;
+        den += (double)a * (double)a;
+    }
+    beta[e] = ok ? nb : 0.0f;
+    return a;
+}
+
+// The generic update of a row whose sum is `s`: NaN / inf / a value outside the fast range somewhere in its wavefront or block.
+// mm_iterate_block writes the same loop out: with this call k_mm_live's register allocation changes (one VGPR or 16 B of scratch
+// more in nine instantiations, profiles/mm_shared_stages_codegen.txt).
+template <int E, int G, int kRegsMaxE>
+__device__ __forceinline__ void mm_generic_row(float (&beta)[E], const RowY<E, G, kRegsMaxE>& yv, int K, int lane, float s,
+                                               bool measure, double& num, double& den) {
+    const float psi_s = digamma_f32(s);
+#pragma unroll
+    for (int e = 0; e < E; e++) mm_finish_one<E, G>(beta, e, mm_update_generic(beta[e], yv.get(e), psi_s), K, lane, measure, num, den);
+}
+
 // Phase C of one MM iteration: every element's digamma, the cheap lgamma branch, the pick-up of
 // the large-argument results queued at `queue[base...]` in ballot order, and the update algebra.
 // Elements are advanced two at a time on the packed fp32 pipe (tclip_pk.h); an odd last one
@@ -566,31 +634,7 @@ __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E,
                                                  const LogTabEntry* tab, const float* queue, int base, bool measure,
                                                  double& num, double& den) {
     const int n_full = full_registers<E, G>(K);    // registers below it hold only elements of the row (wave-uniform)
-    // y of rows that do not keep it in registers: fetched here, all at once (see split_apply_updates)
-    constexpr bool kYLocal = !RowY<E, G>::kInRegs;
-    float yl[kYLocal ? E : 1];
-    if constexpr (kYLocal) yv.fetch_all(yl);
-    auto y_of = [&](int e) { if constexpr (kYLocal) return yl[e]; else return yv.get(e); };
-    // finishes pair p (the square root's table entries were requested one pair ago), stores and measures it
-    auto finish = [&](int p, const PkUpdateStage& st) {
-        const int e = 2 * p;
-        const f2 a{beta[e], beta[e + 1]};
-        const f2 nb = pk_mm_update_stage2(st);
-        const bool full = e + 1 < n_full;
-        const bool ok0 = full || elem_of<E, G>(e, lane) < K, ok1 = full || elem_of<E, G>(e + 1, lane) < K;
-        if (measure) {
-            const double d0 = (double)nb.x - (double)a.x, d1 = (double)nb.y - (double)a.y;
-            if (ok0) { num += d0 * d0; den += (double)a.x * (double)a.x; }
-            if (ok1) { num += d1 * d1; den += (double)a.y * (double)a.y; }
-        }
-        if (full) {                                // uniform branch: nothing to mask
-            beta[e] = nb.x;
-            beta[e + 1] = nb.y;
-        } else {
-            beta[e] = ok0 ? nb.x : 0.0f;
-            beta[e + 1] = ok1 ? nb.y : 0.0f;
-        }
-    };
+    const PhaseCY<E, G, kYRegsMaxE> y_of(yv);
     PkUpdateStage pending;
 #pragma unroll
     for (int p = 0; p < E / 2; p++) {
@@ -604,12 +648,13 @@ __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E,
         const float lg1 = big1 ? queue[base + lanes_below(m1)] : 0.0f;
         base += __popcll(m1);
         const PkUpdateStage st = pk_mm_update_stage1(a, f2{y_of(e), y_of(e + 1)}, pk(psi_s), f2{lg0, lg1}, tab);
-        if (p > 0) finish(p - 1, pending);         // while this pair's table look-ups are in flight
+        // the last pair is finished while this pair's table look-ups are in flight
+        if (p > 0) mm_finish_pair<E, G>(beta, p - 1, pending, n_full, K, lane, measure, num, den);
         pending = st;
     }
-    if (E / 2 > 0) finish(E / 2 - 1, pending);
-#pragma unroll
-    for (int e = E / 2 * 2; e < E; e++) {
+    if (E / 2 > 0) mm_finish_pair<E, G>(beta, E / 2 - 1, pending, n_full, K, lane, measure, num, den);
+    if (E & 1) {
+        constexpr int e = E - 1;
         const float a = beta[e];
         const float x1 = a + 1.0f;
         const bool big = x1 >= 2.3f;
@@ -620,14 +665,7 @@ __device__ __forceinline__ void mm_apply_updates(float (&beta)[E], const RowY<E,
         float lg_small = lgamma_sleef_1_23_f64(big ? 2.0f : x1, sure);
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(!sure) != 0ull, 0)) lg_small = sure ? lg_small : lgamma_sleef_05_23(big ? 2.0f : x1);
         const float psi1 = digamma_xp1(a, tab);
-        const float nb = mm_update_algebra(a, y_of(e), psi_s, psi1, big ? lg_big : lg_small);
-        const bool ok = elem_of<E, G>(e, lane) < K;
-        if (measure && ok) {
-            const double df = (double)nb - (double)a;
-            num += df * df;
-            den += (double)a * (double)a;
-        }
-        beta[e] = ok ? nb : 0.0f;
+        mm_finish_one<E, G>(beta, e, mm_update_algebra(a, y_of(e), psi_s, psi1, big ? lg_big : lg_small), K, lane, measure, num, den);
     }
 }
 
@@ -641,38 +679,16 @@ template <int E, int G = kGroup>
 __device__ __forceinline__ void mm_apply_updates_small(float (&beta)[E], const RowY<E, G>& yv, int K, int lane, float psi_s,
                                                        const LogTabEntry* tab, bool measure, double& num, double& den) {
     const int n_full = full_registers<E, G>(K);
-    constexpr bool kYLocal = !RowY<E, G>::kInRegs;
-    float yl[kYLocal ? E : 1];
-    if constexpr (kYLocal) yv.fetch_all(yl);
-    auto y_of = [&](int e) { if constexpr (kYLocal) return yl[e]; else return yv.get(e); };
-    auto finish = [&](int p, const PkUpdateStage& st) {
-        const int e = 2 * p;
-        const f2 a{beta[e], beta[e + 1]};
-        const f2 nb = pk_mm_update_stage2(st);
-        const bool full = e + 1 < n_full;
-        const bool ok0 = full || elem_of<E, G>(e, lane) < K, ok1 = full || elem_of<E, G>(e + 1, lane) < K;
-        if (measure) {
-            const double d0 = (double)nb.x - (double)a.x, d1 = (double)nb.y - (double)a.y;
-            if (ok0) { num += d0 * d0; den += (double)a.x * (double)a.x; }
-            if (ok1) { num += d1 * d1; den += (double)a.y * (double)a.y; }
-        }
-        if (full) {
-            beta[e] = nb.x;
-            beta[e + 1] = nb.y;
-        } else {
-            beta[e] = ok0 ? nb.x : 0.0f;
-            beta[e + 1] = ok1 ? nb.y : 0.0f;
-        }
-    };
+    const PhaseCY<E, G, kYRegsMaxE> y_of(yv);
     PkUpdateStage pending;
 #pragma unroll
     for (int p = 0; p < E / 2; p++) {
         const int e = 2 * p;
         const PkUpdateStage st = pk_mm_update_stage1_small(f2{beta[e], beta[e + 1]}, f2{y_of(e), y_of(e + 1)}, pk(psi_s), tab);
-        if (p > 0) finish(p - 1, pending);
+        if (p > 0) mm_finish_pair<E, G>(beta, p - 1, pending, n_full, K, lane, measure, num, den);
         pending = st;
     }
-    if (E / 2 > 0) finish(E / 2 - 1, pending);
+    if (E / 2 > 0) mm_finish_pair<E, G>(beta, E / 2 - 1, pending, n_full, K, lane, measure, num, den);
     if (E & 1) {
         constexpr int e = E - 1;
         const float a = beta[e];
@@ -680,14 +696,7 @@ __device__ __forceinline__ void mm_apply_updates_small(float (&beta)[E], const R
         bool sure;
         float lg = lgamma_sleef_1_23_f64(x1, sure);
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(!sure) != 0ull, 0)) lg = sure ? lg : lgamma_sleef_05_23(x1);
-        const float nb = mm_update_algebra(a, y_of(e), psi_s, digamma_xp1(a, tab), lg);
-        const bool ok = elem_of<E, G>(e, lane) < K;
-        if (measure && ok) {
-            const double df = (double)nb - (double)a;
-            num += df * df;
-            den += (double)a * (double)a;
-        }
-        beta[e] = ok ? nb : 0.0f;
+        mm_finish_one<E, G>(beta, e, mm_update_algebra(a, y_of(e), psi_s, digamma_xp1(a, tab), lg), K, lane, measure, num, den);
     }
 }
 
@@ -738,18 +747,7 @@ __device__ __forceinline__ void mm_iterate(float (&beta)[E], const RowY<E, G>& y
     for (int e = 0; e < E; e++) largest = max(largest, f32_bits(beta[e]));
     in_domain = in_domain & mm_fast_domain_of_max_bits(largest);
     if (__builtin_expect(!__all(in_domain), 0)) {   // NaN / inf / out of range somewhere in the wave
-        const float psi_s = digamma_f32(s);
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const float nb = mm_update_generic(beta[e], yv.get(e), psi_s);
-            const bool ok = elem_of<E, G>(e, lane) < K;
-            if (measure && ok) {
-                const double df = (double)nb - (double)beta[e];
-                num += df * df;
-                den += (double)beta[e] * (double)beta[e];
-            }
-            beta[e] = ok ? nb : 0.0f;
-        }
+        mm_generic_row<E, G>(beta, yv, K, lane, s, measure, num, den);
         return;
     }
     const float psi_s = digamma_pos_f32(s, tab);   // row sums are mostly >= 10: the recurrence loop is rarely entered
@@ -1087,6 +1085,24 @@ __device__ __forceinline__ void mm_iterate_block(float (&beta)[R][E], const RowY
                                    measure, num[r], den[r]);
 }
 
+// A row's iterate between global memory and the registers of its lane group (slots beyond the row, and rows that do not run: 0).
+// k_mm_live writes both loops out: with these calls its register allocation changes in 21 instantiations (same record).
+template <int E, int G>
+__device__ __forceinline__ void mm_load_row(float (&beta)[E], const float* src, int row, int K, int lane, bool active) {
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        const int d = elem_of<E, G>(e, lane);
+        beta[e] = (active && d < K) ? src[(size_t)row * K + d] : 0.0f;
+    }
+}
+template <int E, int G>
+__device__ __forceinline__ void mm_store_row(float* dst, int row, int K, int lane, const float (&beta)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        const int d = elem_of<E, G>(e, lane);
+        if (d < K) dst[(size_t)row * K + d] = beta[e];
+    }
+}
 // kDead: the listed rows are dead rows whose cache ends at this chunk: y = -10, the iterate lives in
 // `beta_dead` (their alpha keeps its value, em_dirichlet.py:224-226) and the stop-test pair goes to the cache.
 // G: lanes per row (32; 16 for short rows, where a 32-lane group would leave lanes idle: K = 100 fills 100 of 128
@@ -1213,34 +1229,8 @@ template <int E, int G, bool kTiny, bool kMeasure>
 __device__ __forceinline__ void split_apply_updates(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, float psi_s,
                                                     const float* my0, const float* my1, const uint32_t (&slot)[(E + 1) / 2],
                                                     double& num, double& den) {
-    constexpr bool measure = kMeasure;
-    // y of the row: from the registers of the whole chunk (short rows), or fetched here, all at once, for this phase alone -
-    // 16 values per lane that live across the dense passes were 16 values the compiler spilled and re-read one pair at a
-    // time, each re-read followed by a wait for EVERYTHING in flight, the next pair's square-root table entries included
-    constexpr bool kYLocal = !RowY<E, G, kSplitYRegsMaxE>::kInRegs;
-    float yl[kYLocal ? E : 1];
-    if constexpr (kYLocal) yv.fetch_all(yl);
-    auto y_of = [&](int e) { if constexpr (kYLocal) return yl[e]; else return yv.get(e); };
+    const PhaseCY<E, G, kSplitYRegsMaxE> y_of(yv);
     const int n_full = full_registers<E, G>(K);
-    auto finish = [&](int p, const PkUpdateStage& st) {
-        const int e = 2 * p;
-        const f2 a{beta[e], beta[e + 1]};
-        const f2 nb = pk_mm_update_stage2(st);
-        const bool full = e + 1 < n_full;
-        const bool ok0 = full || elem_of<E, G>(e, lane) < K, ok1 = full || elem_of<E, G>(e + 1, lane) < K;
-        if (measure) {
-            const double d0 = (double)nb.x - (double)a.x, d1 = (double)nb.y - (double)a.y;
-            if (ok0) { num += d0 * d0; den += (double)a.x * (double)a.x; }
-            if (ok1) { num += d1 * d1; den += (double)a.y * (double)a.y; }
-        }
-        if (full) {
-            beta[e] = nb.x;
-            beta[e + 1] = nb.y;
-        } else {
-            beta[e] = ok0 ? nb.x : 0.0f;
-            beta[e + 1] = ok1 ? nb.y : 0.0f;
-        }
-    };
     PkUpdateStage pending;
 #pragma unroll
     for (int p = 0; p < E / 2; p++) {
@@ -1248,22 +1238,14 @@ __device__ __forceinline__ void split_apply_updates(float (&beta)[E], const RowY
         const f2 a{beta[e], beta[e + 1]};
         const int i0 = (int)(slot[p] & 0xffffu), i1 = (int)(slot[p] >> 16);
         const PkUpdateStage st = pk_mm_update_stage1_given<kTiny>(a, f2{y_of(e), y_of(e + 1)}, psi_s, my1[i0], my1[i1], my0[i0], my0[i1]);
-        if (p > 0) finish(p - 1, pending);
+        if (p > 0) mm_finish_pair<E, G>(beta, p - 1, pending, n_full, K, lane, kMeasure, num, den);
         pending = st;
     }
-    if (E / 2 > 0) finish(E / 2 - 1, pending);
+    if (E / 2 > 0) mm_finish_pair<E, G>(beta, E / 2 - 1, pending, n_full, K, lane, kMeasure, num, den);
     if (E & 1) {
         constexpr int e = E - 1;
-        const float a = beta[e];
         const int i = (int)(slot[e >> 1] & 0xffffu);
-        const float nb = mm_update_algebra(a, y_of(e), psi_s, my1[i], my0[i]);
-        const bool ok = elem_of<E, G>(e, lane) < K;
-        if (measure && ok) {
-            const double df = (double)nb - (double)a;
-            num += df * df;
-            den += (double)a * (double)a;
-        }
-        beta[e] = ok ? nb : 0.0f;
+        mm_finish_one<E, G>(beta, e, mm_update_algebra(beta[e], y_of(e), psi_s, my1[i], my0[i]), K, lane, kMeasure, num, den);
     }
 }
 
@@ -1381,6 +1363,10 @@ template <int E, int G, int KC = 0>
 __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, bool active,
                                                       const LogTabEntry* tab, float* my0, float* my1, bool measure,
                                                       double& num, double& den, SplitPlacement<E>& pl, bool keep_placement) {
+    // The head (row sum, domain test, tiny flag, digamma of the sum) and the class-A / class-B passes below stand a second time in
+    // mm_iterate_wave_reuse.  As shared functions they cost several instantiations of both kernels, all at 128 VGPRs, 16 B of
+    // scratch (profiles/mm_shared_stages_codegen.txt).
+
     const int lane64 = threadIdx.x & 63;
     float s = 16.0f;
     bool in_domain = true;
@@ -1394,20 +1380,7 @@ __device__ __forceinline__ void mm_iterate_wave_split(float (&beta)[E], const Ro
     }
     s = __shfl(s, 0, G);                                            // the row's sum in every lane of its group
     if (__builtin_expect(!__all(in_domain), 0)) {                   // NaN / inf / out of range somewhere in the wavefront
-        if (active) {
-            const float psi_s = digamma_f32(s);
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const float nb = mm_update_generic(beta[e], yv.get(e), psi_s);
-                const bool ok = elem_of<E, G>(e, lane) < K;
-                if (measure && ok) {
-                    const double df = (double)nb - (double)beta[e];
-                    num += df * df;
-                    den += (double)beta[e] * (double)beta[e];
-                }
-                beta[e] = ok ? nb : 0.0f;
-            }
-        }
+        if (active) mm_generic_row<E, G>(beta, yv, K, lane, s, measure, num, den);
         pl.valid = false;                                           // the generic path keeps no placement
         return;
     }
@@ -1561,11 +1534,7 @@ __global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void 
         RowY<E, G, kSplitYRegsMaxE> yv;
         double num = 0.0, den = 0.0;
         yv.load(a.y + (size_t)row * K, lane, K);
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int d = elem_of<E, G>(e, lane);
-            beta[e] = (active && d < K) ? a.alpha[(size_t)row * K + d] : 0.0f;
-        }
+        mm_load_row<E, G>(beta, a.alpha, row, K, lane, active);
         SplitPlacement<E> pl;
         pl.valid = false;
         pl.sorts = 0;
@@ -1579,11 +1548,7 @@ __global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void 
             atomicAdd(a.work_counter + 2, (unsigned long long)pl.sorts);
         }
         if (!active) continue;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int d = elem_of<E, G>(e, lane);
-            if (d < K) a.alpha[(size_t)row * K + d] = beta[e];
-        }
+        mm_store_row<E, G>(a.alpha, row, K, lane, beta);
         if (a.work_counter && lane == 0)
             atomicAdd(a.work_counter, (unsigned long long)K * (unsigned long long)(a.l1 - a.l0 + 1));
         if (a.has_check) {
@@ -1622,11 +1587,7 @@ template <int E, int G, bool kTiny, bool kMeasure>
 __device__ __forceinline__ void reuse_apply_updates(float (&beta)[E], const RowY<E, G, kSplitYRegsMaxE>& yv, int K, int lane, float psi_s,
                                                     float* my0, const float* my1, uint16_t* q, int cap, ReuseState& rs,
                                                     double& num, double& den) {
-    constexpr bool measure = kMeasure;
-    constexpr bool kYLocal = !RowY<E, G, kSplitYRegsMaxE>::kInRegs;
-    float yl[kYLocal ? E : 1];
-    if constexpr (kYLocal) yv.fetch_all(yl);
-    auto y_of = [&](int e) { if constexpr (kYLocal) return yl[e]; else return yv.get(e); };
+    const PhaseCY<E, G, kSplitYRegsMaxE> y_of(yv);
     const int n_full = full_registers<E, G>(K);
     const int lane64 = threadIdx.x & 63;
     float* h0 = my0 + lane64;                                       // this lane's home words: register e at h0[64 e]
@@ -1653,22 +1614,7 @@ __device__ __forceinline__ void reuse_apply_updates(float (&beta)[E], const RowY
     };
     auto finish = [&](int p, const PkUpdateStage& st) {
         const int e = 2 * p;
-        const f2 a{beta[e], beta[e + 1]};
-        const f2 nb = pk_mm_update_stage2(st);
-        const bool full = e + 1 < n_full;
-        const bool ok0 = full || elem_of<E, G>(e, lane) < K, ok1 = full || elem_of<E, G>(e + 1, lane) < K;
-        if (measure) {
-            const double d0 = (double)nb.x - (double)a.x, d1 = (double)nb.y - (double)a.y;
-            if (ok0) { num += d0 * d0; den += (double)a.x * (double)a.x; }
-            if (ok1) { num += d1 * d1; den += (double)a.y * (double)a.y; }
-        }
-        if (full) {
-            beta[e] = nb.x;
-            beta[e + 1] = nb.y;
-        } else {
-            beta[e] = ok0 ? nb.x : 0.0f;
-            beta[e + 1] = ok1 ? nb.y : 0.0f;
-        }
+        const f2 a = mm_finish_pair<E, G>(beta, p, st, n_full, K, lane, kMeasure, num, den);
         note(e, a.x, beta[e]);
         note(e + 1, a.y, beta[e + 1]);
     };
@@ -1685,15 +1631,7 @@ __device__ __forceinline__ void reuse_apply_updates(float (&beta)[E], const RowY
     if (E / 2 > 0) finish(E / 2 - 1, pending);
     if (E & 1) {
         constexpr int e = E - 1;
-        const float a = beta[e];
-        const float nb = mm_update_algebra(a, y_of(e), psi_s, h1[64 * e], h0[64 * e]);
-        const bool ok = elem_of<E, G>(e, lane) < K;
-        if (measure && ok) {
-            const double df = (double)nb - (double)a;
-            num += df * df;
-            den += (double)a * (double)a;
-        }
-        beta[e] = ok ? nb : 0.0f;
+        const float a = mm_finish_one<E, G>(beta, e, mm_update_algebra(beta[e], y_of(e), psi_s, h1[64 * e], h0[64 * e]), K, lane, kMeasure, num, den);
         note(e, a, beta[e]);
     }
     rs.nS = cS;
@@ -1719,24 +1657,10 @@ __device__ __forceinline__ void mm_iterate_wave_reuse(float (&beta)[E], const Ro
     }
     s = __shfl(s, 0, G);                                            // the row's sum in every lane of its group
     if (__builtin_expect(!__all(in_domain), 0)) {                   // NaN / inf / out of range somewhere in the wavefront
-        if (active) {
-            const float psi_s = digamma_f32(s);
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const float nb = mm_update_generic(beta[e], yv.get(e), psi_s);
-                const bool ok = elem_of<E, G>(e, lane) < K;
-                if (measure && ok) {
-                    const double df = (double)nb - (double)beta[e];
-                    num += df * df;
-                    den += (double)beta[e] * (double)beta[e];
-                }
-                beta[e] = ok ? nb : 0.0f;
-            }
-        }
+        if (active) mm_generic_row<E, G>(beta, yv, K, lane, s, measure, num, den);
         rs.full = true;                                             // the generic path leaves nothing in the planes
         return;
     }
-    // the tiny-parameter flag and digamma of the row sum: as in mm_iterate_wave_split
     constexpr int kFirstRagged = first_ragged_register<E, G, KC>();
     int32_t smallest = 0x7f800000;
 #pragma unroll
@@ -1876,11 +1800,7 @@ __global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void 
         RowY<E, G, kSplitYRegsMaxE> yv;
         double num = 0.0, den = 0.0;
         yv.load(a.y + (size_t)row * K, lane, K);
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int d = elem_of<E, G>(e, lane);
-            beta[e] = (active && d < K) ? a.alpha[(size_t)row * K + d] : 0.0f;
-        }
+        mm_load_row<E, G>(beta, a.alpha, row, K, lane, active);
         ReuseState rs;
         rs.nS = rs.nL = 0;
         rs.full = true;                                             // nothing is cached across launches
@@ -1890,11 +1810,7 @@ __global__ __launch_bounds__(64, (E > 16 ? kMMWavesLarge : kMMWavesSmall)) void 
         if (a.work_counter && (threadIdx.x & 63) == 0)             // [4]: entries this kernel evaluated
             atomicAdd(a.work_counter + 4, (unsigned long long)rs.evaluated);
         if (!active) continue;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int d = elem_of<E, G>(e, lane);
-            if (d < K) a.alpha[(size_t)row * K + d] = beta[e];
-        }
+        mm_store_row<E, G>(a.alpha, row, K, lane, beta);
         if (a.work_counter && lane == 0) {                          // [0]: with k_mm_live's (the first outer iteration); [5]: this kernel's own
             const unsigned long long updates = (unsigned long long)K * (unsigned long long)(a.l1 - a.l0 + 1);
             atomicAdd(a.work_counter, updates);
