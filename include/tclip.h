@@ -585,8 +585,9 @@ int tclip_bdcspn_visual_run(const tclip_problem* p, int32_t dim, const float* x_
                             size_t workspace_bytes, void* stream);
 
 /* Optional instrumentation used by bench.py (thread-local, off by default).  While enabled,
- * every launch of the live-row majorize-minimize kernel (k_mm_live, the dominant kernel) issued by
- * tclip_em_dirichlet_run on this thread is bracketed by HIP events on the stream it is launched
+ * every launch of a live-row majorize-minimize kernel (k_mm_live, k_mm_reuse or k_mm_split, the dominant kernels; the
+ * dead-row launches and the probes are not covered) issued by the tclip_em_dirichlet_run* entries on this thread is
+ * bracketed by HIP events on the stream it is launched
  * on (independent batches run on a few internal streams, so launches overlap) and the
  * element-updates it executes are counted on the device.  tclip_profile_collect synchronises the device and returns, since the last collection:
  * the time during which at least one such launch was running (union of the intervals), the sum
@@ -594,8 +595,9 @@ int tclip_bdcspn_visual_run(const tclip_problem* p, int32_t dim, const float* x_
 int tclip_profile_enable(int on);
 int tclip_profile_collect(double* mm_busy_ms, double* mm_launch_ms_sum, int64_t* mm_launches,
                           int64_t* element_updates);
-/* The same four figures of the LAST tclip_profile_collect of this thread per kernel: index 0 = k_mm_live (the first outer
- * iteration, k_mm_reuse's launches included, and row lengths without a split instantiation), 1 = k_mm_split.  Every argument points to two values. */
+/* The same four figures of the LAST tclip_profile_collect of this thread per kernel: index 0 = k_mm_live plus k_mm_reuse (the
+ * first outer iteration, and every launch of row lengths without a split instantiation), 1 = k_mm_split.  Every argument
+ * points to two values. */
 int tclip_profile_last_kernels(double* busy_ms, double* launch_ms_sum, int64_t* launches, int64_t* element_updates);
 /* k_mm_split keeps the placement of a wavefront's elements in its three class queues from one MM iteration to the next and
  * sorts anew only when an element has left its class: the wavefront-iterations the kernel ran in the window of the LAST

@@ -3185,12 +3185,12 @@ static int check_workspace(const void* ws, size_t have, size_t need, const char*
     return TCLIP_OK;
 }
 
-// Optional instrumentation (bench.py): HIP events around every k_mm_live launch and a device
+// Optional instrumentation (bench.py): HIP events around every live-row MM launch and a device
 // counter of the element-updates it executes.  Thread-local, off by default, never touched otherwise.
 struct Profile {
     bool on = false;
     std::vector<hipEvent_t> ev;      // start/stop pairs, reused across collections
-    std::vector<uint8_t> kind;       // per pair: 0 = k_mm_live, 1 = k_mm_split
+    std::vector<uint8_t> kind;       // per pair: 0 = k_mm_live / k_mm_reuse, 1 = k_mm_split
     size_t used = 0;
     unsigned long long* counter = nullptr;      // [6]: element-updates executed by k_mm_live / k_mm_split; k_mm_split's wavefront-iterations / full placements;
                                                 // k_mm_reuse's evaluated entries / element-updates
@@ -3200,15 +3200,22 @@ struct Profile {
     uint64_t last_reuse[2] = {0, 0};                              // k_mm_reuse: entries evaluated, element-updates executed (those also under k_mm_live)
     int64_t last_split_iterations = 0, last_split_sorts = 0;    // k_mm_split: wavefront-iterations, and how many of them sorted their queues anew
 };
-static thread_local bool g_last_mm_was_split = false;     // which kernel the last launch_mm(kMMSplit / kMMLive) started
 thread_local Profile g_prof;
-static int g_probe_chunks = kProbeChunks;           // tclip_debug_set_probe_chunks
-static int g_dead_head = kDeadHead;                 // tclip_debug_set_dead_head: iterations a fresh dead row runs before the early probe; 0 = no early probe
-static int g_rowset_min_rows = -1;                  // tclip_debug_set_rowset_min_rows; negative: the default rule
-static int g_mm_split = -1;                         // tclip_debug_set_mm_split: 0 never, 1 always, negative: from the second outer iteration on
-static int g_split_keep_placement = 1;              // tclip_debug_set_split_keep_placement: 0 = k_mm_split sorts its queues in every iteration
-static int g_mm_reuse = 1;                          // tclip_debug_set_mm_reuse: 0 = k_mm_live for the whole first outer iteration, 1 = k_mm_reuse from its
-                                                    // chunk 1 on, 2 = the same with a 64-entry index queue
+
+// The process-wide debug knobs (tclip_debug_set_*, tests and A/B timing): every setting must give the same bits.
+struct Knobs {
+    int probe_chunks = kProbeChunks;    // chunks after which the limit-cycle probe runs
+    int dead_head = kDeadHead;          // iterations a fresh dead row runs before the early probe; 0 = no early probe
+    int rowset_min_rows = -1;           // 0 = the 32-lane layout of the MM kernels for every row length; negative: the default rule
+    int mm_split = -1;                  // k_mm_split: 0 never, 1 always, 100 + n from outer iteration n on, negative: from kSplitFrom on
+    int split_keep_placement = 1;       // 0 = k_mm_split sorts its queues in every iteration
+    int mm_reuse = 1;                   // 0 = k_mm_live for the whole first outer iteration, 1 = k_mm_reuse from its chunk 1 on,
+                                        // 2 = the same with a 64-entry index queue
+    int fixed_k_kernels = 1;            // 0 = the run-time-K MM kernels for every row length
+    int kmeans_tile = -1;               // 0 = the round-3 kernels for every shape (k_kmeans_logits_rows, k_mstats_rows, ...) instead of
+                                        // the tile and 75-column kernels, negative: the default rule
+};
+static Knobs g_knobs;
 
 static hipEvent_t prof_event() {
     if (g_prof.used == g_prof.ev.size()) {
@@ -3220,49 +3227,79 @@ static hipEvent_t prof_event() {
 }
 
 constexpr int kDecideSlices = 64;     // blocks per batch in the first stage of the stop test (large batches)
-struct Layout {
-    size_t logz, y, alpha_old, beta_dead, sup, cnt, cs, live, rowc, logit0, cache, cache_len, rowpart, mm_rows,
-        mm_rows2, mm_rows3, dead_counts, cls, n_live, live_rows, counts, flags, stop, ratio, dpart, total;
-    int n_checks;
-};
-
 static int n_chunks_of(int iter_mm) { return iter_mm <= 51 ? 1 : 1 + (iter_mm - 51 + 49) / 50; }
 static int n_checks_of(int iter_mm) { return iter_mm <= 50 ? 0 : (iter_mm - 1) / 50; }
 
-static Layout make_layout(const tclip_problem& p) {
-    Layout L;
-    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
+// EM-Dirichlet's workspace for `p.n_batches` consecutive batches (one stream group), as typed pointers into it.
+// `bytes` is what the view occupies; a null `base` gives the size alone (every pointer null).  Few-shot has no dead rows and
+// zero-shot no support statistics: the parts a mode lacks take no room and read null.
+struct Workspace {
+    float *logz, *y, *alpha_old, *beta_dead, *sup, *cnt, *cs;
+    uint8_t* live;
+    float *rowc, *logit0;
+    double* cache;                  // [row][n_checks][2]
+    int32_t* cache_len;
+    double* rowpart;
+    int32_t* mm_rows;
+    int32_t* dead_list[2];          // chunk c sweeps dead_list[c & 1]
+    int32_t* head_back;             // rows the early probe hands back to the old dead-row path
+    int32_t* dead_counts;           // [chunk] length of that chunk's list + one spare + [n_chunks + 2]: length of head_back
+    int16_t* cls;                   // compacted lists of live classes (k_live_class_lists)
+    int32_t *n_live, *live_rows, *counts;
+    int32_t* flags;                 // [0]: some log z is not finite
+    int32_t* stop;
+    float* ratio;
+    double* dpart;
+    // the until-stable entries' state, behind the plain layout (`stable`; null otherwise)
+    int32_t* prev_preds;            // [T, Q] the predictions after the previous outer iteration, -1 before the first
+    int32_t* quiet;                 // [B] change-free outer iterations in a row
+    int32_t* done;                  // [B] the batch is stable: nothing of it is written any more
+    int n_chunks, n_checks;         // MM chunks per outer iteration; checkpoints cached per dead row (few-shot: 0, nothing to cache)
+    size_t bytes;
+};
+static Workspace workspace_view(const tclip_problem& p, bool stable, char* base) {
+    Workspace w;
+    const size_t B = p.n_batches, T = B * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
     const bool zs = p.n_support == 0;
-    L.n_checks = n_checks_of(p.iter_mm);
+    w.n_chunks = n_chunks_of(p.iter_mm);
+    w.n_checks = zs ? n_checks_of(p.iter_mm) : 0;
     size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    L.logz = take(T * Q * K * 4);
-    L.y = take(T * K * K * 4);
-    L.alpha_old = take(T * K * K * 4);
-    L.beta_dead = take(zs ? T * K * K * 4 : 0);
-    L.sup = take(zs ? 0 : T * K * K * 4);
-    L.cnt = take(zs ? 0 : T * K * 4);
-    L.cs = take(T * K * 4);
-    L.live = take(T * K);
-    L.rowc = take(T * K * 4);
-    L.logit0 = take(T * Q * K * 4);
-    L.cache = take(zs ? T * K * (size_t)L.n_checks * 16 : 0);
-    L.cache_len = take(T * K * 4);
-    L.rowpart = take(T * K * 16);
-    L.mm_rows = take(T * K * 4);
-    L.mm_rows2 = take(zs ? T * K * 4 : 0);
-    L.mm_rows3 = take(zs ? T * K * 4 : 0);                    // rows the early probe hands back to the old dead-row path
-    L.dead_counts = take(((size_t)n_chunks_of(p.iter_mm) + 3) * 4);    // [chunk] + one spare + [n_chunks + 2]: length of mm_rows3
-    L.cls = take(zs ? T * K * 2 : 0);                         // compacted lists of live classes (k_live_class_lists)
-    L.n_live = take(zs ? T * 4 : 0);
-    L.live_rows = take(T * K * 4);
-    L.counts = take(256);
-    L.flags = take(256);
-    L.stop = take((size_t)p.n_batches * 4);
-    L.ratio = take(T * 4);
-    L.dpart = take((size_t)p.n_batches * kDecideSlices * 2 * sizeof(double));
-    L.total = o;
-    return L;
+    auto take = [&](auto*& ptr, size_t bytes, bool present = true) {
+        ptr = base && present ? (std::remove_reference_t<decltype(ptr)>)(base + o) : nullptr;
+        o += present ? align_up(bytes) : 0;
+    };
+    take(w.logz, T * Q * K * 4);
+    take(w.y, T * K * K * 4);
+    take(w.alpha_old, T * K * K * 4);
+    take(w.beta_dead, T * K * K * 4, zs);
+    take(w.sup, T * K * K * 4, !zs);
+    take(w.cnt, T * K * 4, !zs);
+    take(w.cs, T * K * 4);
+    take(w.live, T * K);
+    take(w.rowc, T * K * 4);
+    take(w.logit0, T * Q * K * 4);
+    take(w.cache, T * K * (size_t)w.n_checks * 16, zs);
+    take(w.cache_len, T * K * 4);
+    take(w.rowpart, T * K * 16);
+    take(w.mm_rows, T * K * 4);
+    take(w.dead_list[1], T * K * 4, zs);
+    w.dead_list[0] = w.mm_rows;
+    if (!zs) w.dead_list[1] = w.mm_rows;
+    take(w.head_back, T * K * 4, zs);
+    take(w.dead_counts, ((size_t)w.n_chunks + 3) * 4);
+    take(w.cls, T * K * 2, zs);
+    take(w.n_live, T * 4, zs);
+    take(w.live_rows, T * K * 4);
+    take(w.counts, 256);
+    take(w.flags, 256);
+    take(w.stop, B * 4);
+    take(w.ratio, T * 4);
+    take(w.dpart, B * kDecideSlices * 2 * sizeof(double));
+    take(w.prev_preds, T * Q * 4, stable);
+    take(w.quiet, B * 4, stable);
+    take(w.done, B * 4, stable);
+    w.bytes = o;
+    return w;
 }
 
 static int check_problem(const tclip_problem* p) {
@@ -3302,112 +3339,108 @@ static void dispatch_E(int K, Args... args) {
 // 1000 tasks (MM loop, 32 -> 16 lanes): K = 10 95 -> 71 ms, K = 37 186 -> 151, K = 47 217 -> 174, K = 100 476 -> 411
 // (460 with round 1's two rows per 32-lane group), K = 196 974 -> 895.  8 lanes per row measured slower than 16 at 1000
 // tasks (too few wavefronts: K = 10 / 37 / 47: 81 / 166 / 211 ms against 71 / 151 / 174), 2 % faster at 3000 tasks of
-// K = 100.  g_rowset_min_rows == 0 (test hook) forces the 32-lane layout, which must give the same bits.
+// K = 100.  g_knobs.rowset_min_rows == 0 (test hook) forces the 32-lane layout, which must give the same bits.
 constexpr int kG16MaxK = 256;
 static_assert(kG16MaxK >= 100 && kG16MaxK < 397 && kG64MinK <= 1000,
               "launch_mm's fixed-K kernels: K = 100 in the 16-lane, 397 in the 32-lane, 1000 in the 64-lane layout");
-// lanes per row of the MM kernels for rows of K elements (the 64-lane layout needs the cascade's first dump, K >= 512:
-// kG64MinK >= 897)
-static int mm_lanes_per_row(int K) {
-    if (g_rowset_min_rows == 0) return 32;
-    if (K >= kG64MinK) return 64;
-    return K <= kG16MaxK ? 16 : 32;
-}
-enum MMKind { kMMLive = 0, kMMDead = 1, kMMProbe = 2, kMMSplit = 3, kMMProbeHead = 4, kMMReuse = 5 };
-template <int E, int G, int KC = 0>
-static void launch_mm_EG(int dead, int rows, hipStream_t st, const MMArgs& a) {
-    constexpr int kWaves = 4, kRowsPerBlock = (64 / G) * kWaves;
-    int grid = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    if (grid > 256 * 16) grid = 256 * 16;
-    if (dead == kMMSplit) {                        // live rows through the class-split kernel where it exists (kSplitMinE <= E <= kSplitMaxE)
-        if constexpr (E <= kSplitMaxE && E >= kSplitMinE) {
-            constexpr int kSplitRows = 64 / G;           // one wavefront per block
-            int sgrid = (rows + kSplitRows - 1) / kSplitRows;
-            if (sgrid > 256 * 64) sgrid = 256 * 64;
-            hipLaunchKernelGGL((k_mm_split<E, G, KC>), dim3(sgrid), dim3(64), 0, st, a);
-            g_last_mm_was_split = true;
-            return;
-        }
-        dead = kMMLive;
-    }
-    if (dead == kMMReuse) {                        // live rows, chunks 1.. of the first outer iteration; instantiated where k_mm_split is
-        if constexpr (E <= kSplitMaxE && E >= kSplitMinE) {
-            constexpr int kReuseRows = 64 / G;           // one wavefront per block
-            int rgrid = (rows + kReuseRows - 1) / kReuseRows;
-            if (rgrid > 256 * 64) rgrid = 256 * 64;
-            hipLaunchKernelGGL((k_mm_reuse<E, G, KC>), dim3(rgrid), dim3(64), 0, st, a);
-            return;
-        }
-        dead = kMMLive;
-    }
-    if (dead == kMMProbe) hipLaunchKernelGGL((k_mm_probe<E, G>), dim3(grid), dim3(256), 0, st, a);
-    else if (dead == kMMProbeHead) {
-        if constexpr (KC == 0) hipLaunchKernelGGL((k_mm_probe_head<E, G>), dim3(grid), dim3(256), 0, st, a);      // (launch_mm: probes have no fixed-K build)
-    } else if (dead) hipLaunchKernelGGL((k_mm_live<E, kWaves, true, 1, G, KC>), dim3(grid), dim3(64 * kWaves), 0, st, a);
-    else hipLaunchKernelGGL((k_mm_live<E, kWaves, false, 1, G, KC>), dim3(grid), dim3(64 * kWaves), 0, st, a);
-}
-template <int G>
-static void launch_mm_G(int need, int dead, int rows, hipStream_t st, const MMArgs& a) {
-    if (need <= 1) return launch_mm_EG<1, G>(dead, rows, st, a);
-    if (need <= 2) return launch_mm_EG<2, G>(dead, rows, st, a);
-    if (need <= 3) return launch_mm_EG<3, G>(dead, rows, st, a);
-    if (need <= 4) return launch_mm_EG<4, G>(dead, rows, st, a);
-    if (need <= 5) return launch_mm_EG<5, G>(dead, rows, st, a);
-    if (need <= 6) return launch_mm_EG<6, G>(dead, rows, st, a);
-    if (need <= 7) return launch_mm_EG<7, G>(dead, rows, st, a);
-    if (need <= 8) return launch_mm_EG<8, G>(dead, rows, st, a);
-    if (need <= 10) return launch_mm_EG<10, G>(dead, rows, st, a);
-    if (need <= 13) return launch_mm_EG<13, G>(dead, rows, st, a);
-    if (need <= 16) return launch_mm_EG<16, G>(dead, rows, st, a);
-    if constexpr (G == 32) {
-        if (need <= 20) return launch_mm_EG<20, G>(dead, rows, st, a);
-        if (need <= 24) return launch_mm_EG<24, G>(dead, rows, st, a);
-        if (need <= 28) return launch_mm_EG<28, G>(dead, rows, st, a);
-        return launch_mm_EG<32, G>(dead, rows, st, a);
-    }
-}
-// registers per lane launch_mm_G picks for `need`
-static int mm_regs_of(int need) {
-    if (need <= 8) return need;
-    if (need <= 10) return 10;
-    if (need <= 13) return 13;
-    if (need <= 16) return 16;
-    if (need <= 20) return 20;
-    if (need <= 24) return 24;
-    return need <= 28 ? 28 : 32;
-}
-// does launch_mm(kMMSplit, K, ..) start k_mm_split (true) or fall back to k_mm_live (no instantiation for this row length)?
-static bool mm_has_split(int K) {
-    const int G = mm_lanes_per_row(K);
-    const int E = G == 64 ? 16 : mm_regs_of((K + G - 1) / G);
-    return E <= kSplitMaxE && E >= kSplitMinE;
-}
-// Row lengths the MM kernels are also compiled for as constants - the class counts of the reference's datasets that BASELINE.json
-// runs (ImageNet 1000, SUN397 397, Caltech101-sized 100): same code, same layout as the run-time-K kernel of the row length's
-// bucket, with every mask and tail of a ragged last register resolved by the compiler (round 4: the run-time forms kept
-// 2 x 4 lane masks per row sum in spilled scalar registers).  g_fixed_k_kernels == 0 (tclip_debug_set_fixed_k_kernels, tests)
-// or the 32-lane test hook: the run-time-K kernels for every row length, which must give the same bits.
-static int g_fixed_k_kernels = 1;
 // Lane layouts in which k_mm_reuse replaces k_mm_live.  Same machine, tclip_debug_set_mm_reuse 0 against 1, summed time of the
 // first outer iteration's live-row launches / time per engine call (three stream groups, 1000 MM iterations at most):
 //   16 lanes: K = 65 -34 % / -1.1 %, K = 100 -35 % / -0.5 %, K = 196 -29 % / -1.8 %, K = 256 -14 % / -0.4 %
 //   32 lanes: K = 300 -21 % / -2.4 %, K = 397 hard -20 % / -4.1 %
 //   64 lanes: K = 1000 against the parent's library -5.4 % per call, few-shot K = 1000 -2.1 % (profiles/mm_reuse_ab.txt)
 constexpr bool kReuseG16 = true, kReuseG32 = true, kReuseG64 = true;
-static bool mm_reuse_pays(int K) {
-    const int G = mm_lanes_per_row(K);
-    return G == 64 ? kReuseG64 : (G == 32 ? kReuseG32 : kReuseG16);
+
+// The layout the MM kernels run rows of K elements in, under the current knobs: the one place that knows it.
+struct MMPlan {
+    int G;              // lanes per row (the 64-lane layout needs the cascade's first dump, K >= 512: kG64MinK >= 897)
+    int E;              // registers per lane: the smallest instantiated bucket that covers ceil(K / G)
+    int KC;             // K where the live, dead, split and reuse kernels are also compiled for exactly this row length, else 0
+    bool split;         // k_mm_split<E, G, KC> and k_mm_reuse<E, G, KC> exist (kSplitMinE <= E <= kSplitMaxE)
+    bool reuse;         // ... and k_mm_reuse pays in this lane layout
+    int reuse_cap;      // entries of k_mm_reuse's index queue in use
+};
+// Row lengths the MM kernels are also compiled for as constants - the class counts of the reference's datasets that BASELINE.json
+// runs (ImageNet 1000, SUN397 397, Caltech101-sized 100): same code, same layout as the run-time-K kernel of the row length's
+// bucket, with every mask and tail of a ragged last register resolved by the compiler (round 4: the run-time forms kept
+// 2 x 4 lane masks per row sum in spilled scalar registers).  fixed_k_kernels == 0 (tests) or the 32-lane test hook: the
+// run-time-K kernels for every row length, which must give the same bits.
+static MMPlan mm_plan(int K, const Knobs& k) {
+    static const int8_t bucket[33] = {1, 1, 2, 3, 4, 5, 6, 7, 8, 10, 10, 13, 13, 13, 16, 16, 16, 20, 20, 20, 20, 24, 24, 24, 24,
+                                      28, 28, 28, 28, 32, 32, 32, 32};        // [ceil(K / G)], the cases of launch_mm_G
+    MMPlan pl;
+    pl.G = k.rowset_min_rows == 0 ? 32 : (K >= kG64MinK ? 64 : (K <= kG16MaxK ? 16 : 32));
+    pl.E = pl.G == 64 ? 16 : bucket[(K + pl.G - 1) / pl.G];
+    pl.KC = k.rowset_min_rows != 0 && k.fixed_k_kernels && (K == 1000 || K == 397 || K == 100) ? K : 0;
+    pl.split = pl.E <= kSplitMaxE && pl.E >= kSplitMinE;
+    pl.reuse = pl.split && (pl.G == 64 ? kReuseG64 : (pl.G == 32 ? kReuseG32 : kReuseG16));
+    pl.reuse_cap = k.mm_reuse == 2 ? 64 : kReuseQueue;
+    return pl;
 }
-static void launch_mm(int dead, int K, int rows, hipStream_t st, const MMArgs& a) {
-    if (g_rowset_min_rows != 0 && g_fixed_k_kernels && dead != kMMProbe && dead != kMMProbeHead) {
-        if (K == 1000) return launch_mm_EG<16, 64, 1000>(dead, rows, st, a);
-        if (K == 397) return launch_mm_EG<13, 32, 397>(dead, rows, st, a);
-        if (K == 100) return launch_mm_EG<7, 16, 100>(dead, rows, st, a);
+enum MMKind { kMMLive = 0, kMMDead = 1, kMMProbe = 2, kMMSplit = 3, kMMProbeHead = 4, kMMReuse = 5 };
+// The kernel of the live rows in chunk `c` of outer iteration `it`: the class-split kernel once the parameters have moved away
+// from their start at 1 (mm_split: 0 never, 1 always, 100 + n from iteration n on, negative from kSplitFrom on), under that
+// default rule k_mm_reuse in chunks 1.. of the first outer iteration; k_mm_live where the row length has neither.
+static MMKind mm_live_kind(int it, int c, const MMPlan& pl, const Knobs& k) {
+    const bool split = k.mm_split < 0 ? it >= kSplitFrom : (k.mm_split >= 100 ? it >= k.mm_split - 100 : k.mm_split != 0);
+    if (split) return pl.split ? kMMSplit : kMMLive;
+    return k.mm_split < 0 && k.mm_reuse != 0 && it == 0 && c > 0 && pl.reuse ? kMMReuse : kMMLive;
+}
+
+// Launches the kernel of `kind`; mm_live_kind asks for kMMSplit / kMMReuse only where the plan has them, and the probes
+// have no fixed-K build (launch_mm).
+template <int E, int G, int KC = 0>
+static void launch_mm_EG(MMKind kind, int rows, hipStream_t st, const MMArgs& a) {
+    constexpr int kWaves = 4, kRowsPerBlock = (64 / G) * kWaves;
+    int grid = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+    if (grid > 256 * 16) grid = 256 * 16;
+    int grid1 = (rows + 64 / G - 1) / (64 / G);         // k_mm_split, k_mm_reuse: one wavefront per block
+    if (grid1 > 256 * 64) grid1 = 256 * 64;
+    switch (kind) {
+    case kMMSplit:
+        if constexpr (E <= kSplitMaxE && E >= kSplitMinE) hipLaunchKernelGGL((k_mm_split<E, G, KC>), dim3(grid1), dim3(64), 0, st, a);
+        break;
+    case kMMReuse:
+        if constexpr (E <= kSplitMaxE && E >= kSplitMinE) hipLaunchKernelGGL((k_mm_reuse<E, G, KC>), dim3(grid1), dim3(64), 0, st, a);
+        break;
+    case kMMProbe: hipLaunchKernelGGL((k_mm_probe<E, G>), dim3(grid), dim3(256), 0, st, a); break;
+    case kMMProbeHead:
+        if constexpr (KC == 0) hipLaunchKernelGGL((k_mm_probe_head<E, G>), dim3(grid), dim3(256), 0, st, a);
+        break;
+    case kMMDead: hipLaunchKernelGGL((k_mm_live<E, kWaves, true, 1, G, KC>), dim3(grid), dim3(64 * kWaves), 0, st, a); break;
+    case kMMLive: hipLaunchKernelGGL((k_mm_live<E, kWaves, false, 1, G, KC>), dim3(grid), dim3(64 * kWaves), 0, st, a); break;
     }
-    const int G = mm_lanes_per_row(K);
-    if (G == 64) launch_mm_EG<16, 64>(dead, rows, st, a);
-    else if (G == 16) launch_mm_G<16>((K + 15) / 16, dead, rows, st, a);
-    else launch_mm_G<32>((K + 31) / 32, dead, rows, st, a);
+}
+template <int G>
+static void launch_mm_G(int E, MMKind kind, int rows, hipStream_t st, const MMArgs& a) {
+    switch (E) {
+    case 1: return launch_mm_EG<1, G>(kind, rows, st, a);
+    case 2: return launch_mm_EG<2, G>(kind, rows, st, a);
+    case 3: return launch_mm_EG<3, G>(kind, rows, st, a);
+    case 4: return launch_mm_EG<4, G>(kind, rows, st, a);
+    case 5: return launch_mm_EG<5, G>(kind, rows, st, a);
+    case 6: return launch_mm_EG<6, G>(kind, rows, st, a);
+    case 7: return launch_mm_EG<7, G>(kind, rows, st, a);
+    case 8: return launch_mm_EG<8, G>(kind, rows, st, a);
+    case 10: return launch_mm_EG<10, G>(kind, rows, st, a);
+    case 13: return launch_mm_EG<13, G>(kind, rows, st, a);
+    case 16: return launch_mm_EG<16, G>(kind, rows, st, a);
+    }
+    if constexpr (G == 32) switch (E) {                 // 16 lanes: K <= kG16MaxK, 16 registers at most
+    case 20: return launch_mm_EG<20, G>(kind, rows, st, a);
+    case 24: return launch_mm_EG<24, G>(kind, rows, st, a);
+    case 28: return launch_mm_EG<28, G>(kind, rows, st, a);
+    case 32: return launch_mm_EG<32, G>(kind, rows, st, a);
+    }
+}
+static void launch_mm(MMKind kind, const MMPlan& pl, int rows, hipStream_t st, const MMArgs& a) {
+    if (pl.KC && kind != kMMProbe && kind != kMMProbeHead) switch (pl.KC) {
+    case 1000: return launch_mm_EG<16, 64, 1000>(kind, rows, st, a);
+    case 397: return launch_mm_EG<13, 32, 397>(kind, rows, st, a);
+    case 100: return launch_mm_EG<7, 16, 100>(kind, rows, st, a);
+    }
+    if (pl.G == 64) launch_mm_EG<16, 64>(kind, rows, st, a);
+    else if (pl.G == 16) launch_mm_G<16>(pl.E, kind, rows, st, a);
+    else launch_mm_G<32>(pl.E, kind, rows, st, a);
 }
 template <int E> struct LaunchRowConsts {
     static void run(int grid, hipStream_t st, const float* alpha, const int32_t* rows, const int32_t* n, int K, float* rowc) {
@@ -3448,8 +3481,6 @@ template <int E> struct LaunchKmeansLogitsRows {
     }
 };
 
-static int g_kmeans_tile = -1;       // tclip_debug_set_kmeans_tile: 0 = the round-3 kernels for every shape (k_kmeans_logits_rows, k_mstats_rows,
-                                     // ...) instead of the tile and 75-column kernels, negative: the default rule
 // squared distances to the centroids: one lane per class where the row length allows it (k_kmeans_logits_tile), else 32 lanes per class
 // the tile kernels' dynamic LDS goes beyond the 64 KB a kernel gets without asking (once per kernel and process)
 static bool kmeans_tile_lds_raised(const void* kernel) {
@@ -3467,7 +3498,7 @@ static bool kmeans_tile_lds_raised(const void* kernel) {
 }
 static void launch_kmeans_logits(int T, hipStream_t st, const float* w, const float* z, const uint8_t* need, int Q, int K, float pre,
                                  float temperature, float* logit0) {
-    if (g_kmeans_tile != 0 && K >= 32 && K <= 511) {
+    if (g_knobs.kmeans_tile != 0 && K >= 32 && K <= 511) {
         const int stride = K | 1;
         const size_t lds = (size_t)kKmeansTile * stride * sizeof(float);
         const bool raised = kmeans_tile_lds_raised((const void*)k_kmeans_logits_tile);
@@ -3832,7 +3863,7 @@ static void launch_mstats_mode(hipStream_t st, const float* u, const float* f, c
     const long ncols = (long)K * K;
     const int full_rows = ncols >= 8 ? (int)(((ncols / 32) * 32) / K) : 0;      // rows 0 .. full_rows-1 are all-cascade
     int groups = full_rows / kMstatsRows;
-    if (!kCov && (dense || cls) && Q == kTileQ && full_rows >= 32 && g_kmeans_tile != 0) {
+    if (!kCov && (dense || cls) && Q == kTileQ && full_rows >= 32 && g_knobs.kmeans_tile != 0) {
         // 32 x 32 register tiles, both operands through LDS: over all classes where (nearly) every class is alive (the caller's
         // word), over the compacted list of the live ones where the caller provides room for it (cls, n_live)
         const int tiles_d = (K + kTileBlock - 1) / kTileBlock, tiles_k = (full_rows + kTileBlock - 1) / kTileBlock;
@@ -3844,7 +3875,7 @@ static void launch_mstats_mode(hipStream_t st, const float* u, const float* f, c
                                paddle, full_rows, wc);
         return;
     }
-    if (Q == kColsQ && full_rows >= kColsChunk && g_kmeans_tile != 0) {
+    if (Q == kColsQ && full_rows >= kColsChunk && g_knobs.kmeans_tile != 0) {
         // the column kernel takes every row of the cascade region; enough blocks to fill the machine, at least 32 rows each
         const int dtiles = (K + 63) / 64;
         int splits = (int)((8192 + (long)T * dtiles - 1) / ((long)T * dtiles));
@@ -3905,195 +3936,191 @@ const char* tclip_last_error(void) { return g_err; }
 
 namespace tclip {
 
-// The until-stable entries' part of a group of batches (tclip_em_dirichlet_run_until_stable): the outputs of the group's
-// batches and its state in the group's workspace slice, behind the plain layout.
+// The caller's tensors of a call, or of one stream group of it (run_em_dirichlet moves every pointer to the group's first
+// task / batch).  criterions and mm_iters keep the row stride of the whole call, p.iters.
+struct EmTensors {
+    RowSrc q, s;
+    const int64_t* y_s;
+    float *u, *v, *alpha;
+    int32_t* preds;
+    float* criterions;
+    int32_t* mm_iters;
+};
+// The until-stable entries' part (tclip_em_dirichlet_run_until_stable): a batch stops once its predictions have stood still
+// for `patience` outer iterations (k_assign_changes); every later launch finds its done flag (Workspace::done) and skips it.
+// Null for the plain entries: their launches and arguments are unchanged.
 struct StableStop {
     int patience;
     int32_t* outer_iters;   // [B]
     int32_t* changes;       // [B, iters]
-    int32_t* prev_preds;    // [T, Q] the predictions after the previous outer iteration, -1 before the first
-    int32_t* quiet;         // [B] change-free outer iterations in a row
-    int32_t* done;          // [B] the batch is stable: nothing of it is written any more
 };
-static size_t stable_state_bytes(const tclip_problem& p) {
-    const size_t B = p.n_batches, T = B * p.tasks_per_batch;
-    return align_up(T * p.n_query * 4) + 2 * align_up(B * 4);
-}
 
-// Enqueues the whole loop for `p.n_batches` consecutive batches on stream `st`.  `crit_stride` is
-// the row stride (= iters of the full problem) of criterions / mm_iters.
-// `stable` (optional): a batch stops once its predictions have stood still for stable->patience outer iterations
-// (k_assign_changes); every later launch finds its done flag and skips it.  Null: the plain entries' launches, unchanged.
-static int enqueue_batches(const tclip_problem& p, const RowSrc& q_src, const RowSrc& s_src, const int64_t* y_s, float* u,
-                           float* v, float* alpha, int32_t* preds, float* criterions, int32_t* mm_iters,
-                           char* ws, hipStream_t st, const StableStop* stable = nullptr) {
-    const bool zs = p.n_support == 0;
-    const Layout L = make_layout(p);
-    const int B = p.n_batches, N = p.tasks_per_batch, Q = p.n_query, K = p.n_class, S = p.n_support;
-    const int T = B * N, TK = T * K;
+// The driver's stages, in the order enqueue_batches runs them on stream `st` for the p.n_batches batches of one group.
+// ---- initialisation (em_dirichlet.py:195-211)
+static int em_init(const Workspace& w, const tclip_problem& p, const EmTensors& x, hipStream_t st) {
+    const int B = p.n_batches, Q = p.n_query, K = p.n_class, S = p.n_support, T = B * p.tasks_per_batch, TK = T * K;
     const size_t TQK = (size_t)T * Q * K, TKK = (size_t)T * K * K;
-    float* logz = (float*)(ws + L.logz);
-    float* y = (float*)(ws + L.y);
-    float* alpha_old = (float*)(ws + L.alpha_old);
-    float* beta_dead = zs ? (float*)(ws + L.beta_dead) : nullptr;
-    float* sup = zs ? nullptr : (float*)(ws + L.sup);
-    float* cnt = zs ? nullptr : (float*)(ws + L.cnt);
-    float* cs = (float*)(ws + L.cs);
-    uint8_t* live = (uint8_t*)(ws + L.live);
-    float* rowc = (float*)(ws + L.rowc);
-    float* logit0 = (float*)(ws + L.logit0);
-    double* cache = zs ? (double*)(ws + L.cache) : nullptr;
-    int32_t* cache_len = (int32_t*)(ws + L.cache_len);
-    double* rowpart = (double*)(ws + L.rowpart);
-    int32_t* mm_rows = (int32_t*)(ws + L.mm_rows);
-    int32_t* dead_list[2] = {mm_rows, zs ? (int32_t*)(ws + L.mm_rows2) : mm_rows};   // chunk c sweeps dead_list[c & 1]
-    int32_t* dead_counts = (int32_t*)(ws + L.dead_counts);                        // [chunk] length of that list
-    int32_t* head_back = zs ? (int32_t*)(ws + L.mm_rows3) : nullptr;              // rows the early probe could not finish
-    int32_t* live_rows = (int32_t*)(ws + L.live_rows);
-    int32_t* counts = (int32_t*)(ws + L.counts);
-    int32_t* flags = (int32_t*)(ws + L.flags);          // [0]: some log z is not finite
-    int32_t* stop = (int32_t*)(ws + L.stop);
-    float* ratio = (float*)(ws + L.ratio);
-    double* dpart = (double*)(ws + L.dpart);
-    const int n_chunks = n_chunks_of(p.iter_mm);
-    const int n_checks = zs ? L.n_checks : 0;   // few-shot has no dead rows: nothing to cache
-    const int32_t* done = stable ? stable->done : nullptr;
-    if (stable) {
-        TCLIP_HIP(hipMemsetAsync(stable->prev_preds, 0xff, (size_t)T * Q * 4, st));
-        TCLIP_HIP(hipMemsetAsync(stable->quiet, 0, (size_t)B * 4, st));
-        TCLIP_HIP(hipMemsetAsync(stable->done, 0, (size_t)B * 4, st));
+    if (w.done) {
+        TCLIP_HIP(hipMemsetAsync(w.prev_preds, 0xff, (size_t)T * Q * 4, st));
+        TCLIP_HIP(hipMemsetAsync(w.quiet, 0, (size_t)B * 4, st));
+        TCLIP_HIP(hipMemsetAsync(w.done, 0, (size_t)B * 4, st));
     }
-
-    // ---- initialisation (em_dirichlet.py:195-211)
-    TCLIP_HIP(hipMemsetAsync(flags, 0, 256, st));
-    if (q_src.idx) {            // rows of a feature table through the task-batch loop's index tensor: gather, copy and log in one pass
+    TCLIP_HIP(hipMemsetAsync(w.flags, 0, 256, st));
+    if (x.q.idx) {              // rows of a feature table through the task-batch loop's index tensor: gather, copy and log in one pass
         const size_t rows = (size_t)T * Q;
-        hipLaunchKernelGGL(k_gather_log_features, dim3((unsigned)(rows > 65536 ? 65536 : rows)), dim3(256), 0, st, q_src, Q, K, rows, u, logz, flags);
+        hipLaunchKernelGGL(k_gather_log_features, dim3((unsigned)(rows > 65536 ? 65536 : rows)), dim3(256), 0, st, x.q, Q, K, rows, x.u, w.logz, w.flags);
     } else {
-        hipLaunchKernelGGL(k_log_features, dim3(ew_grid(TQK)), dim3(256), 0, st, q_src.base, logz, TQK, flags);
-        hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, q_src.base, u, TQK);
+        hipLaunchKernelGGL(k_log_features, dim3(ew_grid(TQK)), dim3(256), 0, st, x.q.base, w.logz, TQK, w.flags);
+        hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x.q.base, x.u, TQK);
     }
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TKK)), dim3(256), 0, st, alpha, 1.0f, TKK);
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TKK)), dim3(256), 0, st, alpha_old, 1.0f, TKK);
-    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
-    TCLIP_HIP(hipMemsetAsync(cache_len, 0, (size_t)TK * 4, st));
-    if (!zs) {
-        hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, s_src, y_s, S, K, 1, sup, cnt);
-    }
+    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TKK)), dim3(256), 0, st, x.alpha, 1.0f, TKK);
+    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TKK)), dim3(256), 0, st, w.alpha_old, 1.0f, TKK);
+    hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, x.v, 0.0f, (size_t)TK);
+    TCLIP_HIP(hipMemsetAsync(w.cache_len, 0, (size_t)TK * 4, st));
+    if (S > 0) hipLaunchKernelGGL(k_support_stats, dim3(K, T), dim3(128), (size_t)S * sizeof(int), st, x.s, x.y_s, S, K, 1, w.sup, w.cnt);
     // E-step terms of the initial alpha = 1 for every row (rows that never come alive keep them).  Every
     // row is the same all-ones vector, so lgamma(sum) - sum lgamma is evaluated for ONE row and copied
     // (at K = 1000 the generic lgamma over all T*K*K ones took a second per 417 tasks); the
     // contraction with log z runs over the full-row list 0..TK-1 once.
-    {
-        TCLIP_HIP(hipMemsetAsync(counts, 0, 256, st));
-        hipLaunchKernelGGL(k_one_row_list, dim3(1), dim3(1), 0, st, mm_rows, counts + 2);
-        dispatch_E<LaunchRowConsts>(K, 1, st, (const float*)alpha, (const int32_t*)mm_rows, (const int32_t*)(counts + 2), K, rowc);
-        hipLaunchKernelGGL(k_broadcast_first, dim3(ew_grid((size_t)TK)), dim3(256), 0, st, rowc, (size_t)TK);
-        // live_rows <- identity, counts[1] <- TK
-        TCLIP_HIP(hipMemsetAsync(live, 1, (size_t)TK, st));
-        hipLaunchKernelGGL(k_build_rows, dim3((TK + 255) / 256), dim3(256), 0, st, live, cache_len, TK, 0, mm_rows,
-                           live_rows, counts, counts + 1);
-        hipLaunchKernelGGL(k_init_logits, dim3(ew_grid(TQK)), dim3(256), 0, st, (const float*)rowc, (const int32_t*)flags, Q, K, TQK, logit0);
-        dispatch_E<LaunchLogits>(K, TK > 262144 ? 262144 : TK, st, (const float*)alpha, (const float*)logz, (const float*)rowc,
-                                 (const int32_t*)live_rows, (const int32_t*)(counts + 1), Q, K, logit0, (const int32_t*)flags);
-    }
+    TCLIP_HIP(hipMemsetAsync(w.counts, 0, 256, st));
+    hipLaunchKernelGGL(k_one_row_list, dim3(1), dim3(1), 0, st, w.mm_rows, w.counts + 2);
+    dispatch_E<LaunchRowConsts>(K, 1, st, (const float*)x.alpha, (const int32_t*)w.mm_rows, (const int32_t*)(w.counts + 2), K, w.rowc);
+    hipLaunchKernelGGL(k_broadcast_first, dim3(ew_grid((size_t)TK)), dim3(256), 0, st, w.rowc, (size_t)TK);
+    // live_rows <- identity, counts[1] <- TK
+    TCLIP_HIP(hipMemsetAsync(w.live, 1, (size_t)TK, st));
+    hipLaunchKernelGGL(k_build_rows, dim3((TK + 255) / 256), dim3(256), 0, st, w.live, w.cache_len, TK, 0, w.mm_rows,
+                       w.live_rows, w.counts, w.counts + 1);
+    hipLaunchKernelGGL(k_init_logits, dim3(ew_grid(TQK)), dim3(256), 0, st, (const float*)w.rowc, (const int32_t*)w.flags, Q, K, TQK, w.logit0);
+    dispatch_E<LaunchLogits>(K, TK > 262144 ? 262144 : TK, st, (const float*)x.alpha, (const float*)w.logz, (const float*)w.rowc,
+                             (const int32_t*)w.live_rows, (const int32_t*)(w.counts + 1), Q, K, w.logit0, (const int32_t*)w.flags);
+    return TCLIP_OK;
+}
 
+// ---- M-step statistics of outer iteration `it`, then the lists of live and dead rows for its MM loop
+static int em_mstep_stats(const Workspace& w, const tclip_problem& p, const EmTensors& x, int it, hipStream_t st) {
+    const int B = p.n_batches, N = p.tasks_per_batch, Q = p.n_query, K = p.n_class, T = B * N, TK = T * K;
+    const bool zs = p.n_support == 0;
+    hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)x.u, T, Q, K, zs ? 1 : 0,
+                       w.cs, w.live, x.v, w.cache_len, (const int32_t*)w.done, N * K);
+    // zero-shot: every class alive in the first outer iteration, a few per cent afterwards - the tile kernel over all classes,
+    // then over the lists of the live ones; few-shot: every class alive throughout
+    const bool lists = zs && it > 0;
+    launch_mstats(st, (const float*)x.u, (const float*)w.logz, (const float*)w.cs, (const uint8_t*)w.live, (const float*)w.sup,
+                  (const float*)w.cnt, T, Q, K, w.y, 0, !lists, lists ? w.cls : nullptr, lists ? w.n_live : nullptr);
+    TCLIP_HIP(hipMemsetAsync(w.counts, 0, 256, st));
+    TCLIP_HIP(hipMemsetAsync(w.dead_counts, 0, ((size_t)w.n_chunks + 3) * 4, st));
+    if (w.done)         // a stable batch starts every outer iteration with its MM stop flag set: its MM launches are no-ops
+        TCLIP_HIP(hipMemcpyAsync(w.stop, w.done, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    else
+        TCLIP_HIP(hipMemsetAsync(w.stop, 0, (size_t)B * 4, st));
+    hipLaunchKernelGGL(k_build_rows, dim3((TK + 255) / 256), dim3(256), 0, st, (const uint8_t*)w.live,
+                       (const int32_t*)w.cache_len, TK, w.n_checks, w.dead_list[0], w.live_rows, w.dead_counts, w.counts + 1,
+                       (const int32_t*)w.done, N * K);
+    return TCLIP_OK;
+}
+
+// ---- one MM chunk: chunk `c` covers iterations l0 .. l1 and ends at a stop-test checkpoint where l1 is a multiple of 50
+static MMArgs mm_chunk_args(const Workspace& w, const tclip_problem& p, float* alpha, const MMPlan& pl, int c) {
+    MMArgs a;
+    a.alpha = alpha; a.beta_dead = w.beta_dead; a.y = w.y; a.live = w.live; a.cache_len = w.cache_len;
+    a.cache = w.cache; a.rowpart = w.rowpart; a.rows = w.live_rows; a.n_rows = w.counts + 1; a.stop = w.stop;
+    a.work_counter = nullptr; a.next_rows = nullptr; a.next_count = nullptr;
+    a.K = p.n_class; a.rows_per_batch = p.tasks_per_batch * p.n_class; a.chunk = c;
+    a.keep_placement = g_knobs.split_keep_placement;
+    a.reuse_cap = pl.reuse_cap;
+    a.l0 = c == 0 ? 0 : 50 * c + 1;
+    a.l1 = 50 * (c + 1) < p.iter_mm - 1 ? 50 * (c + 1) : p.iter_mm - 1;
+    a.has_check = (a.l1 > 0 && a.l1 % 50 == 0) ? 1 : 0;
+    a.n_checks = w.n_checks > 0 ? w.n_checks : 1;
+    return a;
+}
+// the live rows through the kernel of `kind`, between two events and with the work counter when the instrumentation is on
+static int mm_live_rows(MMArgs a, MMKind kind, const MMPlan& pl, int TK, hipStream_t st) {
+    const int split = kind == kMMSplit ? 1 : 0;
+    a.work_counter = g_prof.on ? g_prof.counter + split : nullptr;
+    hipEvent_t e0 = g_prof.on ? prof_event() : nullptr, e1 = g_prof.on ? prof_event() : nullptr;
+    if (e0 && e1) {
+        if (g_prof.kind.size() < g_prof.used / 2) g_prof.kind.resize(g_prof.used / 2);
+        g_prof.kind[g_prof.used / 2 - 1] = (uint8_t)split;
+        TCLIP_HIP(hipEventRecord(e0, st));
+    }
+    launch_mm(kind, pl, TK, st, a);
+    if (e0 && e1) TCLIP_HIP(hipEventRecord(e1, st));
+    return TCLIP_OK;
+}
+// zero-shot, chunks that end at a checkpoint: the dead rows, which only matter through their stop-test terms
+static void mm_dead_rows(const Workspace& w, MMArgs a, const MMPlan& pl, const Knobs& k, int TK, int c, hipStream_t st) {
+    a.rows = w.dead_list[c & 1]; a.n_rows = w.dead_counts + c;
+    if (c == 0 && k.dead_head > 0 && k.probe_chunks > 0) {
+        // rows that have just died: dead_head iterations, then the early probe (k_mm_probe_head), which finishes
+        // every row it finds on its cycle; what is left over takes the path below from the start
+        MMArgs h = a;
+        h.l0 = 0; h.l1 = k.dead_head - 1; h.has_check = 0;
+        launch_mm(kMMDead, pl, TK, st, h);
+        h.l0 = k.dead_head; h.next_rows = w.head_back; h.next_count = w.dead_counts + w.n_chunks + 2;
+        launch_mm(kMMProbeHead, pl, TK, st, h);
+        a.rows = w.head_back; a.n_rows = w.dead_counts + w.n_chunks + 2;
+    }
+    // the probe needs the row to be ON its cycle already; rows that were still approaching
+    // it after chunk 0 get a few more chances before they are left to iterate every chunk
+    const bool more = c + 1 < a.n_checks, probe = c < k.probe_chunks && more;
+    int32_t* next_rows = more ? w.dead_list[(c + 1) & 1] : nullptr;
+    int32_t* next_count = more ? w.dead_counts + c + 1 : nullptr;
+    a.next_rows = probe ? nullptr : next_rows; a.next_count = probe ? nullptr : next_count;
+    launch_mm(kMMDead, pl, TK, st, a);
+    a.next_rows = next_rows; a.next_count = next_count;
+    if (probe) launch_mm(kMMProbe, pl, TK, st, a);
+}
+// the stop test of every batch after chunk `c`, in two stages for large batches; writes the iteration count of outer iteration `it`
+static void mm_stop_test(const Workspace& w, const tclip_problem& p, const MMArgs& a, int c, int32_t* mm_iters_it, hipStream_t st) {
+    const int B = p.n_batches, NK = p.tasks_per_batch * p.n_class;
+    const bool two_stage = a.has_check && NK > 16384;
+    if (two_stage)
+        hipLaunchKernelGGL(k_mm_decide_partial, dim3(kDecideSlices, B), dim3(256), 0, st, (const double*)w.rowpart,
+                           (const double*)w.cache, (const uint8_t*)w.live, NK, a.n_checks, c, (const int32_t*)w.stop, w.dpart);
+    hipLaunchKernelGGL(k_mm_decide, dim3(B), dim3(1024), 0, st, (const double*)w.rowpart, (const double*)w.cache,
+                       (const uint8_t*)w.live, NK, a.n_checks, c, a.has_check, a.l1, c == w.n_chunks - 1 ? 1 : 0,
+                       p.iter_mm, w.stop, mm_iters_it, p.iters, (const double*)(two_stage ? w.dpart : nullptr),
+                       kDecideSlices);
+}
+
+// ---- E-step for the rows whose alpha changed, softmax over all classes, convergence record of outer iteration `it`
+static void em_estep(const Workspace& w, const tclip_problem& p, const EmTensors& x, int it, const StableStop* stable, hipStream_t st) {
+    const int B = p.n_batches, N = p.tasks_per_batch, Q = p.n_query, K = p.n_class, T = B * N, TK = T * K;
+    const int32_t* done = w.done;
+    const int g8 = (TK + 7) / 8 > 65535 * 8 ? 65535 * 8 : (TK + 7) / 8;
+    dispatch_E<LaunchRowConsts>(K, g8 > 4096 ? 4096 : g8, st, (const float*)x.alpha, (const int32_t*)w.live_rows,
+                                (const int32_t*)(w.counts + 1), K, w.rowc);
+    dispatch_E<LaunchLogits>(K, TK > kLogitsGrid ? kLogitsGrid : TK, st, (const float*)x.alpha, (const float*)w.logz, (const float*)w.rowc,
+                             (const int32_t*)w.live_rows, (const int32_t*)(w.counts + 1), Q, K, w.logit0, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)w.logit0, (const float*)x.v,
+                       T * Q, Q, K, (float)p.lambd, p.hard, 0, x.u, x.preds, done, N * Q);
+    hipLaunchKernelGGL(k_criterion, dim3(T), dim3(64), 0, st, (const float*)x.alpha, w.alpha_old, K, T, w.ratio, done, N);
+    hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)w.ratio, N, (p.n_support > 0 && p.hard) ? 1 : 0,
+                       x.criterions + it, p.iters, done);
+    // the batch's predictions against the previous iteration's; last, so that this iteration's record is complete
+    if (stable)
+        hipLaunchKernelGGL(k_assign_changes, dim3(B), dim3(256), 0, st, (const int32_t*)x.preds, w.prev_preds, N * Q, it,
+                           it == p.iters - 1 ? 1 : 0, stable->patience, stable->changes, p.iters, w.quiet, w.done,
+                           stable->outer_iters);
+}
+
+// Enqueues the whole loop for `p.n_batches` consecutive batches on stream `st`; `ws` holds workspace_view(p, stable, ..).bytes.
+static int enqueue_batches(const tclip_problem& p, const EmTensors& x, char* ws, hipStream_t st, const StableStop* stable) {
+    const Workspace w = workspace_view(p, stable != nullptr, ws);
+    const Knobs& knobs = g_knobs;
+    const MMPlan pl = mm_plan(p.n_class, knobs);
+    const int TK = p.n_batches * p.tasks_per_batch * p.n_class;
+    if (int rc = em_init(w, p, x, st)) return rc;
     for (int it = 0; it < p.iters; it++) {
-        // ---- M-step statistics
-        hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, zs ? 1 : 0,
-                           cs, live, v, cache_len, done, N * K);
-        // zero-shot: every class alive in the first outer iteration, a few per cent afterwards - the tile kernel over all classes,
-        // then over the lists of the live ones; few-shot: every class alive throughout
-        launch_mstats(st, (const float*)u, (const float*)logz, (const float*)cs, (const uint8_t*)live, (const float*)sup, (const float*)cnt, T, Q, K, y, 0,
-                      !zs || it == 0, (zs && it > 0) ? (int16_t*)(ws + L.cls) : nullptr, (zs && it > 0) ? (int32_t*)(ws + L.n_live) : nullptr);
-        TCLIP_HIP(hipMemsetAsync(counts, 0, 256, st));
-        TCLIP_HIP(hipMemsetAsync(dead_counts, 0, ((size_t)n_chunks + 3) * 4, st));
-        if (done)       // a stable batch starts every outer iteration with its MM stop flag set: its MM launches are no-ops
-            TCLIP_HIP(hipMemcpyAsync(stop, done, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-        else
-            TCLIP_HIP(hipMemsetAsync(stop, 0, (size_t)B * 4, st));
-        hipLaunchKernelGGL(k_build_rows, dim3((TK + 255) / 256), dim3(256), 0, st, (const uint8_t*)live,
-                           (const int32_t*)cache_len, TK, n_checks, dead_list[0], live_rows, dead_counts, counts + 1, done, N * K);
-        // ---- MM fixed point in chunks aligned with the stop-test checkpoints
-        for (int c = 0; c < n_chunks; c++) {
-            MMArgs a;
-            a.alpha = alpha; a.beta_dead = beta_dead; a.y = y; a.live = live; a.cache_len = cache_len;
-            a.cache = cache; a.rowpart = rowpart; a.rows = mm_rows; a.n_rows = counts; a.stop = stop;
-            a.next_rows = nullptr; a.next_count = nullptr;
-            a.K = K; a.rows_per_batch = N * K; a.chunk = c;
-            a.keep_placement = g_split_keep_placement;
-            a.reuse_cap = g_mm_reuse == 2 ? 64 : kReuseQueue;
-            a.l0 = c == 0 ? 0 : 50 * c + 1;
-            a.l1 = 50 * (c + 1) < p.iter_mm - 1 ? 50 * (c + 1) : p.iter_mm - 1;
-            a.has_check = (a.l1 > 0 && a.l1 % 50 == 0) ? 1 : 0;
-            a.n_checks = n_checks > 0 ? n_checks : 1;
-            // class-split kernel once the parameters have moved away from their start at 1 (k_mm_split)
-            const bool split = g_mm_split < 0 ? it >= kSplitFrom : (g_mm_split >= 100 ? it >= g_mm_split - 100 : g_mm_split != 0);
-            const bool split_runs = split && mm_has_split(K);
-            a.work_counter = g_prof.on ? g_prof.counter + (split_runs ? 1 : 0) : nullptr;
-            hipEvent_t e0 = g_prof.on ? prof_event() : nullptr, e1 = g_prof.on ? prof_event() : nullptr;
-            if (e0 && e1) TCLIP_HIP(hipEventRecord(e0, st));
-            a.rows = live_rows; a.n_rows = counts + 1;
-            g_last_mm_was_split = false;
-            // chunks 1.. of the first outer iteration under the default rule: k_mm_reuse where it exists and pays
-            const bool reuse = g_mm_split < 0 && g_mm_reuse != 0 && it == 0 && c > 0 && mm_has_split(K) && mm_reuse_pays(K);
-            launch_mm(split ? kMMSplit : (reuse ? kMMReuse : kMMLive), K, TK, st, a);
-            if (e0 && e1) {                                     // the instrumentation covers k_mm_live / k_mm_split only
-                TCLIP_HIP(hipEventRecord(e1, st));
-                if (g_prof.kind.size() < g_prof.used / 2) g_prof.kind.resize(g_prof.used / 2);
-                g_prof.kind[g_prof.used / 2 - 1] = g_last_mm_was_split ? 1 : 0;
-            }
-            if (split_runs != g_last_mm_was_split) return fail(TCLIP_ERR_ARG, "internal: mm_has_split disagrees with launch_mm");
-            if (zs && a.has_check) {          // dead rows only matter through their stop-test terms
-                a.rows = dead_list[c & 1]; a.n_rows = dead_counts + c; a.work_counter = nullptr;
-                if (c == 0 && g_dead_head > 0 && g_probe_chunks > 0) {
-                    // rows that have just died: g_dead_head iterations, then the early probe (k_mm_probe_head), which finishes
-                    // every row it finds on its cycle; what is left over takes the path below from the start
-                    MMArgs h = a;
-                    h.l0 = 0; h.l1 = g_dead_head - 1; h.has_check = 0; h.next_rows = nullptr; h.next_count = nullptr;
-                    launch_mm(kMMDead, K, TK, st, h);
-                    h.l0 = g_dead_head; h.next_rows = head_back; h.next_count = dead_counts + n_chunks + 2;
-                    launch_mm(kMMProbeHead, K, TK, st, h);
-                    a.rows = head_back; a.n_rows = dead_counts + n_chunks + 2;
-                }
-                // the probe needs the row to be ON its cycle already; rows that were still approaching
-                // it after chunk 0 get a few more chances before they are left to iterate every chunk
-                const bool more = c + 1 < a.n_checks, probe = c < g_probe_chunks && more;
-                int32_t* next_rows = more ? dead_list[(c + 1) & 1] : nullptr;
-                int32_t* next_count = more ? dead_counts + c + 1 : nullptr;
-                a.next_rows = probe ? nullptr : next_rows; a.next_count = probe ? nullptr : next_count;
-                launch_mm(kMMDead, K, TK, st, a);
-                a.next_rows = next_rows; a.next_count = next_count;
-                if (probe) launch_mm(kMMProbe, K, TK, st, a);
-            }
-            const bool two_stage = a.has_check && N * K > 16384;
-            if (two_stage)
-                hipLaunchKernelGGL(k_mm_decide_partial, dim3(kDecideSlices, B), dim3(256), 0, st, (const double*)rowpart,
-                                   (const double*)cache, (const uint8_t*)live, N * K, a.n_checks, c, (const int32_t*)stop, dpart);
-            hipLaunchKernelGGL(k_mm_decide, dim3(B), dim3(1024), 0, st, (const double*)rowpart, (const double*)cache,
-                               (const uint8_t*)live, N * K, a.n_checks, c, a.has_check, a.l1, c == n_chunks - 1 ? 1 : 0,
-                               p.iter_mm, stop, mm_iters + it, p.iters, (const double*)(two_stage ? dpart : nullptr),
-                               kDecideSlices);
+        if (int rc = em_mstep_stats(w, p, x, it, st)) return rc;
+        for (int c = 0; c < w.n_chunks; c++) {          // MM fixed point in chunks aligned with the stop-test checkpoints
+            const MMArgs a = mm_chunk_args(w, p, x.alpha, pl, c);
+            if (int rc = mm_live_rows(a, mm_live_kind(it, c, pl, knobs), pl, TK, st)) return rc;
+            if (p.n_support == 0 && a.has_check) mm_dead_rows(w, a, pl, knobs, TK, c, st);
+            mm_stop_test(w, p, a, c, x.mm_iters + it, st);
         }
-        // ---- E-step for the rows whose alpha changed, softmax over all classes
-        {
-            const int g8 = (TK + 7) / 8 > 65535 * 8 ? 65535 * 8 : (TK + 7) / 8;
-            dispatch_E<LaunchRowConsts>(K, g8 > 4096 ? 4096 : g8, st, (const float*)alpha, (const int32_t*)live_rows,
-                                        (const int32_t*)(counts + 1), K, rowc);
-            dispatch_E<LaunchLogits>(K, TK > kLogitsGrid ? kLogitsGrid : TK, st, (const float*)alpha, (const float*)logz, (const float*)rowc,
-                                     (const int32_t*)live_rows, (const int32_t*)(counts + 1), Q, K, logit0, (const int32_t*)nullptr);
-        }
-        hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)logit0, (const float*)v,
-                           T * Q, Q, K, (float)p.lambd, p.hard, 0, u, preds, done, N * Q);
-        // ---- convergence record
-        hipLaunchKernelGGL(k_criterion, dim3(T), dim3(64), 0, st, (const float*)alpha, alpha_old, K, T, ratio, done, N);
-        hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)ratio, N, (!zs && p.hard) ? 1 : 0,
-                           criterions + it, p.iters, done);
-        // ---- the batch's predictions against the previous iteration's; last, so that this iteration's record is complete
-        if (stable)
-            hipLaunchKernelGGL(k_assign_changes, dim3(B), dim3(256), 0, st, (const int32_t*)preds, stable->prev_preds, N * Q, it,
-                               it == p.iters - 1 ? 1 : 0, stable->patience, stable->changes, p.iters, stable->quiet,
-                               stable->done, stable->outer_iters);
+        em_estep(w, p, x, it, stable, st);
     }
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
@@ -4179,20 +4206,30 @@ static int n_groups_of(const tclip_problem& p) {
     return g < 1 ? 1 : (int)g;
 }
 
-static tclip_problem group_problem(const tclip_problem& p, int g, int* first_batch) {
-    tclip_problem q = p;
+// The call's batches dealt to its stream groups, in batch order: each group's first batch, its sub-problem and the offset of
+// its slice of the call's workspace (workspace_view of the sub-problem; `stable`: with the until-stable state).
+struct Groups {
+    int n;
+    size_t bytes;           // the whole call's workspace
+    struct Group { int first_batch; tclip_problem p; size_t ws_off; } g[kMaxGroups];
+};
+static Groups split_groups(const tclip_problem& p, bool stable) {
     const GroupSizes& o = group_sizes_override();
-    if (o.n > 0 && o.total == p.n_batches) {
-        int b0 = 0;
-        for (int i = 0; i < g; i++) b0 += o.size[i];
-        q.n_batches = o.size[g];
-        *first_batch = b0;
-        return q;
+    const bool sized = o.n > 0 && o.total == p.n_batches;
+    Groups r;
+    r.n = n_groups_of(p);
+    r.bytes = 0;
+    int b0 = 0;
+    for (int g = 0; g < r.n; g++) {
+        Groups::Group& e = r.g[g];
+        e.first_batch = b0;
+        e.p = p;
+        e.p.n_batches = sized ? o.size[g] : p.n_batches / r.n + (g < p.n_batches % r.n ? 1 : 0);
+        e.ws_off = r.bytes;
+        b0 += e.p.n_batches;
+        r.bytes += workspace_view(e.p, stable, nullptr).bytes;
     }
-    const int G = n_groups_of(p), base = p.n_batches / G, extra = p.n_batches % G;
-    q.n_batches = base + (g < extra ? 1 : 0);
-    *first_batch = g * base + (g < extra ? g : extra);
-    return q;
+    return r;
 }
 
 }  // namespace tclip
@@ -4200,24 +4237,11 @@ static tclip_problem group_problem(const tclip_problem& p, int g, int* first_bat
 extern "C" {
 
 size_t tclip_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    size_t total = 0;
-    for (int g = 0; g < n_groups_of(*p); g++) {
-        int b0;
-        total += make_layout(group_problem(*p, g, &b0)).total;
-    }
-    return total;
+    return check_problem(p) == TCLIP_OK ? split_groups(*p, false).bytes : 0;
 }
 
 size_t tclip_em_dirichlet_until_stable_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    size_t total = 0;
-    for (int g = 0; g < n_groups_of(*p); g++) {
-        int b0;
-        const tclip_problem q = group_problem(*p, g, &b0);
-        total += make_layout(q).total + stable_state_bytes(q);
-    }
-    return total;
+    return check_problem(p) == TCLIP_OK ? split_groups(*p, true).bytes : 0;
 }
 
 }  // extern "C"
@@ -4226,37 +4250,26 @@ namespace tclip {
 
 // Splits the call's batches into stream groups and enqueues each group (see StreamPool).
 // `stable` (optional, the until-stable entries): patience and the outputs outer_iters [n_batches], changes [n_batches, iters] of
-// the whole call; each group's state follows the group's plain layout in its workspace slice.
-static int run_em_dirichlet(const tclip_problem& p, const RowSrc& q_src, const RowSrc& s_src, const int64_t* y_s, float* u,
-                            float* v, float* alpha, int32_t* preds, float* criterions, int32_t* mm_iters,
-                            void* workspace, size_t workspace_bytes, void* stream, const StableStop* stable = nullptr) {
-    const bool zs = p.n_support == 0;
-    if (stable) {
-        if (workspace_bytes < tclip_em_dirichlet_until_stable_workspace_bytes(&p))
-            return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_em_dirichlet_until_stable_workspace_bytes()");
-    } else if (workspace_bytes < tclip_workspace_bytes(&p)) {
-        return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than tclip_workspace_bytes()");
-    }
-    if (((uintptr_t)workspace & 255) != 0) return fail(TCLIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+// the whole call.
+static int run_em_dirichlet(const tclip_problem& p, const EmTensors& x, void* workspace, size_t workspace_bytes, void* stream,
+                            const StableStop* stable = nullptr) {
+    const Groups groups = split_groups(p, stable != nullptr);
+    if (int rc = check_workspace(workspace, workspace_bytes, groups.bytes,
+                                 stable ? "tclip_em_dirichlet_until_stable_workspace_bytes" : "tclip_workspace_bytes"))
+        return rc;
     hipStream_t caller = (hipStream_t)stream;
     if (stable && p.iters > 0) {   // what a stopped batch never writes reads 0; ordered before every group's work (the fork event follows)
-        TCLIP_HIP(hipMemsetAsync(criterions, 0, (size_t)p.n_batches * p.iters * 4, caller));
-        TCLIP_HIP(hipMemsetAsync(mm_iters, 0, (size_t)p.n_batches * p.iters * 4, caller));
+        TCLIP_HIP(hipMemsetAsync(x.criterions, 0, (size_t)p.n_batches * p.iters * 4, caller));
+        TCLIP_HIP(hipMemsetAsync(x.mm_iters, 0, (size_t)p.n_batches * p.iters * 4, caller));
         TCLIP_HIP(hipMemsetAsync(stable->changes, 0, (size_t)p.n_batches * p.iters * 4, caller));
         TCLIP_HIP(hipMemsetAsync(stable->outer_iters, 0, (size_t)p.n_batches * 4, caller));
     }
-    const int G = n_groups_of(p);
+    const int G = groups.n;
     if (G > 1) {
         if (int rc = pool_init(G)) return rc;
         TCLIP_HIP(hipEventRecord(g_pool.fork, caller));
     }
     const size_t N = p.tasks_per_batch, Q = p.n_query, K = p.n_class, S = p.n_support;
-    size_t ws_off[kMaxGroups + 1] = {0};
-    for (int g = 0; g < G; g++) {
-        int b0;
-        const tclip_problem q = group_problem(p, g, &b0);
-        ws_off[g + 1] = ws_off[g] + make_layout(q).total + (stable ? stable_state_bytes(q) : 0);
-    }
     // the rows of the tasks from t0 on: a dense tensor moves its base, an indexed source its index (and column) rows
     auto from_task = [&](const RowSrc& src, size_t t0, size_t rows_per_task) {
         if (!src.base) return src;
@@ -4265,27 +4278,16 @@ static int run_em_dirichlet(const tclip_problem& p, const RowSrc& q_src, const R
     };
     for (int i = 0; i < G; i++) {
         const int g = (i + 1) % G;                       // pool streams first, the caller's stream last
-        int b0;
-        const tclip_problem q = group_problem(p, g, &b0);
-        const size_t t0 = (size_t)b0 * N;
+        const Groups::Group& grp = groups.g[g];
+        const size_t b0 = grp.first_batch, t0 = b0 * N;
         hipStream_t st = g == 0 ? caller : g_pool.s[g];
         if (g != 0) TCLIP_HIP(hipStreamWaitEvent(st, g_pool.fork, 0));
-        tclip_problem qs = q;
-        qs.iters = p.iters;
-        StableStop group;
-        if (stable) {
-            char* state = (char*)workspace + ws_off[g] + make_layout(q).total;
-            group.patience = stable->patience;
-            group.outer_iters = stable->outer_iters + b0;
-            group.changes = stable->changes + (size_t)b0 * p.iters;
-            group.prev_preds = (int32_t*)state;
-            group.quiet = (int32_t*)(state + align_up((size_t)q.n_batches * N * Q * 4));
-            group.done = (int32_t*)(state + align_up((size_t)q.n_batches * N * Q * 4) + align_up((size_t)q.n_batches * 4));
-        }
-        if (int rc = enqueue_batches(qs, from_task(q_src, t0, Q), from_task(s_src, t0, S), zs ? nullptr : y_s + t0 * S,
-                                     u + t0 * Q * K, v + t0 * K, alpha + t0 * K * K, preds + t0 * Q,
-                                     criterions + (size_t)b0 * p.iters, mm_iters + (size_t)b0 * p.iters,
-                                     (char*)workspace + ws_off[g], st, stable ? &group : nullptr)) {
+        const EmTensors xg{from_task(x.q, t0, Q), from_task(x.s, t0, S), S == 0 ? nullptr : x.y_s + t0 * S, x.u + t0 * Q * K,
+                           x.v + t0 * K, x.alpha + t0 * K * K, x.preds + t0 * Q, x.criterions + b0 * p.iters,
+                           x.mm_iters + b0 * p.iters};
+        StableStop sg{};
+        if (stable) sg = StableStop{stable->patience, stable->outer_iters + b0, stable->changes + b0 * p.iters};
+        if (int rc = enqueue_batches(grp.p, xg, (char*)workspace + grp.ws_off, st, stable ? &sg : nullptr)) {
             // kernels already enqueued on the internal streams still use the caller's buffers: let them finish
             // before the error reaches a caller who may free them (the caller's own stream is ordered anyway)
             for (int h = 1; h < G; h++) (void)hipStreamSynchronize(g_pool.s[h]);
@@ -4297,6 +4299,42 @@ static int run_em_dirichlet(const tclip_problem& p, const RowSrc& q_src, const R
     return TCLIP_OK;
 }
 
+// The argument checks of the entries, up to the workspace's (run_em_dirichlet): the problem, the until-stable entries'
+// additions, then the pointers of the dense-row or of the table-row entries.
+static int check_stable(const tclip_problem* pp, const StableStop* stable) {
+    if (int rc = check_problem(pp)) return rc;
+    if (!stable) return TCLIP_OK;
+    if (stable->patience < 1) return fail(TCLIP_ERR_ARG, "patience must be >= 1");
+    if (!stable->outer_iters) return fail(TCLIP_ERR_ARG, "outer_iters is null");
+    if (!stable->changes) return fail(TCLIP_ERR_ARG, "changes is null");
+    return TCLIP_OK;
+}
+static bool outputs_given(const EmTensors& x, const void* workspace) {
+    return x.u && x.v && x.alpha && x.preds && x.criterions && x.mm_iters && workspace;
+}
+static int check_dense(const tclip_problem* pp, const float* x_q, const float* x_s, EmTensors& x, const void* workspace,
+                       const StableStop* stable) {
+    if (int rc = check_stable(pp, stable)) return rc;
+    const bool zs = pp->n_support == 0;
+    if (!x_q || !outputs_given(x, workspace)) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (zs != (x_s == nullptr) || zs != (x.y_s == nullptr))
+        return fail(TCLIP_ERR_ARG, "x_s and y_s must be given exactly when n_support > 0");
+    x.q = dense_rows(x_q);
+    x.s = dense_rows(x_s);
+    return TCLIP_OK;
+}
+static int check_table(const tclip_problem* pp, const tclip_task_source* src, EmTensors& x, const void* workspace,
+                       const StableStop* stable) {
+    if (int rc = check_stable(pp, stable)) return rc;
+    const bool zs = pp->n_support == 0;
+    if (!src || !src->table_q || !src->q_idx || !outputs_given(x, workspace)) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (zs != (src->table_s == nullptr) || zs != (src->s_idx == nullptr) || zs != (x.y_s == nullptr))
+        return fail(TCLIP_ERR_ARG, "table_s, s_idx and y_s must be given exactly when n_support > 0");
+    x.q = RowSrc{src->table_q, src->q_idx, src->cols};
+    x.s = RowSrc{src->table_s, src->s_idx, src->cols};
+    return TCLIP_OK;
+}
+
 }  // namespace tclip
 
 extern "C" {
@@ -4304,67 +4342,37 @@ extern "C" {
 int tclip_em_dirichlet_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float* u,
                            float* v, float* alpha, int32_t* preds, float* criterions, int32_t* mm_iters,
                            void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const bool zs = pp->n_support == 0;
-    if (!x_q || !u || !v || !alpha || !preds || !criterions || !mm_iters || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (zs != (x_s == nullptr) || zs != (y_s == nullptr))
-        return fail(TCLIP_ERR_ARG, "x_s and y_s must be given exactly when n_support > 0");
-    return run_em_dirichlet(*pp, dense_rows(x_q), dense_rows(x_s), y_s, u, v, alpha, preds, criterions, mm_iters, workspace,
-                            workspace_bytes, stream);
+    EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
+    if (int rc = check_dense(pp, x_q, x_s, x, workspace, nullptr)) return rc;
+    return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream);
 }
 
 int tclip_em_dirichlet_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, float* u,
                                  float* v, float* alpha, int32_t* preds, float* criterions, int32_t* mm_iters,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const bool zs = pp->n_support == 0;
-    if (!src || !src->table_q || !src->q_idx || !u || !v || !alpha || !preds || !criterions || !mm_iters || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (zs != (src->table_s == nullptr) || zs != (src->s_idx == nullptr) || zs != (y_s == nullptr))
-        return fail(TCLIP_ERR_ARG, "table_s, s_idx and y_s must be given exactly when n_support > 0");
-    return run_em_dirichlet(*pp, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s,
-                            u, v, alpha, preds, criterions, mm_iters, workspace, workspace_bytes, stream);
-}
-
-// The checks the two until-stable entries add to those of the plain ones
-static int check_stable(int32_t patience, const int32_t* outer_iters, const int32_t* changes) {
-    if (patience < 1) return fail(TCLIP_ERR_ARG, "patience must be >= 1");
-    if (!outer_iters) return fail(TCLIP_ERR_ARG, "outer_iters is null");
-    if (!changes) return fail(TCLIP_ERR_ARG, "changes is null");
-    return TCLIP_OK;
+    EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
+    if (int rc = check_table(pp, src, x, workspace, nullptr)) return rc;
+    return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream);
 }
 
 int tclip_em_dirichlet_run_until_stable(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s,
                                         int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
                                         int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const bool zs = pp->n_support == 0;
-    if (int rc = check_stable(patience, outer_iters, changes)) return rc;
-    if (!x_q || !u || !v || !alpha || !preds || !criterions || !mm_iters || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (zs != (x_s == nullptr) || zs != (y_s == nullptr))
-        return fail(TCLIP_ERR_ARG, "x_s and y_s must be given exactly when n_support > 0");
-    const StableStop stable{patience, outer_iters, changes, nullptr, nullptr, nullptr};
-    return run_em_dirichlet(*pp, dense_rows(x_q), dense_rows(x_s), y_s, u, v, alpha, preds, criterions, mm_iters, workspace,
-                            workspace_bytes, stream, &stable);
+    const StableStop stable{patience, outer_iters, changes};
+    EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
+    if (int rc = check_dense(pp, x_q, x_s, x, workspace, &stable)) return rc;
+    return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream, &stable);
 }
 
 int tclip_em_dirichlet_run_tasks_until_stable(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s,
                                               int32_t patience, float* u, float* v, float* alpha, int32_t* preds,
                                               float* criterions, int32_t* mm_iters, int32_t* outer_iters, int32_t* changes,
                                               void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const bool zs = pp->n_support == 0;
-    if (int rc = check_stable(patience, outer_iters, changes)) return rc;
-    if (!src || !src->table_q || !src->q_idx || !u || !v || !alpha || !preds || !criterions || !mm_iters || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (zs != (src->table_s == nullptr) || zs != (src->s_idx == nullptr) || zs != (y_s == nullptr))
-        return fail(TCLIP_ERR_ARG, "table_s, s_idx and y_s must be given exactly when n_support > 0");
-    const StableStop stable{patience, outer_iters, changes, nullptr, nullptr, nullptr};
-    return run_em_dirichlet(*pp, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s,
-                            u, v, alpha, preds, criterions, mm_iters, workspace, workspace_bytes, stream, &stable);
+    const StableStop stable{patience, outer_iters, changes};
+    EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
+    if (int rc = check_table(pp, src, x, workspace, &stable)) return rc;
+    return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream, &stable);
 }
 
 int tclip_argmax_rows(const float* x, int64_t n_rows, int32_t n_class, int32_t* labels, void* stream) {
@@ -4389,44 +4397,44 @@ int tclip_probability_features(const float* visual, const float* text, int64_t n
 }
 
 int tclip_debug_set_rowset_min_rows(int32_t rows) {
-    g_rowset_min_rows = rows;
+    g_knobs.rowset_min_rows = rows;
     return TCLIP_OK;
 }
 
 int tclip_debug_set_kmeans_tile(int32_t mode) {
-    g_kmeans_tile = mode;
+    g_knobs.kmeans_tile = mode;
     return TCLIP_OK;
 }
 
 int tclip_debug_set_fixed_k_kernels(int32_t on) {
-    g_fixed_k_kernels = on;
+    g_knobs.fixed_k_kernels = on;
     return TCLIP_OK;
 }
 
 int tclip_debug_set_mm_split(int32_t mode) {
-    g_mm_split = mode;
+    g_knobs.mm_split = mode;
     return TCLIP_OK;
 }
 
 int tclip_debug_set_mm_reuse(int32_t mode) {
     if (mode < 0 || mode > 2) return fail(TCLIP_ERR_ARG, "tclip_debug_set_mm_reuse: mode must be 0, 1 or 2");
-    g_mm_reuse = mode;
+    g_knobs.mm_reuse = mode;
     return TCLIP_OK;
 }
 
 int tclip_debug_set_split_keep_placement(int32_t on) {
-    g_split_keep_placement = on != 0;
+    g_knobs.split_keep_placement = on != 0;
     return TCLIP_OK;
 }
 
 int tclip_debug_set_dead_head(int32_t iterations) {
     // the early probe needs its last snapshot (32 iterations in) to lie at or before the first checkpoint (iteration 50)
     if (iterations > 18) return fail(TCLIP_ERR_ARG, "tclip_debug_set_dead_head: at most 18 iterations");
-    g_dead_head = iterations < 0 ? kDeadHead : iterations;
+    g_knobs.dead_head = iterations < 0 ? kDeadHead : iterations;
     return TCLIP_OK;
 }
 int tclip_debug_set_probe_chunks(int32_t chunks) {
-    g_probe_chunks = chunks < 0 ? kProbeChunks : chunks;
+    g_knobs.probe_chunks = chunks < 0 ? kProbeChunks : chunks;
     return TCLIP_OK;
 }
 

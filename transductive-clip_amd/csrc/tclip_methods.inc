@@ -490,7 +490,7 @@ int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, flo
     for (int it = 0; it < p.iters; it++) {
         hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
                            live, (float*)nullptr, (int32_t*)nullptr);
-        if (Q == kColsQ && K >= kColsChunk && g_kmeans_tile != 0) {
+        if (Q == kColsQ && K >= kColsChunk && g_knobs.kmeans_tile != 0) {
             const int dtiles = (K + 63) / 64;
             int splits = (int)((8192 + (long)T * dtiles - 1) / ((long)T * dtiles));
             if (splits > K / (kColsWaves * kColsChunk)) splits = K / (kColsWaves * kColsChunk);
@@ -503,7 +503,7 @@ int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, flo
             hipLaunchKernelGGL(k_kl_centroids, dim3((K + 63) / 64, (K + kMstatsRows - 1) / kMstatsRows, T), dim3(64), 0, st,
                                (const float*)u, x_q, (const float*)cs, Q, K, w);
         }
-        if (g_kmeans_tile != 0 && K >= 32 && K <= 511 && kmeans_tile_lds_raised((const void*)k_kl_divergences_tile)) {
+        if (g_knobs.kmeans_tile != 0 && K >= 32 && K <= 511 && kmeans_tile_lds_raised((const void*)k_kl_divergences_tile)) {
             const int stride = K | 1;
             hipLaunchKernelGGL(k_kl_divergences_tile, dim3((K + kKmeansTile - 1) / kKmeansTile, T), dim3(kKmeansTileThreads),
                                (size_t)kKmeansTile * stride * sizeof(float), st, (const float*)w, x_q, Q, K, stride, divs);
