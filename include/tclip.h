@@ -148,6 +148,36 @@ int tclip_em_dirichlet_run_tasks_until_stable(const tclip_problem* p, const tcli
                                               float* criterions, int32_t* mm_iters, int32_t* outer_iters, int32_t* changes,
                                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same loops, observed (opt-in): the penalised clustering objective they descend - the reference's objective_function
+ * (src/methods/zero_shot/hard_em_dirichlet.py:179-198, few_shot/hard_em_dirichlet.py:149-168), which it defines and never calls -
+ * as four float64 terms per task and outer iteration.  After outer iteration `it` of task t, on the state that iteration
+ * leaves (alpha after the dead-row revert, u after the E-step - one-hot if hard -, eps = 1e-15):
+ *     objective_terms[t, it, 0] = fit_q = sum_n sum_k u[n,k] * logit[n,k]      logit: the E-step's fp32 get_logits(query),
+ *                                                                              before lambd * v / Q is added
+ *     objective_terms[t, it, 1] = fit_s = sum_s get_logits(support)[s, y_s], from the per-class support sums  (0 in zero-shot)
+ *     objective_terms[t, it, 2] = ent   = sum_n sum_k u * log(u + eps)
+ *     objective_terms[t, it, 3] = part  = sum_k p_k * log(p_k + eps),  p_k = (sum_n u[n,k]) / n_query
+ * and the reference's value is  -(fit_q + fit_s) / 2 + ent - lambd * part;  composing it is the caller's.  The operands are
+ * the engine's fp32 values, every product and sum is float64, and the order of each sum is fixed by (n_query, n_class) alone:
+ * the terms of a task have the same bits whatever shares the call and however it is split over stream groups, and the first s
+ * iterations of a run do not depend on iters.
+ *   patience        0: the plain schedule (outer_iters and changes are not written and may be NULL);
+ *                   >= 1: the until-stable schedule above; a batch has zeros from its outer_iters[b] on
+ *   objective_terms device [B * N, iters, 4] f64 out, zero-filled by the entry
+ * Every other output is bit for bit that of the plain entry (patience 0) or of the until-stable entry (patience >= 1).
+ * Checks are those entries'; patience < 0 or a null objective_terms are TCLIP_ERR_ARG before any launch (the error text names
+ * the argument).  Workspace: tclip_em_dirichlet_objective_workspace_bytes(p, patience) bytes (0 on bad input), 256-byte
+ * aligned: the plain or the until-stable workspace plus two doubles per (task, query) row; it does not depend on n_support. */
+size_t tclip_em_dirichlet_objective_workspace_bytes(const tclip_problem* p, int32_t patience);
+int tclip_em_dirichlet_run_objective(const tclip_problem* p, const float* x_q, const float* x_s, const int64_t* y_s,
+                                     int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
+                                     int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, double* objective_terms,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int tclip_em_dirichlet_run_tasks_objective(const tclip_problem* p, const tclip_task_source* src, const int64_t* y_s,
+                                           int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
+                                           int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, double* objective_terms,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Range check of DEVICE-resident index tensors before tclip_em_dirichlet_run_tasks / tclip_gather_rows - what torch's own
  * `all_features_query[indices, :]` (src/eval_zero_shot.py:160-163, src/eval_few_shot.py:233-241) does by raising IndexError:
  *   idx  device [n_idx]  i64, every value must lie in [0, n_rows)         (NULL with n_idx == 0: nothing to check)

@@ -21,6 +21,8 @@
 //   k_logits          (alpha-1) . log z contraction for rows that changed          (:37-38)
 //   k_softmax         u = softmax_k(logit + lambd*v/Q), argmax, one-hot if hard    (:142-143)
 //   k_criterion(+_mean) per-task relative change of alpha; alpha_old <- alpha      (:236-239)
+//   k_objective_rows, k_objective_task   the objective entries only (tclip_objective.inc): the four float64 terms of the
+//                     penalised objective per task, from logit0, u and (few-shot) alpha, sup, cnt, rowc
 //   k_assign_changes  the until-stable entries only: predictions changed since the last iteration, per batch; a batch whose
 //                     predictions stand still is marked done and skipped by every kernel above from then on
 //
@@ -2464,6 +2466,8 @@ __global__ __launch_bounds__(256) void k_assign_changes(const int32_t* __restric
     }
 }
 
+#include "tclip_objective.inc"
+
 // PADDLE prototype initialisation (few_shot/paddle.py:127-140): class means of the support set.
 __global__ void k_div_rows(const float* __restrict__ num, const float* __restrict__ den, size_t n, int K, float* __restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -3254,10 +3258,12 @@ struct Workspace {
     int32_t* prev_preds;            // [T, Q] the predictions after the previous outer iteration, -1 before the first
     int32_t* quiet;                 // [B] change-free outer iterations in a row
     int32_t* done;                  // [B] the batch is stable: nothing of it is written any more
+    // the objective entries' slot, last (`objective`; null otherwise)
+    double* objrows;                // [T * Q][2] per (task, query) row: sum_k u * logit0, sum_k u * log(u + eps)
     int n_chunks, n_checks;         // MM chunks per outer iteration; checkpoints cached per dead row (few-shot: 0, nothing to cache)
     size_t bytes;
 };
-static Workspace workspace_view(const tclip_problem& p, bool stable, char* base) {
+static Workspace workspace_view(const tclip_problem& p, bool stable, bool objective, char* base) {
     Workspace w;
     const size_t B = p.n_batches, T = B * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
     const bool zs = p.n_support == 0;
@@ -3298,6 +3304,7 @@ static Workspace workspace_view(const tclip_problem& p, bool stable, char* base)
     take(w.prev_preds, T * Q * 4, stable);
     take(w.quiet, B * 4, stable);
     take(w.done, B * 4, stable);
+    take(w.objrows, T * Q * 2 * sizeof(double), objective);
     w.bytes = o;
     return w;
 }
@@ -3955,6 +3962,12 @@ struct StableStop {
     int32_t* changes;       // [B, iters]
 };
 
+// The objective entries' part (tclip_em_dirichlet_run_objective): after every E-step the four float64 terms of the penalised
+// objective per task (k_objective_rows, k_objective_task).  Null for the other entries: no launch, no workspace byte.
+struct Objective {
+    double* terms;          // [B * N, iters, 4]
+};
+
 // The driver's stages, in the order enqueue_batches runs them on stream `st` for the p.n_batches batches of one group.
 // ---- initialisation (em_dirichlet.py:195-211)
 static int em_init(const Workspace& w, const tclip_problem& p, const EmTensors& x, hipStream_t st) {
@@ -4085,7 +4098,8 @@ static void mm_stop_test(const Workspace& w, const tclip_problem& p, const MMArg
 }
 
 // ---- E-step for the rows whose alpha changed, softmax over all classes, convergence record of outer iteration `it`
-static void em_estep(const Workspace& w, const tclip_problem& p, const EmTensors& x, int it, const StableStop* stable, hipStream_t st) {
+static void em_estep(const Workspace& w, const tclip_problem& p, const EmTensors& x, int it, const StableStop* stable,
+                     const Objective* objective, hipStream_t st) {
     const int B = p.n_batches, N = p.tasks_per_batch, Q = p.n_query, K = p.n_class, T = B * N, TK = T * K;
     const int32_t* done = w.done;
     const int g8 = (TK + 7) / 8 > 65535 * 8 ? 65535 * 8 : (TK + 7) / 8;
@@ -4095,6 +4109,14 @@ static void em_estep(const Workspace& w, const tclip_problem& p, const EmTensors
                              (const int32_t*)w.live_rows, (const int32_t*)(w.counts + 1), Q, K, w.logit0, (const int32_t*)nullptr);
     hipLaunchKernelGGL(k_softmax, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)w.logit0, (const float*)x.v,
                        T * Q, Q, K, (float)p.lambd, p.hard, 0, x.u, x.preds, done, N * Q);
+    if (objective) {    // on the state this iteration leaves: logit0 still holds get_logits(query), u the new assignments
+        const bool few = p.n_support > 0;
+        hipLaunchKernelGGL(k_objective_rows, dim3((T * Q * 16 + 255) / 256), dim3(256), 0, st, (const float*)w.logit0,
+                           (const float*)x.u, T * Q, K, w.objrows, done, N * Q);
+        hipLaunchKernelGGL(k_objective_task, dim3(T), dim3(256), 0, st, (const double*)w.objrows, (const float*)x.u,
+                           (const float*)x.alpha, (const float*)(few ? w.sup : nullptr), (const float*)w.cnt, (const float*)w.rowc,
+                           Q, K, it, p.iters, objective->terms, done, N);
+    }
     hipLaunchKernelGGL(k_criterion, dim3(T), dim3(64), 0, st, (const float*)x.alpha, w.alpha_old, K, T, w.ratio, done, N);
     hipLaunchKernelGGL(k_criterion_mean, dim3(B), dim3(64), 0, st, (const float*)w.ratio, N, (p.n_support > 0 && p.hard) ? 1 : 0,
                        x.criterions + it, p.iters, done);
@@ -4105,9 +4127,10 @@ static void em_estep(const Workspace& w, const tclip_problem& p, const EmTensors
                            stable->outer_iters);
 }
 
-// Enqueues the whole loop for `p.n_batches` consecutive batches on stream `st`; `ws` holds workspace_view(p, stable, ..).bytes.
-static int enqueue_batches(const tclip_problem& p, const EmTensors& x, char* ws, hipStream_t st, const StableStop* stable) {
-    const Workspace w = workspace_view(p, stable != nullptr, ws);
+// Enqueues the whole loop for `p.n_batches` consecutive batches on stream `st`; `ws` holds workspace_view(p, stable, objective, ..).bytes.
+static int enqueue_batches(const tclip_problem& p, const EmTensors& x, char* ws, hipStream_t st, const StableStop* stable,
+                           const Objective* objective) {
+    const Workspace w = workspace_view(p, stable != nullptr, objective != nullptr, ws);
     const Knobs& knobs = g_knobs;
     const MMPlan pl = mm_plan(p.n_class, knobs);
     const int TK = p.n_batches * p.tasks_per_batch * p.n_class;
@@ -4120,7 +4143,7 @@ static int enqueue_batches(const tclip_problem& p, const EmTensors& x, char* ws,
             if (p.n_support == 0 && a.has_check) mm_dead_rows(w, a, pl, knobs, TK, c, st);
             mm_stop_test(w, p, a, c, x.mm_iters + it, st);
         }
-        em_estep(w, p, x, it, stable, st);
+        em_estep(w, p, x, it, stable, objective, st);
     }
     TCLIP_HIP(hipGetLastError());
     return TCLIP_OK;
@@ -4207,13 +4230,14 @@ static int n_groups_of(const tclip_problem& p) {
 }
 
 // The call's batches dealt to its stream groups, in batch order: each group's first batch, its sub-problem and the offset of
-// its slice of the call's workspace (workspace_view of the sub-problem; `stable`: with the until-stable state).
+// its slice of the call's workspace (workspace_view of the sub-problem; `stable`: with the until-stable state, `objective`: with
+// the objective entries' slot).
 struct Groups {
     int n;
     size_t bytes;           // the whole call's workspace
     struct Group { int first_batch; tclip_problem p; size_t ws_off; } g[kMaxGroups];
 };
-static Groups split_groups(const tclip_problem& p, bool stable) {
+static Groups split_groups(const tclip_problem& p, bool stable, bool objective = false) {
     const GroupSizes& o = group_sizes_override();
     const bool sized = o.n > 0 && o.total == p.n_batches;
     Groups r;
@@ -4227,7 +4251,7 @@ static Groups split_groups(const tclip_problem& p, bool stable) {
         e.p.n_batches = sized ? o.size[g] : p.n_batches / r.n + (g < p.n_batches % r.n ? 1 : 0);
         e.ws_off = r.bytes;
         b0 += e.p.n_batches;
-        r.bytes += workspace_view(e.p, stable, nullptr).bytes;
+        r.bytes += workspace_view(e.p, stable, objective, nullptr).bytes;
     }
     return r;
 }
@@ -4244,20 +4268,28 @@ size_t tclip_em_dirichlet_until_stable_workspace_bytes(const tclip_problem* p) {
     return check_problem(p) == TCLIP_OK ? split_groups(*p, true).bytes : 0;
 }
 
+size_t tclip_em_dirichlet_objective_workspace_bytes(const tclip_problem* p, int32_t patience) {
+    return check_problem(p) == TCLIP_OK && patience >= 0 ? split_groups(*p, patience >= 1, true).bytes : 0;
+}
+
 }  // extern "C"
 
 namespace tclip {
 
 // Splits the call's batches into stream groups and enqueues each group (see StreamPool).
 // `stable` (optional, the until-stable entries): patience and the outputs outer_iters [n_batches], changes [n_batches, iters] of
-// the whole call.
+// the whole call.  `objective` (optional, the objective entries): the output objective_terms [n_batches * tasks_per_batch, iters, 4].
 static int run_em_dirichlet(const tclip_problem& p, const EmTensors& x, void* workspace, size_t workspace_bytes, void* stream,
-                            const StableStop* stable = nullptr) {
-    const Groups groups = split_groups(p, stable != nullptr);
+                            const StableStop* stable = nullptr, const Objective* objective = nullptr) {
+    const Groups groups = split_groups(p, stable != nullptr, objective != nullptr);
     if (int rc = check_workspace(workspace, workspace_bytes, groups.bytes,
-                                 stable ? "tclip_em_dirichlet_until_stable_workspace_bytes" : "tclip_workspace_bytes"))
+                                 objective ? "tclip_em_dirichlet_objective_workspace_bytes"
+                                 : stable  ? "tclip_em_dirichlet_until_stable_workspace_bytes"
+                                           : "tclip_workspace_bytes"))
         return rc;
     hipStream_t caller = (hipStream_t)stream;
+    if (objective && p.iters > 0)   // a stopped batch's later iterations read 0; ordered before every group's work, as below
+        TCLIP_HIP(hipMemsetAsync(objective->terms, 0, (size_t)p.n_batches * p.tasks_per_batch * p.iters * 4 * sizeof(double), caller));
     if (stable && p.iters > 0) {   // what a stopped batch never writes reads 0; ordered before every group's work (the fork event follows)
         TCLIP_HIP(hipMemsetAsync(x.criterions, 0, (size_t)p.n_batches * p.iters * 4, caller));
         TCLIP_HIP(hipMemsetAsync(x.mm_iters, 0, (size_t)p.n_batches * p.iters * 4, caller));
@@ -4287,7 +4319,8 @@ static int run_em_dirichlet(const tclip_problem& p, const EmTensors& x, void* wo
                            x.mm_iters + b0 * p.iters};
         StableStop sg{};
         if (stable) sg = StableStop{stable->patience, stable->outer_iters + b0, stable->changes + b0 * p.iters};
-        if (int rc = enqueue_batches(grp.p, xg, (char*)workspace + grp.ws_off, st, stable ? &sg : nullptr)) {
+        const Objective og{objective ? objective->terms + t0 * p.iters * 4 : nullptr};
+        if (int rc = enqueue_batches(grp.p, xg, (char*)workspace + grp.ws_off, st, stable ? &sg : nullptr, objective ? &og : nullptr)) {
             // kernels already enqueued on the internal streams still use the caller's buffers: let them finish
             // before the error reaches a caller who may free them (the caller's own stream is ordered anyway)
             for (int h = 1; h < G; h++) (void)hipStreamSynchronize(g_pool.s[h]);
@@ -4301,8 +4334,9 @@ static int run_em_dirichlet(const tclip_problem& p, const EmTensors& x, void* wo
 
 // The argument checks of the entries, up to the workspace's (run_em_dirichlet): the problem, the until-stable entries'
 // additions, then the pointers of the dense-row or of the table-row entries.
-static int check_stable(const tclip_problem* pp, const StableStop* stable) {
+static int check_stable(const tclip_problem* pp, const StableStop* stable, const Objective* objective = nullptr) {
     if (int rc = check_problem(pp)) return rc;
+    if (objective && !objective->terms) return fail(TCLIP_ERR_ARG, "objective_terms is null");
     if (!stable) return TCLIP_OK;
     if (stable->patience < 1) return fail(TCLIP_ERR_ARG, "patience must be >= 1");
     if (!stable->outer_iters) return fail(TCLIP_ERR_ARG, "outer_iters is null");
@@ -4313,8 +4347,8 @@ static bool outputs_given(const EmTensors& x, const void* workspace) {
     return x.u && x.v && x.alpha && x.preds && x.criterions && x.mm_iters && workspace;
 }
 static int check_dense(const tclip_problem* pp, const float* x_q, const float* x_s, EmTensors& x, const void* workspace,
-                       const StableStop* stable) {
-    if (int rc = check_stable(pp, stable)) return rc;
+                       const StableStop* stable, const Objective* objective = nullptr) {
+    if (int rc = check_stable(pp, stable, objective)) return rc;
     const bool zs = pp->n_support == 0;
     if (!x_q || !outputs_given(x, workspace)) return fail(TCLIP_ERR_ARG, "null pointer argument");
     if (zs != (x_s == nullptr) || zs != (x.y_s == nullptr))
@@ -4324,8 +4358,8 @@ static int check_dense(const tclip_problem* pp, const float* x_q, const float* x
     return TCLIP_OK;
 }
 static int check_table(const tclip_problem* pp, const tclip_task_source* src, EmTensors& x, const void* workspace,
-                       const StableStop* stable) {
-    if (int rc = check_stable(pp, stable)) return rc;
+                       const StableStop* stable, const Objective* objective = nullptr) {
+    if (int rc = check_stable(pp, stable, objective)) return rc;
     const bool zs = pp->n_support == 0;
     if (!src || !src->table_q || !src->q_idx || !outputs_given(x, workspace)) return fail(TCLIP_ERR_ARG, "null pointer argument");
     if (zs != (src->table_s == nullptr) || zs != (src->s_idx == nullptr) || zs != (x.y_s == nullptr))
@@ -4373,6 +4407,33 @@ int tclip_em_dirichlet_run_tasks_until_stable(const tclip_problem* pp, const tcl
     EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
     if (int rc = check_table(pp, src, x, workspace, &stable)) return rc;
     return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream, &stable);
+}
+
+// patience 0: the plain schedule (outer_iters and changes are not touched and may be null); patience >= 1: until stable
+int tclip_em_dirichlet_run_objective(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s,
+                                     int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
+                                     int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, double* objective_terms,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (patience < 0) return fail(TCLIP_ERR_ARG, "patience must be >= 0");
+    const StableStop stable{patience, outer_iters, changes};
+    const StableStop* sp = patience >= 1 ? &stable : nullptr;
+    const Objective objective{objective_terms};
+    EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
+    if (int rc = check_dense(pp, x_q, x_s, x, workspace, sp, &objective)) return rc;
+    return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream, sp, &objective);
+}
+
+int tclip_em_dirichlet_run_tasks_objective(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s,
+                                           int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
+                                           int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, double* objective_terms,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (patience < 0) return fail(TCLIP_ERR_ARG, "patience must be >= 0");
+    const StableStop stable{patience, outer_iters, changes};
+    const StableStop* sp = patience >= 1 ? &stable : nullptr;
+    const Objective objective{objective_terms};
+    EmTensors x{{}, {}, y_s, u, v, alpha, preds, criterions, mm_iters};
+    if (int rc = check_table(pp, src, x, workspace, sp, &objective)) return rc;
+    return run_em_dirichlet(*pp, x, workspace, workspace_bytes, stream, sp, &objective);
 }
 
 int tclip_argmax_rows(const float* x, int64_t n_rows, int32_t n_class, int32_t* labels, void* stream) {

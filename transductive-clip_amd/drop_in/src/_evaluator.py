@@ -54,6 +54,19 @@ def check_stop_patience(args):
     return patience
 
 
+def check_record_objective(args):
+    """args.record_objective (not a default: absent unless given) belongs to the EM-Dirichlet classes too: ValueError for any
+    other method, before anything touches the device.  Returns whether the objective is to be recorded."""
+    try:
+        on = bool(getattr(args, 'record_objective', None))
+    except KeyError:
+        on = False
+    if on and getattr(args, 'name_method', None) not in _STOP_PATIENCE_METHODS:
+        raise ValueError("record_objective records the penalised objective EM_DIRICHLET / HARD_EM_DIRICHLET descend: "
+                         f"method {getattr(args, 'name_method', None)!r} has no such record")
+    return on
+
+
 class EvaluatorBase:
     _METHODS = {}       # name_method -> class: the subclass's table
 
@@ -108,7 +121,7 @@ class EvaluatorBase:
         of every rank onto rank 0 (`parts`: this rank's, None when it had no batch; `timestamps`: one time per batch it ran).
         Sets last_method (`method`: the object that actually ran on this rank) and, on rank 0, last_task_accuracies,
         last_task_predictions, last_batch_criterions and last_batch_mm_iters (with args.stop_patience also
-        last_batch_outer_iters).  Returns (mean over the batches of their mean
+        last_batch_outer_iters, with args.record_objective also last_task_objectives).  Returns (mean over the batches of their mean
         accuracies, mean time), or (None, None) off rank 0."""
         if parts is None:      # more ranks than batches: this rank only takes part in the gather
             parts = sharding.method_parts(self.args, None, None, 0, N, Q, torch.device(self.device))
@@ -124,4 +137,6 @@ class EvaluatorBase:
         self.last_batch_mm_iters = got['mm_iters'].numpy() if 'mm_iters' in got else None
         if 'outer_iters' in got:       # args.stop_patience: the outer iterations every batch ran, (n_batches,)
             self.last_batch_outer_iters = got['outer_iters'].numpy().reshape(n_batches)
+        if 'objectives' in got:        # args.record_objective: the objective of every task after every outer iteration, float64
+            self.last_task_objectives = sharding.objectives_of(got['objectives']).numpy()      # (n_batches, N, iter)
         return np.asarray(results_task).mean(), (float(np.mean(timestamps)) if timestamps else 0.0)

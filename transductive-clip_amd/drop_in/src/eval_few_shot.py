@@ -7,7 +7,7 @@ import types
 import numpy as np
 import torch
 
-from src._evaluator import EvaluatorBase, _as_tensor, arg_hidden, arg_set_to, check_stop_patience
+from src._evaluator import EvaluatorBase, _as_tensor, arg_hidden, arg_set_to, check_record_objective, check_stop_patience
 from src.methods.few_shot.em_dirichlet import EM_DIRICHLET
 from src.methods.few_shot.hard_em_dirichlet import HARD_EM_DIRICHLET
 from src.methods.few_shot.paddle import PADDLE
@@ -209,7 +209,8 @@ class Evaluator_few_shot(EvaluatorBase):
         si, qi, _, _, rel = self._block(t)
         accs, times, methods = [], [], []
         for v in values:
-            with arg_set_to(a, attr, v), arg_hidden(a, 'stop_patience'):      # a sweep ignores the stop: no swept method has one
+            # a sweep ignores the stop and the objective record: no swept method has either
+            with arg_set_to(a, attr, v), arg_hidden(a, 'stop_patience'), arg_hidden(a, 'record_objective'):
                 if rel is None:
                     acc, time = self.evaluate_tasks(model, all_features_support, all_labels_support, all_features_query,
                                                     all_labels_query, indices=(t.s_idx, t.q_idx))
@@ -236,6 +237,7 @@ class Evaluator_few_shot(EvaluatorBase):
         """`indices`: a (support, query) index pair drawn earlier with sample_indices(); None draws it here."""
         a = self.args
         check_stop_patience(a)
+        check_record_objective(a)
         self.logger.info("=> Runnning evaluation with method {} on {} dataset".format(
             a.name_method, getattr(a, 'used_test_set', 'test')))
         t = self._tasks(all_features_support, all_labels_support, all_features_query, all_labels_query, indices)

@@ -9,7 +9,7 @@ Feature extraction and dataset handling of the reference's Evaluator are out of 
 weights and images): run_full_evaluation starts from the saved feature files the reference writes."""
 import torch
 
-from src._evaluator import EvaluatorBase, _as_tensor, check_stop_patience
+from src._evaluator import EvaluatorBase, _as_tensor, check_record_objective, check_stop_patience
 from src.methods.zero_shot.em_dirichlet import EM_DIRICHLET
 from src.methods.zero_shot.hard_em_dirichlet import HARD_EM_DIRICHLET
 from src.methods.zero_shot.em_gaussian import EM_GAUSSIAN
@@ -60,6 +60,7 @@ class Evaluator_zero_shot(EvaluatorBase):
         labels may already live on the device."""
         a = self.args
         check_stop_patience(a)
+        check_record_objective(a)
         self.logger.info("=> Runnning evaluation with method {} on {} dataset".format(
             a.name_method, getattr(a, 'used_test_set', 'test')))
         dev = torch.device(self.device)

@@ -159,6 +159,20 @@ class EMDirichletBase(MethodBase):
         except KeyError:
             return None
 
+    def _record_objective(self):
+        """args.record_objective (main_features.py --opts record_objective True): the penalised objective of every task after
+        every outer iteration (tclip_amd.objective).  Optional like stop_patience: off when absent."""
+        try:
+            return bool(getattr(self.args, "record_objective", None))
+        except KeyError:
+            return False
+
+    def get_logs(self):
+        logs = super().get_logs()
+        if self._record_objective():
+            logs['objectives'] = self.objectives
+        return logs
+
     # -- the loop ---------------------------------------------------------------------------
     def _run_engine(self, query, support=None, y_s=None, n_batches=1, tables=None):
         """`tables` = dict(table_q, q_idx[, table_s, s_idx, cols]): the task rows are read from the feature tables through the
@@ -169,9 +183,12 @@ class EMDirichletBase(MethodBase):
         kw = dict(n_batches=n_batches, iters=self.iter, iter_mm=self.iter_mm, lambd=self.lambd, hard=self.HARD)
         runner = engine
         patience = self._stop_patience()
+        record = self._record_objective()
         if patience is not None:
             from tclip_amd import until_stable as runner
             kw["patience"] = runner.check_patience(patience)
+        if record:                     # the same run, observed: with the patience when there is one
+            from tclip_amd import objective as runner
         if tables is not None:
             call = lambda: runner.run_em_dirichlet_tasks(tables["table_q"], tables["q_idx"], tables.get("table_s"),      # noqa: E731
                                                          tables.get("s_idx"), y_s, tables.get("cols"), **kw)
@@ -188,6 +205,9 @@ class EMDirichletBase(MethodBase):
         if patience is not None:       # the logs keep their shapes: a stopped batch's records are 0 from its outer_iters on
             self.outer_iters = res.outer_iters.cpu().numpy()                    # (n_batches,)
             self.assignment_changes = res.changes.cpu().numpy()                 # (n_batches, iter)
+        if record:                     # float64; with a patience a stopped batch's rows are 0 from its outer_iters on
+            self.objective_terms = res.objective_terms.cpu().numpy()            # (n_task, iter, 4)
+            self.objectives = runner.objective(self.objective_terms, self.lambd)        # (n_task, iter)
         return res
 
 

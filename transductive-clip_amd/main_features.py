@@ -44,6 +44,12 @@ the same seed writes.  Each element keeps the type it is written with (`5` and `
 it has changed for that many outer iterations in a row: the batch returns exactly what a run with `iter` set to the iterations
 it ran returns, and spends no further MM launches.  The logs keep their shapes (a stopped batch's criterions are 0 from its stop
 on); the evaluator keeps the iterations every batch ran in `last_batch_outer_iters`.  Any other method refuses the option.
+`record_objective True` (EM_DIRICHLET and HARD_EM_DIRICHLET; not a default: absent unless given) records the penalised
+clustering objective the loop descends - the reference's never-called `objective_function` - for every task after every outer
+iteration, evaluated on the device in float64 (tclip_amd.objective).  Predictions, accuracies and every other record are
+unchanged; the logs gain the key `objectives`, the evaluator keeps `last_task_objectives` (batches, tasks, iter), and the mean
+objective per iteration is printed.  It combines with `stop_patience` (a stopped batch's objectives are 0 from its stop on); any
+other method refuses the option, and a `sweep_values` run ignores it.
 Under `python -m torch.distributed.run --nproc-per-node N` batches are sharded over N GPUs.
 """
 import argparse
@@ -126,9 +132,10 @@ def main(argv=None, keep_process_group=False):
         if int(args.shots) < 1:
             raise ValueError("sweep_values tunes a few-shot method: shots must be positive")
         sweep = checked_sweep_values(args, sweep, distributed=True if dist_on else None)
-    from src._evaluator import check_stop_patience
-    if sweep is None:                          # refused here, before the device is touched; a sweep ignores the option
+    from src._evaluator import check_record_objective, check_stop_patience
+    if sweep is None:                          # refused here, before the device is touched; a sweep ignores the options
         check_stop_patience(args)
+        check_record_objective(args)
     local_rank = int(os.environ.get("LOCAL_RANK", args.device))
     if args.seed is not None:                  # main.py:42-46
         random.seed(args.seed)
@@ -179,6 +186,9 @@ def main(argv=None, keep_process_group=False):
     if acc is not None:                        # rank 0
         path = reporting.report_results(args, acc, t, logger, root=ns.results_root)
         print(f"mean accuracy {100 * float(acc):.2f} %  mean time/task statistic {t:.3e} s" + (f"  -> {path}" if path else ""))
+        objectives = getattr(ev, "last_task_objectives", None)
+        if objectives is not None:             # record_objective: the mean over every batch's tasks, per outer iteration
+            logger.info("mean objective per outer iteration: " + " ".join(f"{o:.6g}" for o in objectives.mean((0, 1))))
     if dist_on:
         import torch.distributed as dist
         dist.barrier()

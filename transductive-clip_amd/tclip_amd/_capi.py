@@ -35,6 +35,12 @@ _SIGNATURES = {
                                             + [ctypes.c_size_t, _P]),
     "tclip_em_dirichlet_run_tasks_until_stable": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_int32]
                                                   + [_P] * 9 + [ctypes.c_size_t, _P]),
+    # the until-stable entries' arguments with objective_terms after changes; patience 0 is the plain schedule
+    "tclip_em_dirichlet_objective_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Problem), ctypes.c_int32]),
+    "tclip_em_dirichlet_run_objective": (ctypes.c_int, [ctypes.POINTER(Problem)] + [_P] * 3 + [ctypes.c_int32] + [_P] * 10
+                                         + [ctypes.c_size_t, _P]),
+    "tclip_em_dirichlet_run_tasks_objective": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_int32]
+                                               + [_P] * 10 + [ctypes.c_size_t, _P]),
     "tclip_prototype_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
     "tclip_cluster_prototypes": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 6 + [ctypes.c_size_t, _P]),
     "tclip_match_clusters_host": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 5 + [ctypes.c_int32, _P, _P]),

@@ -48,11 +48,15 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
     (SURVEY.md section 8e): `preds` (N*Q) int32 - the class assigned to every query, after the cluster-to-class
     matching for the zero-shot clustering methods, `acc` (N) f32, and for the EM-Dirichlet classes / ALPHA_TIM the
     per-batch `criterions` (iter) f32 and `mm_iters` (iter) int32; for TIM-GD the per-task `criterions` (iter, N) f32.
-    With args.stop_patience set, the EM-Dirichlet classes add `outer_iters` (1) int32: the outer iterations the batch ran.
+    With args.stop_patience set, the EM-Dirichlet classes add `outer_iters` (1) int32: the outer iterations the batch ran;
+    with args.record_objective set, `objectives` (N, 2 * iter) int32: every task's float64 objective after every outer iteration,
+    each value as its two words (gather_packed moves 32-bit rows; `objectives_of` gives the float64 values back, bit for bit).
     method=None: a rank without a batch (zero rows of the same widths)."""
     records = _PER_BATCH_RECORDS.get(getattr(args, 'name_method', None), ())
     if 'mm_iters' in records and _option(args, 'stop_patience') is not None:
         records = records + ('outer_iters',)
+    if 'mm_iters' in records and _option(args, 'record_objective'):
+        records = records + ('objectives',)
     iters = int(getattr(args, 'iter', 0))
     per_task = getattr(args, 'name_method', None) in _PER_TASK_CRITERIONS
     if method is None:
@@ -63,6 +67,8 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
             parts['mm_iters'] = torch.zeros(0, iters, dtype=torch.int32)
         if 'outer_iters' in records:
             parts['outer_iters'] = torch.zeros(0, 1, dtype=torch.int32)
+        if 'objectives' in records:
+            parts['objectives'] = torch.zeros(0, N, 2 * iters, dtype=torch.int32)
         if per_task:
             parts['criterions'] = torch.zeros(0, iters, N)
     else:
@@ -77,10 +83,18 @@ def method_parts(args, method, logs, n_local, N, Q, dev):
             parts['mm_iters'] = torch.as_tensor(method.mm_iters, dtype=torch.int32).view(n_local, iters)
         if 'outer_iters' in records:
             parts['outer_iters'] = torch.as_tensor(method.outer_iters, dtype=torch.int32).view(n_local, 1)
+        if 'objectives' in records:
+            obj = torch.as_tensor(method.objectives, dtype=torch.float64).reshape(n_local, N, iters).contiguous()
+            parts['objectives'] = obj.view(torch.int32)                      # (n_local, N, 2 * iters)
         if per_task:        # (iter, n_local * N) -> one (iter, N) block per batch
             crit = torch.as_tensor(method.criterions_per_task, dtype=torch.float32)
             parts['criterions'] = crit.view(iters, n_local, N).permute(1, 0, 2).contiguous()
     return {k: v.to(dev) for k, v in parts.items()}
+
+
+def objectives_of(words):
+    """the float64 objectives (..., iter) behind the `objectives` part (..., 2 * iter) int32 of method_parts"""
+    return words.contiguous().view(torch.float64)
 
 
 def concat_parts(a, b):
