@@ -48,7 +48,8 @@ extern "C" {
  *    tclip_paddle_sweep_tasks_workspace_bytes, tclip_paddle_sweep_tasks, tclip_bdcspn_sweep_tasks_workspace_bytes,
  *    tclip_bdcspn_sweep_tasks, tclip_laplacian_shot_sweep_tasks_workspace_bytes, tclip_laplacian_shot_sweep_tasks,
  *    tclip_alpha_tim_sweep_tasks_workspace_bytes, tclip_alpha_tim_sweep_tasks;
- *    tclip_debug_set_mm_reuse, tclip_profile_last_mm_reuse
+ *    tclip_debug_set_mm_reuse, tclip_profile_last_mm_reuse;
+ *    tclip_em_dirichlet_score_workspace_bytes, tclip_em_dirichlet_score, tclip_em_dirichlet_score_tasks (tclip_score_problem)
  * (every entry point of an earlier version keeps its signature) */
 #define TCLIP_ABI_VERSION 5
 
@@ -177,6 +178,46 @@ int tclip_em_dirichlet_run_tasks_objective(const tclip_problem* p, const tclip_t
                                            int32_t patience, float* u, float* v, float* alpha, int32_t* preds, float* criterions,
                                            int32_t* mm_iters, int32_t* outer_iters, int32_t* changes, double* objective_terms,
                                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scoring with a fitted model: one E-step of a given (alpha, v) on rows that need not have been queries of the fit - "fit on
+ * a sample, label the rest of the table".  A run's alpha [T,K,K] and v [T,K] are a complete mixture model per task (one
+ * Dirichlet per class and the penalised class weights); per task t and scored row r, with z the row and eps = 1e-15,
+ *     logits[t,r,k] = lgamma(sum_d alpha[t,k,d]) + (-sum_d lgamma(alpha[t,k,d])) + sum_d (alpha[t,k,d] - 1) * log(z[d] + eps)
+ *                     the reference's get_logits (src/methods/zero_shot/em_dirichlet.py:35-39), in fp32
+ *     u[t,r,:]      = softmax_k(logits[t,r,k] + (lambd * v[t,k]) / (float)n_query)     (:142-143; v == NULL: softmax_k(logits))
+ *     preds[t,r]    = first maximum of u[t,r,:], a NaN counting as the maximum (torch.argmax); hard: u is the one-hot of preds
+ * with the operations and summation orders of the loop's own E-step.  The reference's loop ends with the dead-row revert, v_update
+ * and u_update(query), so scoring a run's x_q with its alpha, v, lambd and n_query returns that run's u and preds bit for bit.
+ * The bits of a scored row depend on (its features, alpha[t], v[t], lambd, n_query, n_class) and on nothing else: not on
+ * rows_per_task, n_task, the row's position, what shares the call, the dense or the table route, or which outputs were asked for.
+ * In zero-shot the classes are clusters; matching clusters to classes stays with the accuracy tail (tclip_match_clusters).
+ *   x      device [T,R,K] f32  rows on the simplex (dense entry)
+ *   table  device [rows,K] f32, idx device [T,R] i64 rows of it, cols device [T,K] i32 column permutation per task or NULL: row r
+ *          of task t is table[idx[t,r]], its column d is table column cols[t,d], read in place as tclip_em_dirichlet_run_tasks reads.
+ *          The entry does not know the table's row count: call tclip_check_task_indices first (the Python binding does).
+ *   alpha  device [T,K,K] f32, v device [T,K] f32 or NULL
+ *   u      device [T,R,K] f32 out, or NULL for labels only (200 MB at R = 50 000, K = 1000)
+ *   preds  device [T,R] i32 out;  logits device [T,R,K] f32 out or NULL
+ * No allocation, no synchronisation, no state; inputs are not modified.  A null problem, x / table, idx, alpha, preds or workspace,
+ * n_task < 1, rows_per_task < 1, n_query < 1, n_class outside 2..1024, n_task * n_class or n_task * rows_per_task beyond int32
+ * are TCLIP_ERR_ARG before any launch (the error text names the argument).  Workspace:
+ * tclip_em_dirichlet_score_workspace_bytes(p) bytes (0 on bad input), 256-byte aligned: the per-class row constants, T * K
+ * floats - O(T K), independent of rows_per_task; the scored rows are staged in LDS only. */
+typedef struct tclip_score_problem {
+    int32_t n_task;         /* T >= 1 fitted models                                            */
+    int32_t rows_per_task;  /* R >= 1 rows scored against each model                           */
+    int32_t n_class;        /* K, 2..1024                                                      */
+    int32_t lambd;          /* the fit's integer lambd                                         */
+    int32_t n_query;        /* the FIT's Q >= 1: the prior term is (lambd * v[k]) / (float)Q   */
+    int32_t hard;           /* 1: u is the one-hot of preds                                    */
+} tclip_score_problem;
+size_t tclip_em_dirichlet_score_workspace_bytes(const tclip_score_problem* p);
+int tclip_em_dirichlet_score(const tclip_score_problem* p, const float* x /*[T,R,K]*/, const float* alpha /*[T,K,K]*/,
+                             const float* v /*[T,K] or NULL*/, float* u /*[T,R,K] or NULL*/, int32_t* preds /*[T,R]*/,
+                             float* logits /*[T,R,K] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+int tclip_em_dirichlet_score_tasks(const tclip_score_problem* p, const float* table /*[rows,K]*/, const int64_t* idx /*[T,R]*/,
+                                   const int32_t* cols /*[T,K] or NULL*/, const float* alpha, const float* v, float* u,
+                                   int32_t* preds, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Range check of DEVICE-resident index tensors before tclip_em_dirichlet_run_tasks / tclip_gather_rows - what torch's own
  * `all_features_query[indices, :]` (src/eval_zero_shot.py:160-163, src/eval_few_shot.py:233-241) does by raising IndexError:

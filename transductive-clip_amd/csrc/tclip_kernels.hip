@@ -23,6 +23,8 @@
 //   k_criterion(+_mean) per-task relative change of alpha; alpha_old <- alpha      (:236-239)
 //   k_objective_rows, k_objective_task   the objective entries only (tclip_objective.inc): the four float64 terms of the
 //                     penalised objective per task, from logit0, u and (few-shot) alpha, sup, cnt, rowc
+//   k_score_row_consts, k_score   not part of the loop (tclip_score.inc): one E-step of a fitted alpha, v on rows that were not
+//                     queries of the fit, from the device functions of the three E-step kernels above
 //   k_assign_changes  the until-stable entries only: predictions changed since the last iteration, per batch; a batch whose
 //                     predictions stand still is marked done and skipped by every kernel above from then on
 //
@@ -1926,6 +1928,21 @@ __global__ __launch_bounds__(1024) void k_mm_decide(const double* __restrict__ r
 
 // ------------------------------------------------------------------------------------------
 // E-step, part 1: per row  lgamma(sum_d alpha) + (-sum_d lgamma(alpha_d))     (em_dirichlet.py:35-36)
+// The constant of one alpha row `ar` on a 32-lane group, the same value in every lane (k_row_consts, k_score_row_consts)
+template <int E>
+__device__ __forceinline__ float dirichlet_row_const(const float* __restrict__ ar, int K, int lane) {
+    float av[E], lg[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        const int d = e * kGroup + lane;
+        const bool ok = d < K;
+        av[e] = ok ? ar[d] : 0.0f;
+        lg[e] = ok ? lgamma_f32(av[e]) : 0.0f;
+    }
+    const float l1 = lgamma_f32(group_sum_torch<E>(av, K, lane));
+    const float l2 = -group_sum_torch<E>(lg, K, lane);
+    return l1 + l2;
+}
 template <int E>
 __global__ __launch_bounds__(256) void k_row_consts(const float* __restrict__ alpha, const int32_t* __restrict__ rows,
                                                     const int32_t* __restrict__ n_rows, int K,
@@ -1935,17 +1952,8 @@ __global__ __launch_bounds__(256) void k_row_consts(const float* __restrict__ al
     const int n = *n_rows;
     for (int i = blockIdx.x * groups_per_block + threadIdx.x / kGroup; i < n; i += gridDim.x * groups_per_block) {
         const int row = rows[i];
-        float av[E], lg[E];
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int d = e * kGroup + lane;
-            const bool ok = d < K;
-            av[e] = ok ? alpha[(size_t)row * K + d] : 0.0f;
-            lg[e] = ok ? lgamma_f32(av[e]) : 0.0f;
-        }
-        const float l1 = lgamma_f32(group_sum_torch<E>(av, K, lane));
-        const float l2 = -group_sum_torch<E>(lg, K, lane);
-        if (lane == 0) rowc[row] = l1 + l2;
+        const float c = dirichlet_row_const<E>(alpha + (size_t)row * K, K, lane);
+        if (lane == 0) rowc[row] = c;
     }
 }
 
@@ -1964,6 +1972,19 @@ constexpr int logits_full_regs(int E) {
         prev = s;
     }
     return prev;
+}
+// sum_d (alpha_d - 1) * log z_d of one (class, row) pair on a 32-lane group, valid in lane 0: am1[e] and lv[e] belong to element
+// 32 e + lane (am1 is 0 past the row, lv may hold anything there).  k_logits and k_score.
+template <int E>
+__device__ __forceinline__ float dirichlet_dot(const float (&am1)[E], const float (&lv)[E], int K, int lane) {
+    constexpr int kFull = logits_full_regs(E);
+    float pr[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        pr[e] = am1[e] * lv[e];
+        if (e >= kFull) pr[e] = e * kGroup + lane < K ? pr[e] : 0.0f;
+    }
+    return group_sum_torch<E, true, kFull>(pr, K, lane);
 }
 template <int E, int R>
 __global__ __launch_bounds__(256) void k_logits(const float* __restrict__ alpha, const float* __restrict__ logz,
@@ -2011,13 +2032,7 @@ __global__ __launch_bounds__(256) void k_logits(const float* __restrict__ alpha,
             }
         };
         auto one = [&](int r, int t, int q, const float (&lv)[E]) {
-            float pr[E];
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                pr[e] = am1[r][e] * lv[e];
-                if (e >= kFull) pr[e] = e * kGroup + lane < K ? pr[e] : 0.0f;
-            }
-            const float l3 = group_sum_torch<E, true, kFull>(pr, K, lane);
+            const float l3 = dirichlet_dot<E>(am1[r], lv, K, lane);
             if (lane == 0) logit0[((size_t)t * Q + q) * K + (row[r] - t * K)] = rc[r] + l3;
         };
         if (same) {
@@ -2239,22 +2254,14 @@ __global__ __launch_bounds__(256) void k_cov_logits_rows(const float* __restrict
 // hard_kmeans.py:193) and the hard one-hot.  u may be logit0 itself (each entry is read before it
 // is written, by the same thread).
 // `done` (optional, the until-stable driver): a row of a batch b with done[b] set keeps its u and preds; rows_per_batch = N * Q.
-__global__ __launch_bounds__(256) void k_softmax(const float* logit0, const float* __restrict__ v, int TQ,
-                                                 int Q, int K, float lambd, int hard, int pick_min, float* u,
-                                                 int32_t* __restrict__ preds, const int32_t* __restrict__ done = nullptr,
-                                                 int rows_per_batch = 0) {
-    const int lane = threadIdx.x & 15;
-    const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    if (r >= TQ) return;
-    if (done && done[r / rows_per_batch]) return;       // the whole 16-lane group of a row leaves together
-    const int t = r / Q;
-    const float* x = logit0 + (size_t)r * K;
-    const float* vt = v ? v + (size_t)t * K : nullptr;
-    float* ur = u + (size_t)r * K;
-    const float qf = (float)Q;
+// softmax_row16 is one row on its 16-lane group (k_softmax; k_score, whose rows lie in LDS): x the row's logits, vt the task's v
+// or null, ur the row of u (may be x), qf the query count the prior term is divided by.  Returns the prediction, the same in
+// all 16 lanes.
+__device__ __forceinline__ int softmax_row16(const float* x, const float* __restrict__ vt, int K, float lambd, float qf, int hard,
+                                             int pick_min, float* ur, int lane) {
     float mx = -__builtin_inff();
     for (int k = lane; k < K; k += 16) {
-        const float val = v ? x[k] + (lambd * vt[k]) / qf : x[k];
+        const float val = vt ? x[k] + (lambd * vt[k]) / qf : x[k];
         ur[k] = val;
         mx = val > mx ? val : mx;
     }
@@ -2303,6 +2310,19 @@ __global__ __launch_bounds__(256) void k_softmax(const float* logit0, const floa
     if (first_nan < K) best_k = first_nan;
     if (hard)
         for (int k = lane; k < K; k += 16) ur[k] = (k == best_k) ? 1.0f : 0.0f;
+    return best_k;
+}
+__global__ __launch_bounds__(256) void k_softmax(const float* logit0, const float* __restrict__ v, int TQ,
+                                                 int Q, int K, float lambd, int hard, int pick_min, float* u,
+                                                 int32_t* __restrict__ preds, const int32_t* __restrict__ done = nullptr,
+                                                 int rows_per_batch = 0) {
+    const int lane = threadIdx.x & 15;
+    const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    if (r >= TQ) return;
+    if (done && done[r / rows_per_batch]) return;       // the whole 16-lane group of a row leaves together
+    const int t = r / Q;
+    const int best_k = softmax_row16(logit0 + (size_t)r * K, v ? v + (size_t)t * K : nullptr, K, lambd, (float)Q, hard, pick_min,
+                                     u + (size_t)r * K, lane);
     if (lane == 0) preds[r] = best_k;
 }
 
@@ -4688,3 +4708,4 @@ int tclip_gather_task_rows(const float* table, int64_t n_rows, int32_t width, co
 #include "tclip_visual_fs.inc"
 #include "tclip_methods.inc"
 #include "tclip_match.inc"
+#include "tclip_score.inc"

@@ -210,6 +210,34 @@ class EMDirichletBase(MethodBase):
             self.objectives = runner.objective(self.objective_terms, self.lambd)        # (n_task, iter)
         return res
 
+    # -- scoring with the fitted model ------------------------------------------------------
+    def _score_kw(self, hard):
+        """what the scoring calls take from the last run: its alpha and v, the class's lambd, args.n_query, HARD"""
+        if not self.args.use_softmax_feature:
+            raise ValueError(_SIMPLEX_ERROR)
+        if getattr(self, "alpha", None) is None or getattr(self, "v", None) is None:
+            raise RuntimeError("{} has no fitted model to score with: run_task (or run_method) goes first".format(type(self).__name__))
+        self._cuda_device("EM-Dirichlet")
+        return dict(lambd=self.lambd, n_query=self.args.n_query, hard=self.HARD if hard is None else bool(hard))
+
+    def score_rows(self, x, hard=None):
+        """One E-step of the model the last run left (self.alpha, self.v) on rows that need not have been its queries:
+        x (T,R,K) probability features, T the tasks of that run, any R -> tclip_amd.score.ScoreResult(u (T,R,K), preds (T,R)
+        i32, logits None), cuda.  hard=None takes the class's HARD.  score_rows(x_q) of the run's own queries returns its
+        self.u and self.preds bit for bit.  In zero-shot the result indexes CLUSTERS: mapping clusters to classes stays with
+        the accuracy tail (compute_acc_clustering) and is not applied here.  Keeps nothing and logs nothing."""
+        kw = self._score_kw(hard)
+        from tclip_amd import score
+        return score.score_em_dirichlet(x.to(self.device), self.alpha, self.v, **kw)
+
+    def score_table_rows(self, table, idx, cols=None, hard=None):
+        """score_rows with the rows read in place from a feature table: table (rows,K), idx (T,R) rows of it, cols (T,K) the
+        per-task column permutation or None (tclip_amd.score.score_em_dirichlet_tasks); the bits of score_rows on the
+        gathered rows.  Clusters, not classes, in zero-shot - as score_rows."""
+        kw = self._score_kw(hard)
+        from tclip_amd import score
+        return score.score_em_dirichlet_tasks(table.to(self.device), idx, self.alpha, self.v, cols, **kw)
+
 
 class ZeroShotMixin:
     def run_task(self, task_dic):

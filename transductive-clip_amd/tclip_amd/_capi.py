@@ -13,7 +13,11 @@ class Problem(ctypes.Structure):
         "n_batches", "tasks_per_batch", "n_query", "n_class", "n_support", "iters", "iter_mm", "lambd", "hard")]
 
 
-class TaskSource(ctypes.Structure):                 # struct tclip_task_source
+class ScoreProblem(ctypes.Structure):               # struct tclip_score_problem
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_task", "rows_per_task", "n_class", "lambd", "n_query", "hard")]
+
+
+class TaskSource(ctypes.Structure):                # struct tclip_task_source
     _fields_ = [(n, ctypes.c_void_p) for n in ("table_q", "q_idx", "table_s", "s_idx", "cols")]
 
 
@@ -41,6 +45,10 @@ _SIGNATURES = {
                                          + [ctypes.c_size_t, _P]),
     "tclip_em_dirichlet_run_tasks_objective": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(TaskSource), _P, ctypes.c_int32]
                                                + [_P] * 10 + [ctypes.c_size_t, _P]),
+    # (problem, x | table, idx, cols, alpha, v, u, preds, logits, workspace)
+    "tclip_em_dirichlet_score_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ScoreProblem)]),
+    "tclip_em_dirichlet_score": (ctypes.c_int, [ctypes.POINTER(ScoreProblem)] + [_P] * 7 + [ctypes.c_size_t, _P]),
+    "tclip_em_dirichlet_score_tasks": (ctypes.c_int, [ctypes.POINTER(ScoreProblem)] + [_P] * 9 + [ctypes.c_size_t, _P]),
     "tclip_prototype_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
     "tclip_cluster_prototypes": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 6 + [ctypes.c_size_t, _P]),
     "tclip_match_clusters_host": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 5 + [ctypes.c_int32, _P, _P]),
