@@ -3202,6 +3202,19 @@ static int fail(int code, const char* fmt, const char* detail = "") {
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The one cursor of every workspace layout: 256-byte aligned regions handed out in order, as typed pointers into `base`.  A null
+// `base` gives the sizes alone (every pointer null); a region that is not `present` takes no room and reads null.  `bytes` is
+// what has been handed out so far.
+struct WsCursor {
+    char* base;
+    size_t bytes = 0;
+    template <typename P>
+    void take(P*& ptr, size_t n_bytes, bool present = true) {
+        ptr = base && present ? (P*)(base + bytes) : nullptr;
+        bytes += present ? align_up(n_bytes) : 0;
+    }
+};
+
 // The end of every entry's argument checks: the caller's workspace holds what `query_name` returns and is 256-byte aligned.
 static int check_workspace(const void* ws, size_t have, size_t need, const char* query_name) {
     if (have < need) return fail(TCLIP_ERR_WORKSPACE, "workspace smaller than %s()", query_name);
@@ -3289,43 +3302,39 @@ static Workspace workspace_view(const tclip_problem& p, bool stable, bool object
     const bool zs = p.n_support == 0;
     w.n_chunks = n_chunks_of(p.iter_mm);
     w.n_checks = zs ? n_checks_of(p.iter_mm) : 0;
-    size_t o = 0;
-    auto take = [&](auto*& ptr, size_t bytes, bool present = true) {
-        ptr = base && present ? (std::remove_reference_t<decltype(ptr)>)(base + o) : nullptr;
-        o += present ? align_up(bytes) : 0;
-    };
-    take(w.logz, T * Q * K * 4);
-    take(w.y, T * K * K * 4);
-    take(w.alpha_old, T * K * K * 4);
-    take(w.beta_dead, T * K * K * 4, zs);
-    take(w.sup, T * K * K * 4, !zs);
-    take(w.cnt, T * K * 4, !zs);
-    take(w.cs, T * K * 4);
-    take(w.live, T * K);
-    take(w.rowc, T * K * 4);
-    take(w.logit0, T * Q * K * 4);
-    take(w.cache, T * K * (size_t)w.n_checks * 16, zs);
-    take(w.cache_len, T * K * 4);
-    take(w.rowpart, T * K * 16);
-    take(w.mm_rows, T * K * 4);
-    take(w.dead_list[1], T * K * 4, zs);
+    WsCursor c{base};
+    c.take(w.logz, T * Q * K * 4);
+    c.take(w.y, T * K * K * 4);
+    c.take(w.alpha_old, T * K * K * 4);
+    c.take(w.beta_dead, T * K * K * 4, zs);
+    c.take(w.sup, T * K * K * 4, !zs);
+    c.take(w.cnt, T * K * 4, !zs);
+    c.take(w.cs, T * K * 4);
+    c.take(w.live, T * K);
+    c.take(w.rowc, T * K * 4);
+    c.take(w.logit0, T * Q * K * 4);
+    c.take(w.cache, T * K * (size_t)w.n_checks * 16, zs);
+    c.take(w.cache_len, T * K * 4);
+    c.take(w.rowpart, T * K * 16);
+    c.take(w.mm_rows, T * K * 4);
+    c.take(w.dead_list[1], T * K * 4, zs);
     w.dead_list[0] = w.mm_rows;
     if (!zs) w.dead_list[1] = w.mm_rows;
-    take(w.head_back, T * K * 4, zs);
-    take(w.dead_counts, ((size_t)w.n_chunks + 3) * 4);
-    take(w.cls, T * K * 2, zs);
-    take(w.n_live, T * 4, zs);
-    take(w.live_rows, T * K * 4);
-    take(w.counts, 256);
-    take(w.flags, 256);
-    take(w.stop, B * 4);
-    take(w.ratio, T * 4);
-    take(w.dpart, B * kDecideSlices * 2 * sizeof(double));
-    take(w.prev_preds, T * Q * 4, stable);
-    take(w.quiet, B * 4, stable);
-    take(w.done, B * 4, stable);
-    take(w.objrows, T * Q * 2 * sizeof(double), objective);
-    w.bytes = o;
+    c.take(w.head_back, T * K * 4, zs);
+    c.take(w.dead_counts, ((size_t)w.n_chunks + 3) * 4);
+    c.take(w.cls, T * K * 2, zs);
+    c.take(w.n_live, T * 4, zs);
+    c.take(w.live_rows, T * K * 4);
+    c.take(w.counts, 256);
+    c.take(w.flags, 256);
+    c.take(w.stop, B * 4);
+    c.take(w.ratio, T * 4);
+    c.take(w.dpart, B * kDecideSlices * 2 * sizeof(double));
+    c.take(w.prev_preds, T * Q * 4, stable);
+    c.take(w.quiet, B * 4, stable);
+    c.take(w.done, B * 4, stable);
+    c.take(w.objrows, T * Q * 2 * sizeof(double), objective);
+    w.bytes = c.bytes;
     return w;
 }
 

@@ -9,6 +9,8 @@
 // tclip_laplacian_shot_sweep_tasks solves the same tasks for a list of lmd values: everything up to the kNN graph once per task
 // (k_lshot_knn), the updates on a grid of (task, value) (k_lshot_sweep_updates); lshot_knn_rows and lshot_solve are the code
 // k_lshot_task runs, so every value's slice holds the single-value entry's bits.
+// Host side: lshot_ws lays the workspace out for every form, lshot_entry is the one function behind the five entries (their
+// form as a Rows of tclip_tim.inc; DESIGN.md, "The method host drivers"), lshot_run the launch sequence.
 //
 // Per task: L2-normalised features, prototypes = support class means, unary[q][k] = ||proto_k - z_q||^2, a kNN graph
 // over the task's queries (W[i][j] = 1 for the knn-1 nearest other queries j of i), then `iter` bound updates
@@ -345,33 +347,33 @@ __global__ __launch_bounds__(64 * kLshotWaves) void k_lshot_sweep_updates(LshotA
                 a.energies + vt * a.iters, Q, K, nn, a.iters, lmd[p]);
 }
 
-struct LshotWs { size_t zs, zq, sup, cnt, proto, ybuf, d2, vals, total; };
-// rows of `dim` elements; pairdist: room for k_lshot_pairdist's [T][Q][Q] fp64 table (the visual entry); n_values > 0 (the
+// The workspace as typed pointers; a null `base` gives `bytes` alone.
+// rows of `dim` elements; pairdist: room for k_lshot_pairdist's [T][Q][Q] fp64 table (the visual entries); n_values > 0 (the
 // sweep entry): ybuf for every (value, task) - the only region that grows with the values - and the values themselves; both
 // take a whole number of 256-byte units PER VALUE, so that the total is affine in n_values
-static LshotWs lshot_ws(const tclip_problem& p, int dim, bool pairdist, int n_values = 0) {
+struct LshotWs {
+    float *zs, *zq, *sup, *cnt, *proto;
+    double *ybuf, *d2, *vals;
+    size_t bytes;
+};
+static LshotWs lshot_ws(const tclip_problem& p, int dim, bool pairdist, int n_values, char* base) {
     const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, D = dim;
     LshotWs w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    w.zs = take(T * S * D * 4);
-    w.zq = take(T * Q * D * 4);
-    w.sup = take(T * K * D * 4);
-    w.cnt = take(T * K * 4);
-    w.proto = take(T * K * D * 4);
-    w.ybuf = take((n_values > 0 ? (size_t)n_values : 1) * align_up(T * 2 * Q * K * 8));
-    w.d2 = pairdist ? take(T * Q * Q * 8) : 0;
-    w.vals = n_values > 0 ? take((size_t)n_values * align_up(8)) : 0;
-    w.total = o;
+    WsCursor c{base};
+    c.take(w.zs, T * S * D * 4);
+    c.take(w.zq, T * Q * D * 4);
+    c.take(w.sup, T * K * D * 4);
+    c.take(w.cnt, T * K * 4);
+    c.take(w.proto, T * K * D * 4);
+    c.take(w.ybuf, (n_values > 0 ? (size_t)n_values : 1) * align_up(T * 2 * Q * K * 8));
+    c.take(w.d2, T * Q * Q * 8, pairdist);
+    c.take(w.vals, (size_t)n_values * align_up(8), n_values > 0);
+    w.bytes = c.bytes;
     return w;
 }
 
-// what both entries check of the problem and of knn / norm_type
-static int check_lshot(const tclip_problem* pp, int32_t knn, int32_t norm_type) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem& p = *pp;
-    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT needs iters >= 1");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive");
+// what every entry checks of knn / norm_type on a checked problem
+static int check_lshot(const tclip_problem& p, int32_t knn, int32_t norm_type) {
     if (norm_type != 0 && norm_type != 1) return fail(TCLIP_ERR_ARG, "norm_type must be 0 (UN) or 1 (L2N); CL2N needs a train mean the reference never passes");
     if (knn < 2 || knn > p.n_query) return fail(TCLIP_ERR_ARG, "knn must be in 2..n_query (the nearest neighbour of a query is the query itself)");
     if (p.n_query > kLshotMaxQ) return fail(TCLIP_ERR_ARG, "n_query must be <= 1024 for LAPLACIAN_SHOT");
@@ -386,17 +388,12 @@ static int check_lshot(const tclip_problem* pp, int32_t knn, int32_t norm_type) 
 // neighbour lists and k_lshot_sweep_updates solves every (task, value) (preds_iter [P][T][iters][Q], energies [P][T][iters]).
 static int lshot_run(const tclip_problem& p, int D, bool pairdist, const RowSrc& x_q, const RowSrc& x_s, const int64_t* y_s,
                      int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter,
-                     double* energies, char* ws, hipStream_t st, const double* values = nullptr, int n_values = 0) {
-    const LshotWs o = lshot_ws(p, D, pairdist, values ? n_values : 0);
+                     double* energies, const LshotWs& ws, hipStream_t st, const double* values = nullptr, int n_values = 0) {
     const size_t smem = (((size_t)p.n_query * (knn - 1) * sizeof(int) + 7) & ~(size_t)7) + (size_t)p.n_query * sizeof(double);
     if (smem > 60000) return fail(TCLIP_ERR_ARG, "n_query * knn too large for the neighbour lists in LDS");
     const int Q = p.n_query, K = p.n_class, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
-    float* zs = (float*)(ws + o.zs);
-    float* zq = (float*)(ws + o.zq);
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* proto = (float*)(ws + o.proto);
-    double* d2 = pairdist ? (double*)(ws + o.d2) : nullptr;
+    float *const zs = ws.zs, *const zq = ws.zq, *const sup = ws.sup, *const cnt = ws.cnt, *const proto = ws.proto;
+    double* const d2 = ws.d2;                                         // null without pairdist
     // normalization (:66-89), prototypes = class means of the normalised support (:201-205); the only launches that read the
     // task rows: a dense tensor, or table rows in place (x.idx != nullptr)
     auto normalize = [&](const RowSrc& x, int rows_per_task, float* out) {
@@ -418,11 +415,11 @@ static int lshot_run(const tclip_problem& p, int D, bool pairdist, const RowSrc&
                        unary);
     if (pairdist)
         hipLaunchKernelGGL(k_lshot_pairdist, dim3((Q + kLshotPdTile - 1) / kLshotPdTile, T), dim3(256), 0, st, (const float*)zq, Q, D, d2);
-    const LshotArgs a{zq, d2, unary, (double*)(ws + o.ybuf), neighbours, preds_iter, energies, Q, K, D, knn, p.iters, lmd};
+    const LshotArgs a{zq, d2, unary, ws.ybuf, neighbours, preds_iter, energies, Q, K, D, knn, p.iters, lmd};
     if (!values) {
         hipLaunchKernelGGL(k_lshot_task, dim3(T), dim3(64 * kLshotWaves), smem, st, a);
     } else {
-        double* lmds = (double*)(ws + o.vals);
+        double* lmds = ws.vals;
         launch_sweep_values(st, values, n_values, lmds, nullptr);
         hipLaunchKernelGGL(k_lshot_knn, dim3((Q + kLshotWaves - 1) / kLshotWaves, T), dim3(64 * kLshotWaves), 0, st, (const float*)zq,
                            (const double*)d2, Q, D, knn - 1, neighbours);
@@ -432,125 +429,81 @@ static int lshot_run(const tclip_problem& p, int D, bool pairdist, const RowSrc&
     return TCLIP_OK;
 }
 
-// The entries fed from the feature tables: check_lshot, then the dense entries' checks with `src` in place of x_q / x_s
-static int lshot_run_tasks(const tclip_problem* pp, int dim, bool visual, const tclip_task_source* src, const int64_t* y_s, int32_t knn,
-                           double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter, double* energies,
-                           void* workspace, size_t workspace_bytes, const char* query_name, void* stream) {
-    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
-    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !unary || !neighbours || !preds_iter ||
-        !energies || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT on visual features permutes no columns: cols must be NULL");
+static const MethodRule kLshot{"LAPLACIAN_SHOT", true, kFewShotOnly, "%s needs iters >= 1", Limits::None};
+
+// All five forms (ws_query: the workspace query to name): the checks in the one order of DESIGN.md ("The method host drivers"),
+// then lshot_run.  The table forms read the task rows in place in the two normalisations; x_s and x_q are never built.  The
+// pairwise-distance table goes with the visual rows.
+static int lshot_entry(const tclip_problem* pp, const Rows& r, const int64_t* y_s, int32_t knn, double lmd, int32_t norm_type,
+                       float* unary, int32_t* neighbours, int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes,
+                       void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, kLshot)) return rc;
     const tclip_problem p = *pp;
-    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, dim, visual).total, query_name)) return rc;
-    return lshot_run(p, dim, visual, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, knn,
-                     lmd, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace, (hipStream_t)stream);
+    if (int rc = check_lshot(p, knn, norm_type)) return rc;
+    if (int rc = check_pointers(r, kLshot, y_s && unary && neighbours && preds_iter && energies && workspace)) return rc;
+    if (int rc = check_values(pp, r)) return rc;
+    const int D = r.D(p);
+    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, D, r.visual, r.n_sweep(), nullptr).bytes, ws_query)) return rc;
+    return lshot_run(p, D, r.visual, r.q(), r.s(), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies,
+                     lshot_ws(p, D, r.visual, r.n_sweep(), (char*)workspace), (hipStream_t)stream, r.values, r.n_sweep());
+}
+static size_t lshot_bytes(const tclip_problem* p, const Rows& r) {
+    return query_accepts(p, r, kLshot) ? lshot_ws(*p, r.D(*p), r.visual, r.n_sweep(), nullptr).bytes : 0;
 }
 
 }  // namespace tclip
 
 extern "C" {
 
-// ---- LAPLACIAN_SHOT for a list of lmd values on the same tasks (see lshot_run): dim == 0 is tclip_laplacian_shot_run_tasks'
-// problem, dim > 0 tclip_laplacian_shot_visual_run_tasks'
-size_t tclip_laplacian_shot_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
-    if (check_problem(p) != TCLIP_OK || check_sweep_dim(dim) != TCLIP_OK) return 0;
-    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive"), 0;
-    if (check_sweep_count(p, n_values) != TCLIP_OK) return 0;
-    return lshot_ws(*p, dim ? dim : p->n_class, dim > 0, n_values).total;
-}
-
-int tclip_laplacian_shot_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, int32_t knn,
-                                     const double* values, int32_t n_values, int32_t norm_type, float* unary, int32_t* neighbours,
-                                     int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (int rc = check_sweep_dim(dim)) return rc;
-    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
-    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !unary || !neighbours || !preds_iter ||
-        !energies || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    const bool visual = dim > 0;
-    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT on visual features permutes no columns: cols must be NULL");
-    if (int rc = check_sweep_values(pp, values, n_values)) return rc;
-    const tclip_problem p = *pp;
-    const int D = visual ? dim : p.n_class;
-    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, D, visual, n_values).total,
-                                 "tclip_laplacian_shot_sweep_tasks_workspace_bytes"))
-        return rc;
-    return lshot_run(p, D, visual, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, knn,
-                     0.0, norm_type, unary, neighbours, preds_iter, energies, (char*)workspace, (hipStream_t)stream, values, n_values);
-}
-
+// No query looks at iters; the two dense ones do not look at n_support either.
 size_t tclip_laplacian_shot_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    return lshot_ws(*p, p->n_class, false).total;
+    return lshot_bytes(p, rows_dense(nullptr, nullptr, kAnyIters | kAnySupport));
+}
+size_t tclip_laplacian_shot_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return lshot_bytes(p, rows_visual(dim, nullptr, nullptr, kAnyIters | kAnySupport));
+}
+size_t tclip_laplacian_shot_tasks_workspace_bytes(const tclip_problem* p) { return lshot_bytes(p, rows_tables(nullptr, kAnyIters)); }
+size_t tclip_laplacian_shot_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return lshot_bytes(p, rows_visual_tables(dim, nullptr, kAnyIters));
+}
+size_t tclip_laplacian_shot_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    return lshot_bytes(p, rows_sweep(dim, nullptr, nullptr, n_values, kAnyIters));
 }
 
 int tclip_laplacian_shot_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, int32_t knn,
                              double lmd, int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter,
                              double* energies, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT needs iters >= 1");
-    if (!x_q || !x_s || !y_s || !unary || !neighbours || !preds_iter || !energies || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
-    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, p.n_class, false).total, "tclip_laplacian_shot_workspace_bytes")) return rc;
-    return lshot_run(p, p.n_class, false, dense_rows(x_q), dense_rows(x_s), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter,
-                     energies, (char*)workspace, (hipStream_t)stream);
-}
-
-size_t tclip_laplacian_shot_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024"), 0;
-    return lshot_ws(*p, dim, true).total;
+    return lshot_entry(pp, rows_dense(x_q, x_s), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
+                       workspace_bytes, stream, "tclip_laplacian_shot_workspace_bytes");
 }
 
 int tclip_laplacian_shot_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s,
                                     int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours,
                                     int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
-    if (int rc = check_lshot(pp, knn, norm_type)) return rc;
-    if (!x_q || !x_s || !y_s || !unary || !neighbours || !preds_iter || !energies || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    const tclip_problem p = *pp;
-    if (int rc = check_workspace(workspace, workspace_bytes, lshot_ws(p, dim, true).total, "tclip_laplacian_shot_visual_workspace_bytes"))
-        return rc;
-    return lshot_run(p, dim, true, dense_rows(x_q), dense_rows(x_s), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies,
-                     (char*)workspace, (hipStream_t)stream);
-}
-
-// ---- LAPLACIAN_SHOT fed from the feature tables: the two normalisations read the task rows in place, x_s and x_q are never
-// built; workspace, checks and everything after the normalisations are the dense entries'
-size_t tclip_laplacian_shot_tasks_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive"), 0;
-    return lshot_ws(*p, p->n_class, false).total;
-}
-
-size_t tclip_laplacian_shot_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024"), 0;
-    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "LAPLACIAN_SHOT is a few-shot method: n_support must be positive"), 0;
-    return lshot_ws(*p, dim, true).total;
+    return lshot_entry(pp, rows_visual(dim, x_q, x_s), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
+                       workspace_bytes, stream, "tclip_laplacian_shot_visual_workspace_bytes");
 }
 
 int tclip_laplacian_shot_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, int32_t knn, double lmd,
                                    int32_t norm_type, float* unary, int32_t* neighbours, int32_t* preds_iter, double* energies,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    return lshot_run_tasks(pp, pp->n_class, false, src, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
-                           workspace_bytes, "tclip_laplacian_shot_tasks_workspace_bytes", stream);
+    return lshot_entry(pp, rows_tables(src), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
+                       workspace_bytes, stream, "tclip_laplacian_shot_tasks_workspace_bytes");
 }
 
 int tclip_laplacian_shot_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s,
                                           int32_t knn, double lmd, int32_t norm_type, float* unary, int32_t* neighbours,
                                           int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
-    return lshot_run_tasks(pp, dim, true, src, y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
-                           workspace_bytes, "tclip_laplacian_shot_visual_tasks_workspace_bytes", stream);
+    return lshot_entry(pp, rows_visual_tables(dim, src), y_s, knn, lmd, norm_type, unary, neighbours, preds_iter, energies, workspace,
+                       workspace_bytes, stream, "tclip_laplacian_shot_visual_tasks_workspace_bytes");
+}
+
+// LAPLACIAN_SHOT for a list of lmd values on the same tasks (see lshot_run)
+int tclip_laplacian_shot_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, int32_t knn,
+                                     const double* values, int32_t n_values, int32_t norm_type, float* unary, int32_t* neighbours,
+                                     int32_t* preds_iter, double* energies, void* workspace, size_t workspace_bytes, void* stream) {
+    return lshot_entry(pp, rows_sweep(dim, src, values, n_values), y_s, knn, 0.0, norm_type, unary, neighbours, preds_iter, energies,
+                       workspace, workspace_bytes, stream, "tclip_laplacian_shot_sweep_tasks_workspace_bytes");
 }
 
 }  // extern "C"

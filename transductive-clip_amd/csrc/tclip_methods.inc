@@ -8,6 +8,10 @@
 // exists on probability features only and keeps its own loop below.  EM-Dirichlet does not come through here.
 // PADDLE and BD-CSPN also run from the feature tables (tclip_*_run_tasks): PADDLE's class sums and BD-CSPN's normalisations
 // read the task rows in place through a RowSrc.
+// Host side, in this order: the FeatureSpace, one layout function per method (typed views over the one WsCursor), the loops,
+// then one entry function per method for all its call forms (kmeans_entry, em_gaussian_cov_entry, paddle_entry, bdcspn_entry;
+// the form as a Rows of tclip_tim.inc, the checks in the one order of DESIGN.md, "The method host drivers") and the extern "C"
+// functions, each an adaptor call and that one call.
 
 namespace tclip {
 
@@ -70,137 +74,104 @@ struct FeatureSpace {
     }
 };
 
-// ---- workspace layouts: byte offsets of 256-byte aligned regions, `total` their sum ------------------------------------
+// ---- workspace layouts: one function per method that returns typed pointers to 256-byte aligned regions and `bytes`, their
+// sum; a null `base` gives `bytes` alone ---------------------------------------------------------------------------------------
 // The k-means loops hold no feature rows of their own: no region depends on the row length.
+// det (EM_GAUSSIAN_COV on visual features): the half log-determinants [T, K] f32, behind the k-means regions
 struct KmeansWs {
-    size_t cs, live, ones, logit, change, total;      // change [T] f32: HARD_KMEANS and KL_KMEANS only
-    static KmeansWs layout(const tclip_problem& p) {
-        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
-        KmeansWs w;
-        size_t o = 0;
-        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-        w.cs = take(T * K * 4);
-        w.live = take(T * K);
-        w.ones = take(T * K);
-        w.logit = take(T * Q * K * 4);
-        w.change = take(T * 4);
-        w.total = o;
-        return w;
-    }
+    float* cs;
+    uint8_t *live, *ones;
+    float *logit, *change, *det;      // change [T] f32: HARD_KMEANS and KL_KMEANS only
+    size_t bytes;
 };
+static KmeansWs kmeans_ws(const tclip_problem& p, bool det, char* base) {
+    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query;
+    KmeansWs w;
+    WsCursor c{base};
+    c.take(w.cs, T * K * 4);
+    c.take(w.live, T * K);
+    c.take(w.ones, T * K);
+    c.take(w.logit, T * Q * K * 4);
+    c.take(w.change, T * 4);
+    c.take(w.det, T * K * 4, det);
+    w.bytes = c.bytes;
+    return w;
+}
 
-// EM_GAUSSIAN_COV on visual features: the k-means regions and the half log-determinants [T, K] f32
-struct CovVisualWs {
-    size_t det, total;
-    static CovVisualWs layout(const tclip_problem& p) {
-        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class;
-        CovVisualWs w;
-        w.det = KmeansWs::layout(p).total;
-        w.total = w.det + align_up(T * K * 4);
-        return w;
-    }
-};
-
+// tables (PADDLE fed from the feature tables): the query rows [T, Q, D] follow, gathered once; nothing depends on n_support
 struct PaddleWs {
-    size_t sup, cnt, cs, live, logit, total;
-    static PaddleWs layout(const tclip_problem& p, int dim) {
-        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, D = dim;
-        PaddleWs w;
-        size_t o = 0;
-        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-        w.sup = take(T * K * D * 4);
-        w.cnt = take(T * K * 4);
-        w.cs = take(T * K * 4);
-        w.live = take(T * K);
-        w.logit = take(T * Q * K * 4);
-        w.total = o;
-        return w;
-    }
+    float *sup, *cnt, *cs;
+    uint8_t* live;
+    float *logit, *xq;
+    size_t bytes;
 };
+static PaddleWs paddle_ws(const tclip_problem& p, int dim, bool tables, char* base) {
+    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, D = dim;
+    PaddleWs w;
+    WsCursor c{base};
+    c.take(w.sup, T * K * D * 4);
+    c.take(w.cnt, T * K * 4);
+    c.take(w.cs, T * K * 4);
+    c.take(w.live, T * K);
+    c.take(w.logit, T * Q * K * 4);
+    c.take(w.xq, T * Q * D * 4, tables);
+    w.bytes = c.bytes;
+    return w;
+}
 
-// PADDLE fed from the feature tables: PaddleWs and the query rows [T, Q, D], gathered once; nothing depends on n_support
-struct PaddleTasksWs {
-    size_t xq, total;
-    static PaddleTasksWs layout(const tclip_problem& p, int dim) {
-        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, Q = p.n_query, D = dim;
-        PaddleTasksWs w;
-        w.xq = PaddleWs::layout(p, dim).total;
-        w.total = w.xq + align_up(T * Q * D * 4);
-        return w;
-    }
-};
-
+// tables (BD-CSPN fed from the feature tables, bdcspn_pass with indexed sources): zs has no region of its own - it lies at the
+// start of the logit region, which then holds max(T R K, T S D) floats.  Their lifetimes in bdcspn_pass do not overlap: zs is
+// written by the first normalisation and last read by the normalisation that builds aug (after the support statistics and
+// k_bdcspn_eta); logit is first written by the sp.dist that follows it, on the same stream, and nothing after that reads zs.
+// sweep (tclip_bdcspn_sweep_tasks): the normalised initial prototypes get a region of their own, wn0 - every value reads
+// them, and wn is overwritten by each value's rectified prototypes; otherwise wn0 is wn itself.  No region depends on the
+// number of values.
 struct BdcspnWs {
-    size_t zs, zq, zqn, mean, eta, sup, cnt, wn, aug, logit, cs, live, dummy, wn0, total;
-    static BdcspnWs layout(const tclip_problem& p, int dim) {
-        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
-        BdcspnWs w;
-        size_t o = 0;
-        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-        w.zs = take(T * S * D * 4);
-        w.zq = take(T * Q * D * 4);
-        w.zqn = take(T * Q * D * 4);
-        w.mean = take(T * D * 4);
-        w.eta = take(T * D * 4);
-        w.sup = take(T * K * D * 4);
-        w.cnt = take(T * K * 4);
-        w.wn = take(T * K * D * 4);
-        w.aug = take(T * R * D * 4);
-        w.logit = take(T * R * K * 4);
-        w.cs = take(T * K * 4);
-        w.live = take(T * K);
-        w.dummy = take(T * R * 4);
-        w.wn0 = w.wn;
-        w.total = o;
-        return w;
-    }
-    // BD-CSPN fed from the feature tables (bdcspn_pass with indexed sources): the dense regions, except that zs has none of its
-    // own - it lies at the start of the logit region, which holds max(T R K, T S D) floats.  Their lifetimes in bdcspn_pass do
-    // not overlap: zs is written by the first normalisation and last read by the normalisation that builds aug (after the
-    // support statistics and k_bdcspn_eta); logit is first written by the sp.dist that follows it, on the same stream, and
-    // nothing after that reads zs.
-    // sweep (tclip_bdcspn_sweep_tasks): the normalised initial prototypes get a region of their own, wn0 - every value reads
-    // them, and wn is overwritten by each value's rectified prototypes.  No region depends on the number of values.
-    static BdcspnWs layout_tasks(const tclip_problem& p, int dim, bool sweep = false) {
-        const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
-        BdcspnWs w;
-        size_t o = 0;
-        auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-        w.zq = take(T * Q * D * 4);
-        w.zqn = take(T * Q * D * 4);
-        w.mean = take(T * D * 4);
-        w.eta = take(T * D * 4);
-        w.sup = take(T * K * D * 4);
-        w.cnt = take(T * K * 4);
-        w.wn = take(T * K * D * 4);
-        w.aug = take(T * R * D * 4);
-        w.logit = take((R * K > S * D ? T * R * K : T * S * D) * 4);
-        w.zs = w.logit;
-        w.cs = take(T * K * 4);
-        w.live = take(T * K);
-        w.dummy = take(T * R * 4);
-        w.wn0 = sweep ? take(T * K * D * 4) : w.wn;
-        w.total = o;
-        return w;
-    }
+    float *zs, *zq, *zqn, *mean, *eta, *sup, *cnt, *wn, *aug, *logit, *cs;
+    uint8_t* live;
+    int32_t* dummy;
+    float* wn0;
+    size_t bytes;
 };
+static BdcspnWs bdcspn_ws(const tclip_problem& p, int dim, bool tables, bool sweep, char* base) {
+    const size_t T = (size_t)p.n_batches * p.tasks_per_batch, K = p.n_class, Q = p.n_query, S = p.n_support, R = S + Q, D = dim;
+    BdcspnWs w;
+    WsCursor c{base};
+    c.take(w.zs, T * S * D * 4, !tables);
+    c.take(w.zq, T * Q * D * 4);
+    c.take(w.zqn, T * Q * D * 4);
+    c.take(w.mean, T * D * 4);
+    c.take(w.eta, T * D * 4);
+    c.take(w.sup, T * K * D * 4);
+    c.take(w.cnt, T * K * 4);
+    c.take(w.wn, T * K * D * 4);
+    c.take(w.aug, T * R * D * 4);
+    c.take(w.logit, (tables && S * D >= R * K ? T * S * D : T * R * K) * 4);
+    if (tables) w.zs = w.logit;
+    c.take(w.cs, T * K * 4);
+    c.take(w.live, T * K);
+    c.take(w.dummy, T * R * 4);
+    c.take(w.wn0, T * K * D * 4, sweep);
+    if (!sweep) w.wn0 = w.wn;
+    w.bytes = c.bytes;
+    return w;
+}
 
 // ---- SOFT_KMEANS, EM_GAUSSIAN, HARD_KMEANS (SURVEY.md section 8f, F1; BASELINE config 3's second method) ----------------
 // Soft and EmGaussian share everything but the class-proportion term lambd * v / Q in the softmax and the v update
 // (em_gaussian.py:129-143).  u_init: the features themselves for probability features, the text-prompt u0 for visual ones.
-enum class Kmeans { Soft, EmGaussian, Hard };
+// Kl: the checks and outputs of Hard and a loop of its own.  kmeans_entry is the only place that turns a Kmeans into a loop and
+// sends Kl to kl_kmeans_loop: kmeans_loop never receives it (it has no branch for it and would run it as Soft).
+enum class Kmeans { Soft, EmGaussian, Hard, Kl };
 
 static int kmeans_loop(const FeatureSpace& sp, Kmeans kind, const tclip_problem& p, const float* x_q, const float* u_init,
-                       float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, char* ws, hipStream_t st) {
-    const KmeansWs o = KmeansWs::layout(p);
+                       float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, const KmeansWs& ws,
+                       hipStream_t st) {
     const bool hard = kind == Kmeans::Hard, emg = kind == Kmeans::EmGaussian;
     const int Q = p.n_query, K = p.n_class, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
     const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    uint8_t* ones = (uint8_t*)(ws + o.ones);
-    float* logit0 = (float*)(ws + o.logit);
-    float* change = (float*)(ws + o.change);
+    float *const cs = ws.cs, *const logit0 = ws.logit, *const change = ws.change;
+    uint8_t *const live = ws.live, *const ones = ws.ones;
     hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, u_init, u, TQK);       // u = z / u = u0
     TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));                                     // HARD_KMEANS: every centroid moves every iteration
     if (emg) hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
@@ -243,16 +214,13 @@ static int kmeans_loop(const FeatureSpace& sp, Kmeans kind, const tclip_problem&
 }
 
 // ---- EM_GAUSSIAN_COV (SURVEY.md F1): EM_GAUSSIAN with a diagonal inverse covariance per cluster; no temperature -----------
-// `det`: room for [T, K] floats on visual features, unused on probability features.
+// ws.det: room for [T, K] floats on visual features, null (unused) on probability features.
 static int em_gaussian_cov_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const float* u_init, float* u, float* v,
-                                float* w, float* s, int32_t* preds, float* det, char* ws, hipStream_t st) {
-    const KmeansWs o = KmeansWs::layout(p);
+                                float* w, float* s, int32_t* preds, const KmeansWs& ws, hipStream_t st) {
     const int Q = p.n_query, K = p.n_class, T = p.n_batches * p.tasks_per_batch, TK = T * K;
     const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    uint8_t* ones = (uint8_t*)(ws + o.ones);
-    float* logit0 = (float*)(ws + o.logit);
+    float *const cs = ws.cs, *const logit0 = ws.logit, *const det = ws.det;
+    uint8_t *const live = ws.live, *const ones = ws.ones;
     hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, u_init, u, TQK);       // u = z / u = u0
     TCLIP_HIP(hipMemsetAsync(ones, 1, (size_t)TK, st));
     hipLaunchKernelGGL(k_fill, dim3(ew_grid(TK)), dim3(256), 0, st, v, 0.0f, (size_t)TK);
@@ -285,16 +253,12 @@ static int em_gaussian_cov_loop(const FeatureSpace& sp, const tclip_problem& p, 
 // that reads the support set, and the only one before the loop that is more than a fill - are taken once; cs, live and the
 // logits are scratch every value reuses.  Each value sees the launches of a single-value call with the same arguments.
 static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const float* x_q, const RowSrc& x_s, const int64_t* y_s,
-                       float lambd, float* u, float* v, float* w, int32_t* preds, char* ws, hipStream_t st,
+                       float lambd, float* u, float* v, float* w, int32_t* preds, const PaddleWs& ws, hipStream_t st,
                        const double* values = nullptr, int n_values = 0) {
-    const PaddleWs o = PaddleWs::layout(p, sp.D);
     const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, T = p.n_batches * p.tasks_per_batch, TK = T * K;
     const size_t TQ = (size_t)T * Q;
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    float* logit0 = (float*)(ws + o.logit);
+    float *const sup = ws.sup, *const cnt = ws.cnt, *const cs = ws.cs, *const logit0 = ws.logit;
+    uint8_t* const live = ws.live;
     // init (paddle.py:180-197): v = 0, w = class means of the support set (on visual features the text-prompt u is overwritten
     // before it is read); every centroid moves every iteration
     for (int i = 0; i < (values ? n_values : 1); i++, u += TQ * K, v += TK, w += (size_t)TK * D, preds += TQ) {
@@ -322,30 +286,21 @@ static int paddle_loop(const FeatureSpace& sp, const tclip_problem& p, const flo
 // ---- BD-CSPN (SURVEY.md F4): one pass, no loop ------------------------------------------------------------------------
 // k_col_mean, k_bdcspn_normalize, k_bdcspn_eta and k_div_rows take the row length where their signatures say K.
 // x_q / x_s: dense tensors, or table rows read in place by the only three launches that touch them (the train mean and the
-// two normalisations into zs / zq); `o`: BdcspnWs::layout for the former, ::layout_tasks (zs inside logit) for the latter.
-// values != nullptr (tclip_bdcspn_sweep_tasks; o.wn0 a region of its own): everything up to and including the augmented set
+// two normalisations into zs / zq); `ws`: bdcspn_ws of the form (table rows: zs inside logit).
+// values != nullptr (tclip_bdcspn_sweep_tasks; ws.wn0 a region of its own): everything up to and including the augmented set
 // reads no temp and runs once; from the first soft assignment on the pass runs once per value, one after the other on the
 // stream, with temp = (float)values[i] and slice i of prototypes [P,T,K,D], u [P,T,Q,K], preds [P,T,Q].  Each value sees the
 // launches of a single-value call with the same arguments.
-static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const BdcspnWs& o, const RowSrc& x_q, const RowSrc& x_s,
-                       const int64_t* y_s, float temp, int norm_type, float* prototypes, float* u, int32_t* preds, char* ws, hipStream_t st,
+static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const BdcspnWs& ws, const RowSrc& x_q, const RowSrc& x_s,
+                       const int64_t* y_s, float temp, int norm_type, float* prototypes, float* u, int32_t* preds, hipStream_t st,
                        const double* values = nullptr, int n_values = 0) {
     const int Q = p.n_query, K = p.n_class, D = sp.D, S = p.n_support, R = S + Q, T = p.n_batches * p.tasks_per_batch, TK = T * K;
     const int TD = T * D;
-    float* zs = (float*)(ws + o.zs);
-    float* zq = (float*)(ws + o.zq);
-    float* zqn = (float*)(ws + o.zqn);
-    float* mean = (float*)(ws + o.mean);
-    float* eta = (float*)(ws + o.eta);
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* wn = (float*)(ws + o.wn);
-    float* wn0 = (float*)(ws + o.wn0);                                // the normalised initial prototypes: wn itself but in a sweep
-    float* aug = (float*)(ws + o.aug);
-    float* logit = (float*)(ws + o.logit);
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    int32_t* dummy = (int32_t*)(ws + o.dummy);
+    float *const zs = ws.zs, *const zq = ws.zq, *const zqn = ws.zqn, *const mean = ws.mean, *const eta = ws.eta, *const sup = ws.sup;
+    float *const cnt = ws.cnt, *const wn = ws.wn, *const aug = ws.aug, *const logit = ws.logit, *const cs = ws.cs;
+    float* const wn0 = ws.wn0;                                        // the normalised initial prototypes: wn itself but in a sweep
+    uint8_t* const live = ws.live;
+    int32_t* const dummy = ws.dummy;
     auto rows_grid = [](int n_rows) { return dim3((unsigned)(((size_t)n_rows * 8 + 255) / 256)); };
     auto normalize = [&](const float* x, const float* x2, int R0, int Rr, int mode, const float* mn, const float* sh, float* out) {
         hipLaunchKernelGGL(k_bdcspn_normalize<false>, rows_grid(T * Rr), dim3(256), 0, st, dense_rows(x), x2, R0, Rr, D, mode, mn, sh,
@@ -396,96 +351,15 @@ static int bdcspn_pass(const FeatureSpace& sp, const tclip_problem& p, const Bdc
     return TCLIP_OK;
 }
 
-static const char* const kNullArg = "null pointer argument";
-static const char* const kZeroShotOnly = "%s is a zero-shot method: n_support must be 0";
-static const char* const kFewShotOnly = "%s is a few-shot method: n_support must be positive";
-static const char* const kNormType = "norm_type must be 0 (UN), 1 (L2N) or 2 (CL2N)";
-static const char* const kDimRange = "dim must be in 1..1024";
-
-// the checks the two visual few-shot entries and their workspace queries share
-static int check_visual_fs(const tclip_problem* p, int32_t dim, const char* who) {
-    if (int rc = check_problem(p)) return rc;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, kDimRange);
-    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, who);
-    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)p->n_support + p->n_query;
-    if (T * R * 16 > 0x7fffffffu || T * (size_t)dim > 0x7fffffffu)
-        return fail(TCLIP_ERR_ARG, "%s: tasks * (n_support + n_query) * 16 and tasks * dim must fit in int32", who);
-    return TCLIP_OK;
-}
-
-}  // namespace tclip
-
-extern "C" {
-
-// ---- zero-shot, probability features ------------------------------------------------------------------------------------
-size_t tclip_soft_kmeans_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    return KmeansWs::layout(*p).total;
-}
-
-size_t tclip_hard_kmeans_workspace_bytes(const tclip_problem* p) { return tclip_soft_kmeans_workspace_bytes(p); }
-
-int tclip_soft_kmeans_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* w,
-                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "SOFT_KMEANS");
-    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_soft_kmeans_workspace_bytes")) return rc;
-    return kmeans_loop(FeatureSpace{p.n_class, false}, Kmeans::Soft, p, x_q, x_q, temperature, u, nullptr, w, preds, nullptr,
-                       (char*)workspace, (hipStream_t)stream);
-}
-
-int tclip_em_gaussian_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* v, float* w,
-                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN");
-    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_soft_kmeans_workspace_bytes")) return rc;
-    return kmeans_loop(FeatureSpace{p.n_class, false}, Kmeans::EmGaussian, p, x_q, x_q, temperature, u, v, w, preds, nullptr,
-                       (char*)workspace, (hipStream_t)stream);
-}
-
-int tclip_hard_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
-                          float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !w || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "HARD_KMEANS");
-    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_hard_kmeans_workspace_bytes")) return rc;
-    return kmeans_loop(FeatureSpace{p.n_class, false}, Kmeans::Hard, p, x_q, x_q, 1.0f, u, nullptr, w, preds, criterions,
-                       (char*)workspace, (hipStream_t)stream);
-}
-
-int tclip_em_gaussian_cov_run(const tclip_problem* pp, const float* x_q, float* u, float* v, float* w, float* s,
-                              int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !v || !w || !s || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV");
-    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_soft_kmeans_workspace_bytes")) return rc;
-    return em_gaussian_cov_loop(FeatureSpace{p.n_class, false}, p, x_q, x_q, u, v, w, s, preds, nullptr, (char*)workspace,
-                                (hipStream_t)stream);
-}
-
-// ---- KL_KMEANS: HARD_KMEANS's outputs with KL centroids and divergences
-int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
-                        float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !u || !w || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "KL_KMEANS");
-    const KmeansWs o = KmeansWs::layout(p);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_hard_kmeans_workspace_bytes")) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
+// ---- KL_KMEANS: HARD_KMEANS's outputs with KL centroids and divergences; probability features only.  The 75-column split below
+// is its own arithmetic, not launch_mstats_mode's.  The loop stands behind bdcspn_pass, where the entry that held it stood: the
+// kernel templates of a translation unit are emitted in the order of their first use, and the device code keeps that order.
+static int kl_kmeans_loop(const tclip_problem& p, const float* x_q, float* u, float* w, int32_t* preds, float* criterions,
+                          const KmeansWs& ws, hipStream_t st) {
     const int Q = p.n_query, K = p.n_class, B = p.n_batches, N = p.tasks_per_batch, T = B * N, TK = T * K;
     const size_t TQK = (size_t)T * Q * K;
-    float* cs = (float*)(ws + o.cs);
-    uint8_t* live = (uint8_t*)(ws + o.live);
-    float* divs = (float*)(ws + o.logit);
-    float* change = (float*)(ws + o.change);
+    float *const cs = ws.cs, *const divs = ws.logit, *const change = ws.change;
+    uint8_t* const live = ws.live;
     hipLaunchKernelGGL(k_copy, dim3(ew_grid(TQK)), dim3(256), 0, st, x_q, u, TQK);          // u = z
     for (int it = 0; it < p.iters; it++) {
         hipLaunchKernelGGL(k_cluster_sizes, dim3((TK + 255) / 256), dim3(256), 0, st, (const float*)u, T, Q, K, 1, cs,
@@ -518,245 +392,242 @@ int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, flo
     return TCLIP_OK;
 }
 
-// ---- zero-shot, visual features ---------------------------------------------------------------------------------------
+// ---- the entries: one function per method for all its call forms (`r`: tclip_tim.inc), the checks in the one order of
+// DESIGN.md ("The method host drivers"), then the loop; ws_query: the workspace query the entry's caller was told to use ------
+static const MethodRule kSoftKmeans{"SOFT_KMEANS", false, kZeroShotOnly, nullptr, Limits::None};
+static const MethodRule kEmGaussian{"EM_GAUSSIAN", false, kZeroShotOnly, nullptr, Limits::None};
+static const MethodRule kHardKmeans{"HARD_KMEANS", false, kZeroShotOnly, nullptr, Limits::None};
+static const MethodRule kKlKmeans{"KL_KMEANS", false, kZeroShotOnly, nullptr, Limits::None};
+static const MethodRule kEmGaussianCov{"EM_GAUSSIAN_COV", false, kZeroShotOnly, nullptr, Limits::None};
+static const MethodRule kVisualKmeans{"", false, "the visual k-means methods are zero-shot: n_support must be 0", nullptr, Limits::None};
+static const MethodRule kPaddle{"PADDLE", true, kFewShotOnly, nullptr, Limits::Rows16};
+static const MethodRule kBdcspn{"BDCSPN", true, kFewShotOnly, nullptr, Limits::Rows16};
+
+// SOFT_KMEANS, EM_GAUSSIAN, HARD_KMEANS on either feature kind and KL_KMEANS (probability features); `known`: the visual
+// entry's method code names one of them; u0: the text-prompt assignment of visual features.  v and criterions are needed by the
+// methods that write them.
+static int kmeans_entry(const tclip_problem* pp, const Rows& r, const MethodRule& m, Kmeans kind, bool known, const float* u0,
+                        float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
+                        size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, m)) return rc;
+    if (!known) return fail(TCLIP_ERR_ARG, "unknown method");
+    const bool hard = kind == Kmeans::Hard || kind == Kmeans::Kl;
+    if (int rc = check_pointers(r, m, (u0 || !r.visual) && u && w && preds && workspace && (criterions || !hard) &&
+                                          (v || kind != Kmeans::EmGaussian)))
+        return rc;
+    const tclip_problem p = *pp;
+    if (int rc = check_workspace(workspace, workspace_bytes, kmeans_ws(p, false, nullptr).bytes, ws_query)) return rc;
+    const KmeansWs ws = kmeans_ws(p, false, (char*)workspace);
+    if (kind == Kmeans::Kl) return kl_kmeans_loop(p, r.x_q, u, w, preds, criterions, ws, (hipStream_t)stream);
+    return kmeans_loop(FeatureSpace{r.D(p), r.visual}, kind, p, r.x_q, r.visual ? u0 : r.x_q, temperature, u, v, w, preds, criterions, ws,
+                       (hipStream_t)stream);
+}
+
+static int em_gaussian_cov_entry(const tclip_problem* pp, const Rows& r, const float* u0, float* u, float* v, float* w, float* s,
+                                 int32_t* preds, void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, kEmGaussianCov)) return rc;
+    if (int rc = check_pointers(r, kEmGaussianCov, (u0 || !r.visual) && u && v && w && s && preds && workspace)) return rc;
+    const tclip_problem p = *pp;
+    if (int rc = check_workspace(workspace, workspace_bytes, kmeans_ws(p, r.visual, nullptr).bytes, ws_query)) return rc;
+    return em_gaussian_cov_loop(FeatureSpace{r.D(p), r.visual}, p, r.x_q, r.visual ? u0 : r.x_q, u, v, w, s, preds,
+                                kmeans_ws(p, r.visual, (char*)workspace), (hipStream_t)stream);
+}
+
+// PADDLE.  From the feature tables the queries are gathered (and, probability features, permuted) once into the workspace and
+// the support rows are read in place by the support statistics; then paddle_loop as it stands.
+static int paddle_entry(const tclip_problem* pp, const Rows& r, const int64_t* y_s, float lambd, float* u, float* v, float* w,
+                        int32_t* preds, void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, kPaddle)) return rc;
+    if (int rc = check_pointers(r, kPaddle, y_s && u && v && w && preds && workspace)) return rc;
+    if (int rc = check_values(pp, r)) return rc;
+    const tclip_problem p = *pp;
+    const int D = r.D(p);
+    if (int rc = check_workspace(workspace, workspace_bytes, paddle_ws(p, D, r.tables, nullptr).bytes, ws_query)) return rc;
+    const PaddleWs ws = paddle_ws(p, D, r.tables, (char*)workspace);
+    hipStream_t st = (hipStream_t)stream;
+    // every q_idx value has been checked by the caller (tclip_check_task_indices): no row of ws.xq stays unwritten
+    if (r.tables)
+        launch_gather_task_rows(st, r.src->table_q, INT64_MAX, D, r.src->q_idx, p.n_query, r.src->cols,
+                                (int64_t)p.n_batches * p.tasks_per_batch * p.n_query, ws.xq);
+    return paddle_loop(FeatureSpace{D, r.visual}, p, r.tables ? ws.xq : r.x_q, r.s(), y_s, lambd, u, v, w, preds, ws, st, r.values,
+                       r.n_sweep());
+}
+static size_t paddle_bytes(const tclip_problem* p, const Rows& r) {
+    return query_accepts(p, r, kPaddle) ? paddle_ws(*p, r.D(*p), r.tables, nullptr).bytes : 0;
+}
+
+// BD-CSPN.  From the feature tables bdcspn_pass reads both row sets in place, neither x_s nor x_q is built.
+static int bdcspn_entry(const tclip_problem* pp, const Rows& r, const int64_t* y_s, float temp, int32_t norm_type, float* prototypes,
+                        float* u, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, kBdcspn)) return rc;
+    if (int rc = check_pointers(r, kBdcspn, y_s && prototypes && u && preds && workspace)) return rc;
+    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, "norm_type must be 0 (UN), 1 (L2N) or 2 (CL2N)");
+    if (int rc = check_values(pp, r)) return rc;
+    const tclip_problem p = *pp;
+    const int D = r.D(p);
+    if (int rc = check_workspace(workspace, workspace_bytes, bdcspn_ws(p, D, r.tables, r.sweep, nullptr).bytes, ws_query)) return rc;
+    return bdcspn_pass(FeatureSpace{D, r.visual}, p, bdcspn_ws(p, D, r.tables, r.sweep, (char*)workspace), r.q(), r.s(), y_s, temp,
+                       norm_type, prototypes, u, preds, (hipStream_t)stream, r.values, r.n_sweep());
+}
+static size_t bdcspn_bytes(const tclip_problem* p, const Rows& r) {
+    return query_accepts(p, r, kBdcspn) ? bdcspn_ws(*p, r.D(*p), r.tables, r.sweep, nullptr).bytes : 0;
+}
+
+}  // namespace tclip
+
+extern "C" {
+
+// ---- zero-shot, probability features: the two queries do not look at n_support ------------------------------------------------
+size_t tclip_soft_kmeans_workspace_bytes(const tclip_problem* p) {
+    return query_accepts(p, rows_dense(nullptr, nullptr, kAnySupport), kSoftKmeans) ? kmeans_ws(*p, false, nullptr).bytes : 0;
+}
+
+size_t tclip_hard_kmeans_workspace_bytes(const tclip_problem* p) { return tclip_soft_kmeans_workspace_bytes(p); }
+
+int tclip_soft_kmeans_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* w,
+                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    return kmeans_entry(pp, rows_dense(x_q, nullptr), kSoftKmeans, Kmeans::Soft, true, nullptr, temperature, u, nullptr, w, preds, nullptr,
+                        workspace, workspace_bytes, stream, "tclip_soft_kmeans_workspace_bytes");
+}
+
+int tclip_em_gaussian_run(const tclip_problem* pp, const float* x_q, float temperature, float* u, float* v, float* w,
+                          int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    return kmeans_entry(pp, rows_dense(x_q, nullptr), kEmGaussian, Kmeans::EmGaussian, true, nullptr, temperature, u, v, w, preds, nullptr,
+                        workspace, workspace_bytes, stream, "tclip_soft_kmeans_workspace_bytes");
+}
+
+int tclip_hard_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
+                          float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
+    return kmeans_entry(pp, rows_dense(x_q, nullptr), kHardKmeans, Kmeans::Hard, true, nullptr, 1.0f, u, nullptr, w, preds, criterions,
+                        workspace, workspace_bytes, stream, "tclip_hard_kmeans_workspace_bytes");
+}
+
+// KL_KMEANS: HARD_KMEANS's arguments and outputs, with KL centroids and divergences
+int tclip_kl_kmeans_run(const tclip_problem* pp, const float* x_q, float* u, float* w, int32_t* preds,
+                        float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
+    return kmeans_entry(pp, rows_dense(x_q, nullptr), kKlKmeans, Kmeans::Kl, true, nullptr, 1.0f, u, nullptr, w, preds, criterions,
+                        workspace, workspace_bytes, stream, "tclip_hard_kmeans_workspace_bytes");
+}
+
+int tclip_em_gaussian_cov_run(const tclip_problem* pp, const float* x_q, float* u, float* v, float* w, float* s,
+                              int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    return em_gaussian_cov_entry(pp, rows_dense(x_q, nullptr), nullptr, u, v, w, s, preds, workspace, workspace_bytes, stream,
+                                 "tclip_soft_kmeans_workspace_bytes");
+}
+
+// ---- zero-shot, visual features: the k-means query does not look at n_support, EM_GAUSSIAN_COV's does --------------------------
 size_t tclip_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (dim < 1 || dim > 1024) { fail(TCLIP_ERR_ARG, kDimRange); return 0; }
-    return KmeansWs::layout(*p).total;
+    return query_accepts(p, rows_visual(dim, nullptr, nullptr, kAnySupport), kVisualKmeans) ? kmeans_ws(*p, false, nullptr).bytes : 0;
 }
 
 int tclip_kmeans_visual_run(const tclip_problem* pp, int32_t dim, int32_t method, const float* x_q, const float* u0,
                             float temperature, float* u, float* v, float* w, int32_t* preds, float* criterions, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, kDimRange);
-    if (method != TCLIP_VISUAL_SOFT_KMEANS && method != TCLIP_VISUAL_HARD_KMEANS && method != TCLIP_VISUAL_EM_GAUSSIAN)
-        return fail(TCLIP_ERR_ARG, "unknown method");
+    const bool known = method == TCLIP_VISUAL_SOFT_KMEANS || method == TCLIP_VISUAL_HARD_KMEANS || method == TCLIP_VISUAL_EM_GAUSSIAN;
     const Kmeans kind = method == TCLIP_VISUAL_HARD_KMEANS ? Kmeans::Hard : method == TCLIP_VISUAL_EM_GAUSSIAN ? Kmeans::EmGaussian : Kmeans::Soft;
-    if (!x_q || !u0 || !u || !w || !preds || !workspace || (kind == Kmeans::Hard && !criterions) || (kind == Kmeans::EmGaussian && !v))
-        return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, "the visual k-means methods are zero-shot: n_support must be 0");
-    if (int rc = check_workspace(workspace, workspace_bytes, KmeansWs::layout(p).total, "tclip_visual_workspace_bytes")) return rc;
-    return kmeans_loop(FeatureSpace{dim, true}, kind, p, x_q, u0, temperature, u, v, w, preds, criterions, (char*)workspace,
-                       (hipStream_t)stream);
+    return kmeans_entry(pp, rows_visual(dim, x_q, nullptr), kVisualKmeans, kind, known, u0, temperature, u, v, w, preds, criterions,
+                        workspace, workspace_bytes, stream, "tclip_visual_workspace_bytes");
 }
 
 size_t tclip_em_gaussian_cov_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (dim < 1 || dim > 1024) { fail(TCLIP_ERR_ARG, kDimRange); return 0; }
-    if (p->n_support != 0) { fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV"); return 0; }
-    return CovVisualWs::layout(*p).total;
+    return query_accepts(p, rows_visual(dim, nullptr, nullptr), kEmGaussianCov) ? kmeans_ws(*p, true, nullptr).bytes : 0;
 }
 
 int tclip_em_gaussian_cov_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* u0, float* u, float* v,
                                      float* w, float* s, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, kDimRange);
-    if (!x_q || !u0 || !u || !v || !w || !s || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support != 0) return fail(TCLIP_ERR_ARG, kZeroShotOnly, "EM_GAUSSIAN_COV");
-    const CovVisualWs o = CovVisualWs::layout(p);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, "tclip_em_gaussian_cov_visual_workspace_bytes")) return rc;
-    return em_gaussian_cov_loop(FeatureSpace{dim, true}, p, x_q, u0, u, v, w, s, preds, (float*)((char*)workspace + o.det),
-                                (char*)workspace, (hipStream_t)stream);
+    return em_gaussian_cov_entry(pp, rows_visual(dim, x_q, nullptr), u0, u, v, w, s, preds, workspace, workspace_bytes, stream,
+                                 "tclip_em_gaussian_cov_visual_workspace_bytes");
 }
 
-// ---- few-shot, both feature kinds -------------------------------------------------------------------------------------
-size_t tclip_paddle_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    return PaddleWs::layout(*p, p->n_class).total;
+// ---- PADDLE: the dense probability query does not look at n_support -----------------------------------------------------------
+size_t tclip_paddle_workspace_bytes(const tclip_problem* p) { return paddle_bytes(p, rows_dense(nullptr, nullptr, kAnySupport)); }
+size_t tclip_paddle_tasks_workspace_bytes(const tclip_problem* p) { return paddle_bytes(p, rows_tables(nullptr)); }
+size_t tclip_paddle_visual_workspace_bytes(const tclip_problem* p, int32_t dim) { return paddle_bytes(p, rows_visual(dim, nullptr, nullptr)); }
+size_t tclip_paddle_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return paddle_bytes(p, rows_visual_tables(dim, nullptr));
+}
+size_t tclip_paddle_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    return paddle_bytes(p, rows_sweep(dim, nullptr, nullptr, n_values));
 }
 
 int tclip_paddle_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float lambd,
                      float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
                      void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE");
-    if (int rc = check_workspace(workspace, workspace_bytes, PaddleWs::layout(p, p.n_class).total, "tclip_paddle_workspace_bytes")) return rc;
-    return paddle_loop(FeatureSpace{p.n_class, false}, p, x_q, dense_rows(x_s), y_s, lambd, u, v, w, preds, (char*)workspace,
-                       (hipStream_t)stream);
-}
-
-// PADDLE from the feature tables on rows of `dim` elements: the queries are gathered (and, probability features, permuted)
-// once into the workspace, the support rows are read in place by the support statistics; then paddle_loop as it stands
-// sweep: values / n_values in place of lambd (paddle_loop), checked here
-static int paddle_run_tasks(const FeatureSpace& sp, const tclip_problem& p, const tclip_task_source* src, const int64_t* y_s, float lambd,
-                            float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes, const char* query_name,
-                            hipStream_t st, bool sweep = false, const double* values = nullptr, int n_values = 0) {
-    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !u || !v || !w || !preds || !workspace)
-        return fail(TCLIP_ERR_ARG, kNullArg);
-    if (sp.visual && src->cols) return fail(TCLIP_ERR_ARG, "PADDLE on visual features permutes no columns: cols must be NULL");
-    if (sweep)
-        if (int rc = check_sweep_values(&p, values, n_values)) return rc;
-    const PaddleTasksWs o = PaddleTasksWs::layout(p, sp.D);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, query_name)) return rc;
-    const int64_t T = (int64_t)p.n_batches * p.tasks_per_batch;
-    float* x_q = (float*)((char*)workspace + o.xq);
-    // every q_idx value has been checked by the caller (tclip_check_task_indices): no row of x_q stays unwritten
-    launch_gather_task_rows(st, src->table_q, INT64_MAX, sp.D, src->q_idx, p.n_query, src->cols, T * p.n_query, x_q);
-    return paddle_loop(sp, p, x_q, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, lambd, u, v, w, preds, (char*)workspace, st, values,
-                       n_values);
-}
-
-size_t tclip_paddle_tasks_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (p->n_support < 1) { fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE"); return 0; }
-    return PaddleTasksWs::layout(*p, p->n_class).total;
-}
-
-int tclip_paddle_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, float lambd, float* u, float* v,
-                           float* w, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (pp->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "PADDLE");
-    return paddle_run_tasks(FeatureSpace{pp->n_class, false}, *pp, src, y_s, lambd, u, v, w, preds, workspace, workspace_bytes,
-                            "tclip_paddle_tasks_workspace_bytes", (hipStream_t)stream);
-}
-
-size_t tclip_paddle_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_visual_fs(p, dim, "PADDLE") != TCLIP_OK) return 0;
-    return PaddleWs::layout(*p, dim).total;
+    return paddle_entry(pp, rows_dense(x_q, x_s), y_s, lambd, u, v, w, preds, workspace, workspace_bytes, stream,
+                        "tclip_paddle_workspace_bytes");
 }
 
 int tclip_paddle_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s,
                             float lambd, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
                             void* stream) {
-    if (int rc = check_visual_fs(pp, dim, "PADDLE")) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !x_s || !y_s || !u || !v || !w || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (int rc = check_workspace(workspace, workspace_bytes, PaddleWs::layout(p, dim).total, "tclip_paddle_visual_workspace_bytes")) return rc;
-    return paddle_loop(FeatureSpace{dim, true}, p, x_q, dense_rows(x_s), y_s, lambd, u, v, w, preds, (char*)workspace, (hipStream_t)stream);
+    return paddle_entry(pp, rows_visual(dim, x_q, x_s), y_s, lambd, u, v, w, preds, workspace, workspace_bytes, stream,
+                        "tclip_paddle_visual_workspace_bytes");
 }
 
-size_t tclip_paddle_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_visual_fs(p, dim, "PADDLE") != TCLIP_OK) return 0;
-    return PaddleTasksWs::layout(*p, dim).total;
+int tclip_paddle_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, float lambd, float* u, float* v,
+                           float* w, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
+    return paddle_entry(pp, rows_tables(src), y_s, lambd, u, v, w, preds, workspace, workspace_bytes, stream,
+                        "tclip_paddle_tasks_workspace_bytes");
 }
 
 int tclip_paddle_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, float lambd,
                                   float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_visual_fs(pp, dim, "PADDLE")) return rc;
-    return paddle_run_tasks(FeatureSpace{dim, true}, *pp, src, y_s, lambd, u, v, w, preds, workspace, workspace_bytes,
-                            "tclip_paddle_visual_tasks_workspace_bytes", (hipStream_t)stream);
+    return paddle_entry(pp, rows_visual_tables(dim, src), y_s, lambd, u, v, w, preds, workspace, workspace_bytes, stream,
+                        "tclip_paddle_visual_tasks_workspace_bytes");
 }
 
-size_t tclip_bdcspn_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    return BdcspnWs::layout(*p, p->n_class).total;
+// for a list of lambd values on the same tasks (paddle_loop with `values`)
+int tclip_paddle_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
+                             int32_t n_values, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    return paddle_entry(pp, rows_sweep(dim, src, values, n_values), y_s, 0.0f, u, v, w, preds, workspace, workspace_bytes, stream,
+                        "tclip_paddle_sweep_tasks_workspace_bytes");
+}
+
+// ---- BD-CSPN: the dense probability query does not look at n_support ----------------------------------------------------------
+size_t tclip_bdcspn_workspace_bytes(const tclip_problem* p) { return bdcspn_bytes(p, rows_dense(nullptr, nullptr, kAnySupport)); }
+size_t tclip_bdcspn_tasks_workspace_bytes(const tclip_problem* p) { return bdcspn_bytes(p, rows_tables(nullptr)); }
+size_t tclip_bdcspn_visual_workspace_bytes(const tclip_problem* p, int32_t dim) { return bdcspn_bytes(p, rows_visual(dim, nullptr, nullptr)); }
+size_t tclip_bdcspn_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return bdcspn_bytes(p, rows_visual_tables(dim, nullptr));
+}
+size_t tclip_bdcspn_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    return bdcspn_bytes(p, rows_sweep(dim, nullptr, nullptr, n_values));
 }
 
 int tclip_bdcspn_run(const tclip_problem* pp, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
                      int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
                      size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !x_s || !y_s || !prototypes || !u || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN");
-    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
-    if (int rc = check_workspace(workspace, workspace_bytes, BdcspnWs::layout(p, p.n_class).total, "tclip_bdcspn_workspace_bytes")) return rc;
-    return bdcspn_pass(FeatureSpace{p.n_class, false}, p, BdcspnWs::layout(p, p.n_class), dense_rows(x_q), dense_rows(x_s), y_s, temp,
-                       norm_type, prototypes, u, preds, (char*)workspace, (hipStream_t)stream);
-}
-
-size_t tclip_bdcspn_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_visual_fs(p, dim, "BDCSPN") != TCLIP_OK) return 0;
-    return BdcspnWs::layout(*p, dim).total;
+    return bdcspn_entry(pp, rows_dense(x_q, x_s), y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes, stream,
+                        "tclip_bdcspn_workspace_bytes");
 }
 
 int tclip_bdcspn_visual_run(const tclip_problem* pp, int32_t dim, const float* x_q, const float* x_s, const int64_t* y_s, float temp,
                             int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    if (int rc = check_visual_fs(pp, dim, "BDCSPN")) return rc;
-    const tclip_problem p = *pp;
-    if (!x_q || !x_s || !y_s || !prototypes || !u || !preds || !workspace) return fail(TCLIP_ERR_ARG, kNullArg);
-    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
-    if (int rc = check_workspace(workspace, workspace_bytes, BdcspnWs::layout(p, dim).total, "tclip_bdcspn_visual_workspace_bytes")) return rc;
-    return bdcspn_pass(FeatureSpace{dim, true}, p, BdcspnWs::layout(p, dim), dense_rows(x_q), dense_rows(x_s), y_s, temp, norm_type,
-                       prototypes, u, preds, (char*)workspace, (hipStream_t)stream);
-}
-
-// BD-CSPN from the feature tables on rows of `dim` elements: bdcspn_pass reads both row sets in place, neither x_s nor x_q is
-// built, and zs shares the logit region (BdcspnWs::layout_tasks)
-// sweep: values / n_values in place of temp (bdcspn_pass), checked here
-static int bdcspn_run_tasks(const FeatureSpace& sp, const tclip_problem& p, const tclip_task_source* src, const int64_t* y_s, float temp,
-                            int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace, size_t workspace_bytes,
-                            const char* query_name, hipStream_t st, bool sweep = false, const double* values = nullptr, int n_values = 0) {
-    if (!src || !src->table_q || !src->q_idx || !src->table_s || !src->s_idx || !y_s || !prototypes || !u || !preds || !workspace)
-        return fail(TCLIP_ERR_ARG, kNullArg);
-    if (sp.visual && src->cols) return fail(TCLIP_ERR_ARG, "BDCSPN on visual features permutes no columns: cols must be NULL");
-    if (norm_type < 0 || norm_type > 2) return fail(TCLIP_ERR_ARG, kNormType);
-    if (sweep)
-        if (int rc = check_sweep_values(&p, values, n_values)) return rc;
-    const BdcspnWs o = BdcspnWs::layout_tasks(p, sp.D, sweep);
-    if (int rc = check_workspace(workspace, workspace_bytes, o.total, query_name)) return rc;
-    return bdcspn_pass(sp, p, o, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s, temp,
-                       norm_type, prototypes, u, preds, (char*)workspace, st, values, n_values);
-}
-
-size_t tclip_bdcspn_tasks_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    if (p->n_support < 1) { fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN"); return 0; }
-    return BdcspnWs::layout_tasks(*p, p->n_class).total;
+    return bdcspn_entry(pp, rows_visual(dim, x_q, x_s), y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes, stream,
+                        "tclip_bdcspn_visual_workspace_bytes");
 }
 
 int tclip_bdcspn_run_tasks(const tclip_problem* pp, const tclip_task_source* src, const int64_t* y_s, float temp, int32_t norm_type,
                            float* prototypes, float* u, int32_t* preds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (pp->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, "BDCSPN");
-    return bdcspn_run_tasks(FeatureSpace{pp->n_class, false}, *pp, src, y_s, temp, norm_type, prototypes, u, preds, workspace,
-                            workspace_bytes, "tclip_bdcspn_tasks_workspace_bytes", (hipStream_t)stream);
-}
-
-size_t tclip_bdcspn_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_visual_fs(p, dim, "BDCSPN") != TCLIP_OK) return 0;
-    return BdcspnWs::layout_tasks(*p, dim).total;
+    return bdcspn_entry(pp, rows_tables(src), y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes, stream,
+                        "tclip_bdcspn_tasks_workspace_bytes");
 }
 
 int tclip_bdcspn_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, float temp,
                                   int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    if (int rc = check_visual_fs(pp, dim, "BDCSPN")) return rc;
-    return bdcspn_run_tasks(FeatureSpace{dim, true}, *pp, src, y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes,
-                            "tclip_bdcspn_visual_tasks_workspace_bytes", (hipStream_t)stream);
+    return bdcspn_entry(pp, rows_visual_tables(dim, src), y_s, temp, norm_type, prototypes, u, preds, workspace, workspace_bytes, stream,
+                        "tclip_bdcspn_visual_tasks_workspace_bytes");
 }
 
-// ---- PADDLE and BD-CSPN for a list of values on the same tasks (paddle_loop / bdcspn_pass with `values`): dim == 0 is the
-// problem of tclip_paddle_run_tasks / tclip_bdcspn_run_tasks, dim > 0 that of the _visual_run_tasks entries
-// the checks before `src` is looked at: the problem, dim, and what the entry for this feature kind checks of both
-static int check_sweep_fs(const tclip_problem* p, int32_t dim, const char* who) {
-    if (int rc = check_problem(p)) return rc;
-    if (int rc = check_sweep_dim(dim)) return rc;
-    if (dim > 0) return check_visual_fs(p, dim, who);
-    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, kFewShotOnly, who);
-    return TCLIP_OK;
-}
-
-size_t tclip_paddle_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
-    if (check_sweep_fs(p, dim, "PADDLE") != TCLIP_OK || check_sweep_count(p, n_values) != TCLIP_OK) return 0;
-    return PaddleTasksWs::layout(*p, dim ? dim : p->n_class).total;
-}
-
-int tclip_paddle_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
-                             int32_t n_values, float* u, float* v, float* w, int32_t* preds, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-    if (int rc = check_sweep_fs(pp, dim, "PADDLE")) return rc;
-    return paddle_run_tasks(FeatureSpace{dim ? dim : pp->n_class, dim > 0}, *pp, src, y_s, 0.0f, u, v, w, preds, workspace, workspace_bytes,
-                            "tclip_paddle_sweep_tasks_workspace_bytes", (hipStream_t)stream, true, values, n_values);
-}
-
-size_t tclip_bdcspn_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
-    if (check_sweep_fs(p, dim, "BDCSPN") != TCLIP_OK || check_sweep_count(p, n_values) != TCLIP_OK) return 0;
-    return BdcspnWs::layout_tasks(*p, dim ? dim : p->n_class, true).total;
-}
-
+// for a list of temp values on the same tasks (bdcspn_pass with `values`)
 int tclip_bdcspn_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_task_source* src, const int64_t* y_s, const double* values,
                              int32_t n_values, int32_t norm_type, float* prototypes, float* u, int32_t* preds, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    if (int rc = check_sweep_fs(pp, dim, "BDCSPN")) return rc;
-    return bdcspn_run_tasks(FeatureSpace{dim ? dim : pp->n_class, dim > 0}, *pp, src, y_s, 0.0f, norm_type, prototypes, u, preds, workspace,
-                            workspace_bytes, "tclip_bdcspn_sweep_tasks_workspace_bytes", (hipStream_t)stream, true, values, n_values);
+    return bdcspn_entry(pp, rows_sweep(dim, src, values, n_values), y_s, 0.0f, norm_type, prototypes, u, preds, workspace, workspace_bytes,
+                        stream, "tclip_bdcspn_sweep_tasks_workspace_bytes");
 }
 
 }  // extern "C"

@@ -16,6 +16,10 @@
 // k_tim_gemm_mfma<true> (dW, also the column sums of G), k_tim_adam (one wavefront per weight row), k_tim_criterion.
 // tclip_alpha_tim_sweep_tasks runs the same loop over n_values x tasks solves for a list of alpha values (tim_loop_on with
 // `values`); the helpers all four sweep entries share (check_sweep_*, k_sweep_values) are here too, this file being included first.
+// So is what the host drivers of every method of tclip_tim.inc, tclip_lshot.inc and tclip_methods.inc share: the description of
+// the rows an entry was given (Rows and its five adaptors), a method's MethodRule, and the shared checks in their one order
+// (check_method_problem, check_pointers, check_values; DESIGN.md, "The method host drivers").  Here tim_ws lays the workspace
+// out, alpha_tim_run and tim_gd_run are the one function behind each method's entries, tim_run picks the dense or the table rows.
 
 namespace tclip {
 
@@ -52,6 +56,13 @@ struct TimRows<true> {
     __device__ const int32_t* task_cols(int t) const { return cols ? cols + (size_t)t * D : nullptr; }
 };
 
+// one constant per message that more than one entry gives
+static const char* const kNullArg = "null pointer argument";
+static const char* const kZeroShotOnly = "%s is a zero-shot method: n_support must be 0";
+static const char* const kFewShotOnly = "%s is a few-shot method: n_support must be positive";
+static const char* const kDimRange = "dim must be in 1..1024";
+static const char* const kItersForLogits = "%s needs iters >= 1 (the accuracy is read from the last iteration's logits)";
+
 // ---- value sweeps (tclip_*_sweep_tasks): what the four entries share ---------------------------------------------------------
 // dim of a sweep entry: 0 = probability features (rows of n_class elements), 1..1024 = visual features
 static int check_sweep_dim(int32_t dim) {
@@ -70,11 +81,101 @@ static int check_sweep_count(const tclip_problem* p, int32_t n_values) {
 }
 
 static int check_sweep_values(const tclip_problem* p, const double* values, int32_t n_values) {
-    if (!values) return fail(TCLIP_ERR_ARG, "null pointer argument");
+    if (!values) return fail(TCLIP_ERR_ARG, kNullArg);
     if (int rc = check_sweep_count(p, n_values)) return rc;
     for (int i = 0; i < n_values; i++)
         if (!(values[i] - values[i] == 0.0)) return fail(TCLIP_ERR_ARG, "every value of a sweep must be finite");
     return TCLIP_OK;
+}
+
+// ---- what rows an entry was given, and the checks every method's entries share (DESIGN.md, "The method host drivers") ---------
+// The five call forms of a method differ in three things: the row length, whether the rows are dense tensors or table rows
+// behind a tclip_task_source, and whether a value list replaces the scalar.  One adaptor per form builds the description; a
+// workspace query uses its entry's adaptor with null pointers.
+enum : unsigned {                  // checks an entry leaves out that its siblings make (kept as they were; DESIGN.md lists them)
+    kAnySupport = 1,               // does not look at n_support
+    kAnyIters = 2,                 // does not look at iters
+};
+struct Rows {
+    int32_t dim;                   // the entry's dim argument; 0 where it has none
+    bool visual;                   // rows of dim elements; otherwise of n_class
+    bool tables, sweep;
+    const float *x_q, *x_s;        // dense forms (x_s: few-shot methods)
+    const tclip_task_source* src;  // table forms
+    const double* values;          // sweeps
+    int32_t n_values;
+    unsigned skip;
+    int D(const tclip_problem& p) const { return visual ? dim : p.n_class; }
+    int n_sweep() const { return sweep ? n_values : 0; }
+    RowSrc q() const { return tables ? RowSrc{src->table_q, src->q_idx, src->cols} : dense_rows(x_q); }
+    RowSrc s() const { return tables ? RowSrc{src->table_s, src->s_idx, src->cols} : dense_rows(x_s); }
+};
+static Rows rows_dense(const float* x_q, const float* x_s, unsigned skip = 0) {
+    return Rows{0, false, false, false, x_q, x_s, nullptr, nullptr, 0, skip};
+}
+static Rows rows_visual(int32_t dim, const float* x_q, const float* x_s, unsigned skip = 0) {
+    return Rows{dim, true, false, false, x_q, x_s, nullptr, nullptr, 0, skip};
+}
+static Rows rows_tables(const tclip_task_source* src, unsigned skip = 0) {
+    return Rows{0, false, true, false, nullptr, nullptr, src, nullptr, 0, skip};
+}
+static Rows rows_visual_tables(int32_t dim, const tclip_task_source* src, unsigned skip = 0) {
+    return Rows{dim, true, true, false, nullptr, nullptr, src, nullptr, 0, skip};
+}
+// the sweeps' rule, once: dim == 0 is the problem of the _run_tasks entry, dim > 0 that of the _visual_run_tasks entry
+static Rows rows_sweep(int32_t dim, const tclip_task_source* src, const double* values, int32_t n_values, unsigned skip = 0) {
+    return Rows{dim, dim > 0, true, true, nullptr, nullptr, src, values, n_values, skip};
+}
+
+// a tclip_task_source whose members other than cols are all there
+static bool task_source_complete(const tclip_task_source* src) {
+    return src && src->table_q && src->q_idx && src->table_s && src->s_idx;
+}
+
+// What a method asks of the problem, whichever form it is called in
+enum class Limits { None, Rows, Rows16 };      // int32 limits of the kernels on rows of dim elements
+struct MethodRule {
+    const char* who;
+    bool few_shot;
+    const char* support_text;      // kFewShotOnly / kZeroShotOnly, or the method's own wording
+    const char* iters_text;        // null: iters may be 0
+    Limits limits;
+};
+
+// The checks a run entry and its workspace query share, in the one order of every method: the problem, dim, iters, n_support,
+// the int32 limits; a sweep query adds check_sweep_count.
+static int check_method_problem(const tclip_problem* p, const Rows& r, const MethodRule& m) {
+    if (int rc = check_problem(p)) return rc;
+    if (r.sweep) {
+        if (int rc = check_sweep_dim(r.dim)) return rc;
+    } else if (r.visual && (r.dim < 1 || r.dim > 1024)) {
+        return fail(TCLIP_ERR_ARG, kDimRange);
+    }
+    if (m.iters_text && !(r.skip & kAnyIters) && p->iters < 1) return fail(TCLIP_ERR_ARG, m.iters_text, m.who);
+    if (!(r.skip & kAnySupport) && (p->n_support > 0) != m.few_shot) return fail(TCLIP_ERR_ARG, m.support_text, m.who);
+    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)p->n_support + p->n_query;
+    if (r.visual && m.limits == Limits::Rows && T * R > 0x7fffffffu)
+        return fail(TCLIP_ERR_ARG, "%s: tasks * (n_support + n_query) must fit in int32", m.who);
+    if (r.visual && m.limits == Limits::Rows16 && (T * R * 16 > 0x7fffffffu || T * (size_t)r.dim > 0x7fffffffu))
+        return fail(TCLIP_ERR_ARG, "%s: tasks * (n_support + n_query) * 16 and tasks * dim must fit in int32", m.who);
+    return TCLIP_OK;
+}
+// a workspace query's checks: true when `p` may be laid out
+static bool query_accepts(const tclip_problem* p, const Rows& r, const MethodRule& m) {
+    return check_method_problem(p, r, m) == TCLIP_OK && (!r.sweep || check_sweep_count(p, r.n_values) == TCLIP_OK);
+}
+
+// The rows' own pointers and every other pointer of the entry (`others`), then "cols must be NULL on visual features"
+static int check_pointers(const Rows& r, const MethodRule& m, bool others, bool cols_allowed = false) {
+    const bool rows = r.tables ? task_source_complete(r.src) : r.x_q && (r.x_s || !m.few_shot);
+    if (!rows || !others) return fail(TCLIP_ERR_ARG, kNullArg);
+    if (r.tables && r.visual && r.src->cols && !cols_allowed)
+        return fail(TCLIP_ERR_ARG, "%s on visual features permutes no columns: cols must be NULL", m.who);
+    return TCLIP_OK;
+}
+// a sweep's value list (the workspace check follows)
+static int check_values(const tclip_problem* p, const Rows& r) {
+    return r.sweep ? check_sweep_values(p, r.values, r.n_values) : TCLIP_OK;
 }
 
 // The values on the device for the kernels that read one per solve: kSweepChunk of them per launch as a kernel argument.  (A
@@ -494,31 +595,33 @@ __global__ void k_tim_criterion(const float* __restrict__ moved, int n, float* _
     if (threadIdx.x == 0) out[(size_t)blockIdx.x * stride] = part[0] / (float)n;
 }
 
-struct TimWs { size_t sup, cnt, P, xn, wn, marg, cs, dW, M, V, moved, alphas, total; };
+// The workspace of both methods as typed pointers; a null `base` gives `bytes` alone.
 // n_values > 0 (the sweep entry): the support class sums stay per task; every other region holds n_values * tasks solves, and
 // the values follow as floats.  A region takes a whole number of 256-byte units PER VALUE (more than its contiguous contents
 // need), so that the total is affine in n_values.
-static TimWs tim_ws(const tclip_problem& p, int dim, int n_values = 0) {
-    const size_t K = p.n_class, R = (size_t)p.n_support + p.n_query, D = dim;
-    size_t T = (size_t)p.n_batches * p.tasks_per_batch;
-    TimWs w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
-    w.sup = take(T * K * D * 4);
-    w.cnt = take(T * K * 4);
+struct TimWs {
+    float *sup, *cnt, *P, *xn, *wn, *marg, *cs, *dW, *M, *V, *moved, *alphas;
+    size_t bytes;
+};
+static TimWs tim_ws(const tclip_problem& p, int dim, int n_values, char* base) {
+    const size_t K = p.n_class, R = (size_t)p.n_support + p.n_query, D = dim, T = (size_t)p.n_batches * p.tasks_per_batch;
     const size_t P = n_values > 0 ? (size_t)n_values : 1;
-    auto take_per_value = [&](size_t bytes) { return take(P * align_up(bytes)); };
-    w.P = take_per_value(T * R * K * 4);
-    w.xn = take_per_value(T * R * 4);
-    w.wn = take_per_value(T * K * 4);
-    w.marg = take_per_value(T * K * 4);
-    w.cs = take_per_value(T * K * 4);
-    w.dW = take_per_value(T * K * D * 4);
-    w.M = take_per_value(T * K * D * 4);
-    w.V = take_per_value(T * K * D * 4);
-    w.moved = take_per_value(T * K * 4);
-    w.alphas = n_values > 0 ? take_per_value(4) : 0;
-    w.total = o;
+    TimWs w;
+    WsCursor c{base};
+    auto take_per_value = [&](float*& ptr, size_t bytes, bool present = true) { c.take(ptr, P * align_up(bytes), present); };
+    c.take(w.sup, T * K * D * 4);
+    c.take(w.cnt, T * K * 4);
+    take_per_value(w.P, T * R * K * 4);
+    take_per_value(w.xn, T * R * 4);
+    take_per_value(w.wn, T * K * 4);
+    take_per_value(w.marg, T * K * 4);
+    take_per_value(w.cs, T * K * 4);
+    take_per_value(w.dW, T * K * D * 4);
+    take_per_value(w.M, T * K * D * 4);
+    take_per_value(w.V, T * K * D * 4);
+    take_per_value(w.moved, T * K * 4);
+    take_per_value(w.alphas, 4, n_values > 0);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -534,24 +637,13 @@ static TimWs tim_ws(const tclip_problem& p, int dim, int n_values = 0) {
 template <bool kIdx>
 static int tim_loop_on(const tclip_problem& p, const TimRows<kIdx>& X, const RowSrc& x_s, double lr, float temp, const TimLoss& loss,
                        bool per_task, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
-                       char* ws, hipStream_t st, const double* values = nullptr, int n_values = 0) {
+                       const TimWs& ws, hipStream_t st, const double* values = nullptr, int n_values = 0) {
     const int D = X.D;
-    const TimWs o = tim_ws(p, D, values ? n_values : 0);
     const int n_real = p.n_batches * p.tasks_per_batch, n_sweep = values ? n_values : 1;      // n_sweep * n_real <= 65535 (checked)
     const int Q = p.n_query, K = p.n_class, S = p.n_support, R = S + Q, B = p.n_batches * n_sweep, N = p.tasks_per_batch, T = B * N, TK = T * K;
     const int TR = T * R;
-    float* sup = (float*)(ws + o.sup);
-    float* cnt = (float*)(ws + o.cnt);
-    float* P = (float*)(ws + o.P);
-    float* xn = (float*)(ws + o.xn);
-    float* wn = (float*)(ws + o.wn);
-    float* marg = (float*)(ws + o.marg);
-    float* cs = (float*)(ws + o.cs);
-    float* dW = (float*)(ws + o.dW);
-    float* M = (float*)(ws + o.M);
-    float* V = (float*)(ws + o.V);
-    float* moved = (float*)(ws + o.moved);
-    float* alphas = values ? (float*)(ws + o.alphas) : nullptr;
+    float *const sup = ws.sup, *const cnt = ws.cnt, *const P = ws.P, *const xn = ws.xn, *const wn = ws.wn, *const marg = ws.marg;
+    float *const cs = ws.cs, *const dW = ws.dW, *const M = ws.M, *const V = ws.V, *const moved = ws.moved, *const alphas = ws.alphas;
     if (values) launch_sweep_values(st, values, n_values, nullptr, alphas);
     const int tiles_k = (K + kTimTile - 1) / kTimTile, tiles_r = (R + kTimTile - 1) / kTimTile, tiles_d = (D + kTimTile - 1) / kTimTile;
     // init_weights (tim.py:115-134, :218-238): the class means of the support set (of the n_real tasks; one copy per value); Adam
@@ -592,205 +684,142 @@ static int tim_loop_on(const tclip_problem& p, const TimRows<kIdx>& X, const Row
     return TCLIP_OK;
 }
 
-// x_q, x_s: dense tensors, or (idx != nullptr) the feature tables with the task-batch loop's index tensors and, at D = K, its
-// column permutation: both row sets are then read in place in every step, with the dense workspace and the dense launches.
-static int tim_loop(const tclip_problem& p, int D, double lr, float temp, const TimLoss& loss, bool per_task, const RowSrc& x_q,
-                    const RowSrc& x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
-                    char* ws, hipStream_t st) {
-    if (x_s.idx != nullptr)
-        return tim_loop_on(p, TimRows<true>{x_s.base, x_q.base, x_s.idx, x_q.idx, x_s.cols, p.n_support, p.n_query, D}, x_s, lr, temp,
-                           loss, per_task, y_s, weights, logits_q, preds, criterions, ws, st);
-    return tim_loop_on(p, TimRows<false>{x_s.base, x_q.base, p.n_support, p.n_query, D}, x_s, lr, temp, loss, per_task, y_s, weights,
-                       logits_q, preds, criterions, ws, st);
+// The rule of each method, and its one entry: the checks in the one order of DESIGN.md ("The method host drivers"), then the loop
+// on the rows as given - dense, or the feature tables read in place in every step (TimRows<true>), with the dense workspace and
+// the dense launches; a sweep (ALPHA_TIM) runs n_values * tasks solves of it.
+static const MethodRule kAlphaTim{"ALPHA_TIM", true, kFewShotOnly, kItersForLogits, Limits::Rows};
+static const MethodRule kTimGd{"TIM_GD", true, kFewShotOnly, kItersForLogits, Limits::Rows};
+
+struct TimOutputs {
+    float *weights, *logits_q;
+    int32_t* preds;
+    float* criterions;
+    bool given() const { return weights && logits_q && preds && criterions; }
+};
+
+static int tim_run(const tclip_problem& p, const Rows& r, double lr, float temp, const TimLoss& loss, bool per_task, const int64_t* y_s,
+                   const TimOutputs& out, void* workspace, void* stream) {
+    const int D = r.D(p);
+    const TimWs ws = tim_ws(p, D, r.n_sweep(), (char*)workspace);
+    const RowSrc x_q = r.q(), x_s = r.s();
+    if (r.tables)
+        return tim_loop_on(p, TimRows<true>{x_s.base, x_q.base, x_s.idx, x_q.idx, x_s.cols, p.n_support, p.n_query, D,
+                                            r.sweep ? p.n_batches * p.tasks_per_batch : 0},
+                           x_s, lr, temp, loss, per_task, y_s, out.weights, out.logits_q, out.preds, out.criterions, ws,
+                           (hipStream_t)stream, r.values, r.n_sweep());
+    return tim_loop_on(p, TimRows<false>{x_s.base, x_q.base, p.n_support, p.n_query, D}, x_s, lr, temp, loss, per_task, y_s, out.weights,
+                       out.logits_q, out.preds, out.criterions, ws, (hipStream_t)stream);
 }
 
-// what tclip_tim_gd_run and its workspace query check of the problem
-static int check_tim_gd(const tclip_problem* p, int32_t dim) {
-    if (int rc = check_problem(p)) return rc;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
-    if (p->iters < 1) return fail(TCLIP_ERR_ARG, "TIM_GD needs iters >= 1 (the accuracy is read from the last iteration's logits)");
-    if (p->n_support < 1) return fail(TCLIP_ERR_ARG, "TIM_GD is a few-shot method: n_support must be positive");
-    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)p->n_support + p->n_query;
-    if (T * R > 0x7fffffffu) return fail(TCLIP_ERR_ARG, "TIM_GD: tasks * (n_support + n_query) must fit in int32");
-    return TCLIP_OK;
-}
-
-// ALPHA_TIM on rows of D elements: the checks and the loop of all four entries (ws_query: the workspace query to name); x_q and
-// x_s dense, or the feature tables (the members of a tclip_task_source, checked by alpha_tim_run_tasks)
-static int alpha_tim_run(const tclip_problem* pp, int D, const tclip_tim_params* prm, const RowSrc& x_q, const RowSrc& x_s,
-                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions, void* workspace,
-                         size_t workspace_bytes, void* stream, const char* ws_query) {
-    const tclip_problem p = *pp;
-    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM needs iters >= 1 (the accuracy is read from the last iteration's logits)");
-    if (!prm || !x_q.base || !x_s.base || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM is a few-shot method: n_support must be positive");
+// ALPHA_TIM, all five forms (ws_query: the workspace query to name).  A sweep does not read prm->alpha_value.
+static int alpha_tim_run(const tclip_problem* pp, const Rows& r, const tclip_tim_params* prm, const int64_t* y_s, const TimOutputs& out,
+                         void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, kAlphaTim)) return rc;
+    if (int rc = check_pointers(r, kAlphaTim, prm && y_s && out.given() && workspace)) return rc;
     for (int i = 0; i < 3; i++)
         if (prm->entropies[i] != TCLIP_TIM_SHANNON && prm->entropies[i] != TCLIP_TIM_ALPHA)
             return fail(TCLIP_ERR_ARG, "entropies must be TCLIP_TIM_SHANNON or TCLIP_TIM_ALPHA");
+    if (int rc = check_values(pp, r)) return rc;
     const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
-    if (any_alpha && !(prm->alpha_value != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
-    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, D).total, ws_query)) return rc;
-    const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], prm->alpha_value,
+    for (int i = 0; i < (r.sweep ? r.n_values : 1); i++)
+        if (any_alpha && !((r.sweep ? (float)r.values[i] : prm->alpha_value) != 1.0f))
+            return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(*pp, r.D(*pp), r.n_sweep(), nullptr).bytes, ws_query)) return rc;
+    const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], r.sweep ? 0.0f : prm->alpha_value,
                        prm->entropies[0], prm->entropies[1], prm->entropies[2]};
-    return tim_loop(p, D, prm->lr, prm->temp, loss, false, x_q, x_s, y_s, weights, logits_q, preds, criterions,
-                    (char*)workspace, (hipStream_t)stream);
+    return tim_run(*pp, r, prm->lr, prm->temp, loss, false, y_s, out, workspace, stream);
+}
+static size_t alpha_tim_bytes(const tclip_problem* p, const Rows& r) {
+    return query_accepts(p, r, kAlphaTim) ? tim_ws(*p, r.D(*p), r.n_sweep(), nullptr).bytes : 0;
 }
 
-// a tclip_task_source whose members other than cols are all there
-static bool task_source_complete(const tclip_task_source* src) {
-    return src && src->table_q && src->q_idx && src->table_s && src->s_idx;
-}
-
-// The ALPHA_TIM entries fed from the feature tables: `src` in place of x_q / x_s, then alpha_tim_run
-static int alpha_tim_run_tasks(const tclip_problem* pp, int D, bool visual, const tclip_tim_params* prm, const tclip_task_source* src,
-                               const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
-                               void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
-    if (!task_source_complete(src)) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "ALPHA_TIM on visual features permutes no columns: cols must be NULL");
-    return alpha_tim_run(pp, D, prm, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols}, y_s,
-                         weights, logits_q, preds, criterions, workspace, workspace_bytes, stream, ws_query);
-}
-
-// what tclip_alpha_tim_visual_run and its workspace query check of the problem
-static int check_alpha_tim_visual(const tclip_problem* p, int32_t dim) {
-    if (int rc = check_problem(p)) return rc;
-    if (dim < 1 || dim > 1024) return fail(TCLIP_ERR_ARG, "dim must be in 1..1024");
-    const size_t T = (size_t)p->n_batches * p->tasks_per_batch, R = (size_t)(p->n_support > 0 ? p->n_support : 0) + p->n_query;
-    if (T * R > 0x7fffffffu) return fail(TCLIP_ERR_ARG, "ALPHA_TIM: tasks * (n_support + n_query) must fit in int32");
-    return TCLIP_OK;
+// TIM_GD, both forms: dim is always given (dim == n_class: probability features, the only rows whose columns are permuted)
+static int tim_gd_run(const tclip_problem* pp, const Rows& r, double lr, float temp, const float loss_weights[3], const int64_t* y_s,
+                      const TimOutputs& out, void* workspace, size_t workspace_bytes, void* stream, const char* ws_query) {
+    if (int rc = check_method_problem(pp, r, kTimGd)) return rc;
+    if (int rc = check_pointers(r, kTimGd, loss_weights && y_s && out.given() && workspace, true)) return rc;
+    if (r.tables && r.src->cols && r.dim != pp->n_class)
+        return fail(TCLIP_ERR_ARG, "TIM_GD permutes columns on probability features only: cols must be NULL unless dim == n_class");
+    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(*pp, r.dim, 0, nullptr).bytes, ws_query)) return rc;
+    // tim.py:166-175: all three entropies Shannon, the marginal one with 1e-12 inside its logarithm
+    const TimLoss loss{loss_weights[0], loss_weights[1], loss_weights[2], 0.0f, TCLIP_TIM_SHANNON, kTimMarginalGd, TCLIP_TIM_SHANNON};
+    return tim_run(*pp, r, lr, temp, loss, true, y_s, out, workspace, stream);
 }
 
 }  // namespace tclip
 
 extern "C" {
 
-size_t tclip_alpha_tim_workspace_bytes(const tclip_problem* p) {
-    if (check_problem(p) != TCLIP_OK) return 0;
-    return tim_ws(*p, p->n_class).total;
+// ---- ALPHA_TIM.  Its queries look at neither iters nor n_support.  The _tasks forms read the task rows in place in
+// k_tim_row_sqnorm, the two GEMMs of every Adam step and the class sums of init_weights; neither x_s nor x_q is built, workspace
+// and checks are the dense entries'.
+constexpr unsigned kAlphaTimQuery = kAnyIters | kAnySupport;
+size_t tclip_alpha_tim_workspace_bytes(const tclip_problem* p) { return alpha_tim_bytes(p, rows_dense(nullptr, nullptr, kAlphaTimQuery)); }
+size_t tclip_alpha_tim_tasks_workspace_bytes(const tclip_problem* p) { return alpha_tim_bytes(p, rows_tables(nullptr, kAlphaTimQuery)); }
+size_t tclip_alpha_tim_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return alpha_tim_bytes(p, rows_visual(dim, nullptr, nullptr, kAlphaTimQuery));
+}
+size_t tclip_alpha_tim_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return alpha_tim_bytes(p, rows_visual_tables(dim, nullptr, kAlphaTimQuery));
+}
+size_t tclip_alpha_tim_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
+    return alpha_tim_bytes(p, rows_sweep(dim, nullptr, nullptr, n_values, kAlphaTimQuery));
 }
 
 int tclip_alpha_tim_run(const tclip_problem* pp, const tclip_tim_params* prm, const float* x_q, const float* x_s,
                         const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    return alpha_tim_run(pp, pp->n_class, prm, dense_rows(x_q), dense_rows(x_s), y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
+    return alpha_tim_run(pp, rows_dense(x_q, x_s), prm, y_s, {weights, logits_q, preds, criterions}, workspace, workspace_bytes, stream,
                          "tclip_alpha_tim_workspace_bytes");
-}
-
-size_t tclip_alpha_tim_visual_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_alpha_tim_visual(p, dim) != TCLIP_OK) return 0;
-    return tim_ws(*p, dim).total;
 }
 
 int tclip_alpha_tim_visual_run(const tclip_problem* pp, int32_t dim, const tclip_tim_params* prm, const float* x_q, const float* x_s,
                                const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
-    return alpha_tim_run(pp, dim, prm, dense_rows(x_q), dense_rows(x_s), y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
-                         "tclip_alpha_tim_visual_workspace_bytes");
+    return alpha_tim_run(pp, rows_visual(dim, x_q, x_s), prm, y_s, {weights, logits_q, preds, criterions}, workspace, workspace_bytes,
+                         stream, "tclip_alpha_tim_visual_workspace_bytes");
 }
-
-size_t tclip_tim_gd_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    if (check_tim_gd(p, dim) != TCLIP_OK) return 0;
-    return tim_ws(*p, dim).total;
-}
-
-int tclip_tim_gd_run(const tclip_problem* pp, int32_t dim, double lr, float temp, const float loss_weights[3], const float* x_q,
-                     const float* x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_tim_gd(pp, dim)) return rc;
-    const tclip_problem p = *pp;
-    if (!loss_weights || !x_q || !x_s || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, dim).total, "tclip_tim_gd_workspace_bytes")) return rc;
-    // tim.py:166-175: all three entropies Shannon, the marginal one with 1e-12 inside its logarithm
-    const TimLoss loss{loss_weights[0], loss_weights[1], loss_weights[2], 0.0f, TCLIP_TIM_SHANNON, kTimMarginalGd, TCLIP_TIM_SHANNON};
-    return tim_loop(p, dim, lr, temp, loss, true, dense_rows(x_q), dense_rows(x_s), y_s, weights, logits_q, preds, criterions,
-                    (char*)workspace, (hipStream_t)stream);
-}
-
-// ---- ALPHA_TIM and TIM_GD fed from the feature tables: k_tim_row_sqnorm, the two GEMMs of every Adam step and the class sums of
-// init_weights read the task rows in place, neither x_s nor x_q is built; workspace and checks are the dense entries'
-size_t tclip_alpha_tim_tasks_workspace_bytes(const tclip_problem* p) { return tclip_alpha_tim_workspace_bytes(p); }
 
 int tclip_alpha_tim_run_tasks(const tclip_problem* pp, const tclip_tim_params* prm, const tclip_task_source* src, const int64_t* y_s,
                               float* weights, float* logits_q, int32_t* preds, float* criterions, void* workspace,
                               size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    return alpha_tim_run_tasks(pp, pp->n_class, false, prm, src, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes,
-                               stream, "tclip_alpha_tim_tasks_workspace_bytes");
-}
-
-size_t tclip_alpha_tim_visual_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) {
-    return tclip_alpha_tim_visual_workspace_bytes(p, dim);
+    return alpha_tim_run(pp, rows_tables(src), prm, y_s, {weights, logits_q, preds, criterions}, workspace, workspace_bytes, stream,
+                         "tclip_alpha_tim_tasks_workspace_bytes");
 }
 
 int tclip_alpha_tim_visual_run_tasks(const tclip_problem* pp, int32_t dim, const tclip_tim_params* prm, const tclip_task_source* src,
                                      const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
-    return alpha_tim_run_tasks(pp, dim, true, prm, src, y_s, weights, logits_q, preds, criterions, workspace, workspace_bytes, stream,
-                               "tclip_alpha_tim_visual_tasks_workspace_bytes");
+    return alpha_tim_run(pp, rows_visual_tables(dim, src), prm, y_s, {weights, logits_q, preds, criterions}, workspace, workspace_bytes,
+                         stream, "tclip_alpha_tim_visual_tasks_workspace_bytes");
 }
 
-// ---- ALPHA_TIM for a list of alpha values on the same tasks (see tim_loop_on): dim == 0 is tclip_alpha_tim_run_tasks' problem,
-// dim > 0 tclip_alpha_tim_visual_run_tasks'; prm->alpha_value is not read
-size_t tclip_alpha_tim_sweep_tasks_workspace_bytes(const tclip_problem* p, int32_t dim, int32_t n_values) {
-    if (check_problem(p) != TCLIP_OK || check_sweep_dim(dim) != TCLIP_OK) return 0;
-    if (dim > 0 && check_alpha_tim_visual(p, dim) != TCLIP_OK) return 0;
-    if (check_sweep_count(p, n_values) != TCLIP_OK) return 0;
-    return tim_ws(*p, dim ? dim : p->n_class, n_values).total;
-}
-
+// ALPHA_TIM for a list of alpha values on the same tasks (see tim_loop_on)
 int tclip_alpha_tim_sweep_tasks(const tclip_problem* pp, int32_t dim, const tclip_tim_params* prm, const tclip_task_source* src,
                                 const int64_t* y_s, const double* values, int32_t n_values, float* weights, float* logits_q,
                                 int32_t* preds, float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_problem(pp)) return rc;
-    if (int rc = check_sweep_dim(dim)) return rc;
-    const bool visual = dim > 0;
-    if (visual)
-        if (int rc = check_alpha_tim_visual(pp, dim)) return rc;
-    if (!task_source_complete(src)) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (visual && src->cols) return fail(TCLIP_ERR_ARG, "ALPHA_TIM on visual features permutes no columns: cols must be NULL");
-    const tclip_problem p = *pp;
-    if (p.iters < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM needs iters >= 1 (the accuracy is read from the last iteration's logits)");
-    if (!prm || !y_s || !weights || !logits_q || !preds || !criterions || !workspace) return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (p.n_support < 1) return fail(TCLIP_ERR_ARG, "ALPHA_TIM is a few-shot method: n_support must be positive");
-    for (int i = 0; i < 3; i++)
-        if (prm->entropies[i] != TCLIP_TIM_SHANNON && prm->entropies[i] != TCLIP_TIM_ALPHA)
-            return fail(TCLIP_ERR_ARG, "entropies must be TCLIP_TIM_SHANNON or TCLIP_TIM_ALPHA");
-    if (int rc = check_sweep_values(pp, values, n_values)) return rc;
-    const bool any_alpha = prm->entropies[0] || prm->entropies[1] || prm->entropies[2];
-    for (int i = 0; i < n_values; i++)
-        if (any_alpha && !((float)values[i] != 1.0f)) return fail(TCLIP_ERR_ARG, "alpha_value must differ from 1 for an Alpha entropy");
-    const int D = visual ? dim : p.n_class;
-    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, D, n_values).total, "tclip_alpha_tim_sweep_tasks_workspace_bytes"))
-        return rc;
-    const TimLoss loss{prm->loss_weights[0], prm->loss_weights[1], prm->loss_weights[2], 0.0f,
-                       prm->entropies[0], prm->entropies[1], prm->entropies[2]};
-    const RowSrc x_s{src->table_s, src->s_idx, src->cols};
-    const TimRows<true> X{src->table_s, src->table_q, src->s_idx, src->q_idx, src->cols, p.n_support, p.n_query, D,
-                          p.n_batches * p.tasks_per_batch};
-    return tim_loop_on(p, X, x_s, prm->lr, prm->temp, loss, false, y_s, weights, logits_q, preds, criterions, (char*)workspace,
-                       (hipStream_t)stream, values, n_values);
+    return alpha_tim_run(pp, rows_sweep(dim, src, values, n_values), prm, y_s, {weights, logits_q, preds, criterions}, workspace,
+                         workspace_bytes, stream, "tclip_alpha_tim_sweep_tasks_workspace_bytes");
 }
 
+// ---- TIM_GD: the queries make every check of the problem that the entries make
+size_t tclip_tim_gd_workspace_bytes(const tclip_problem* p, int32_t dim) {
+    return query_accepts(p, rows_visual(dim, nullptr, nullptr), kTimGd) ? tim_ws(*p, dim, 0, nullptr).bytes : 0;
+}
 size_t tclip_tim_gd_tasks_workspace_bytes(const tclip_problem* p, int32_t dim) { return tclip_tim_gd_workspace_bytes(p, dim); }
+
+int tclip_tim_gd_run(const tclip_problem* pp, int32_t dim, double lr, float temp, const float loss_weights[3], const float* x_q,
+                     const float* x_s, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds, float* criterions,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return tim_gd_run(pp, rows_visual(dim, x_q, x_s), lr, temp, loss_weights, y_s, {weights, logits_q, preds, criterions}, workspace,
+                      workspace_bytes, stream, "tclip_tim_gd_workspace_bytes");
+}
 
 int tclip_tim_gd_run_tasks(const tclip_problem* pp, int32_t dim, double lr, float temp, const float loss_weights[3],
                            const tclip_task_source* src, const int64_t* y_s, float* weights, float* logits_q, int32_t* preds,
                            float* criterions, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_tim_gd(pp, dim)) return rc;
-    const tclip_problem p = *pp;
-    if (!loss_weights || !task_source_complete(src) || !y_s || !weights || !logits_q || !preds || !criterions || !workspace)
-        return fail(TCLIP_ERR_ARG, "null pointer argument");
-    if (src->cols && dim != p.n_class)
-        return fail(TCLIP_ERR_ARG, "TIM_GD permutes columns on probability features only: cols must be NULL unless dim == n_class");
-    if (int rc = check_workspace(workspace, workspace_bytes, tim_ws(p, dim).total, "tclip_tim_gd_tasks_workspace_bytes")) return rc;
-    const TimLoss loss{loss_weights[0], loss_weights[1], loss_weights[2], 0.0f, TCLIP_TIM_SHANNON, kTimMarginalGd, TCLIP_TIM_SHANNON};
-    return tim_loop(p, dim, lr, temp, loss, true, RowSrc{src->table_q, src->q_idx, src->cols}, RowSrc{src->table_s, src->s_idx, src->cols},
-                    y_s, weights, logits_q, preds, criterions, (char*)workspace, (hipStream_t)stream);
+    return tim_gd_run(pp, rows_visual_tables(dim, src), lr, temp, loss_weights, y_s, {weights, logits_q, preds, criterions}, workspace,
+                      workspace_bytes, stream, "tclip_tim_gd_tasks_workspace_bytes");
 }
 
 }  // extern "C"
